@@ -1,12 +1,16 @@
 #!/usr/bin/env python
 """bench.py -- fused 3-D query points / second of the d3fields field query on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is ONE pass of the hot path (Fusion.batch_eval == one fused HIP launch) over one
 batch of synthetic query points, with every input already resident in HBM.  Rank 0 prints ONE
-JSON line (contract in the task statement) carrying `roofline` and, at N=1, `cpu_baseline`.
+JSON line.  A plain run sets up, warms up, times the K steps and prints the headline (`value`,
+`ms_per_step`, ...); `--dump-outputs DIR` also writes what the last timed step returned.  `--full`
+adds everything else: device-event and fused-kernel times, `roofline` (traffic measured in the run),
+the cached-order / static-map figures, the multi-rank figures, the oracle check and, at N=1,
+`cpu_baseline`.
 
 Workloads (BASELINE.json configs; no datasets/checkpoints offline -> random maps of the same
 shape):
@@ -27,7 +31,7 @@ shape):
             fused_eval_dist_kernel (VALU issue of the arithmetic the contract fixes; depth lookups in a tiled copy)
 The default workload is c2_dense for EVERY --gpus N (weak scaling: the same per-GPU work at every N, so that the values of
 `bench.py --gpus 1/2/4/8` form one curve); `--workload c4_patch --gpus N` is BASELINE.json's eight-GPU configuration, whose N = 1
-point is `--gpus 1 --workload c4_patch`.  Every N > 1 line also carries rank 0's single-rank figure of the SAME workload
+point is `--gpus 1 --workload c4_patch`.  Every N > 1 line of a --full run also carries rank 0's single-rank figure of the SAME workload
 (`single_rank_points_per_s_same_workload`, measured alone before the group run) and `value_full_field` (the whole field
 reassembled on every GPU) beside `value` (compute + the `dist` / `valid_mask` gather).
 Multi-GPU: weak scaling -- every rank queries its own shard of N points against replicated
@@ -125,7 +129,8 @@ def traffic_in_this_run(argv_workload, kernel_hint, timeout_s=150):
         for counter in ("FETCH_SIZE", "WRITE_SIZE"):
             out = os.path.join(tmp, counter)
             cmd = [exe, "--kernel-trace", "--pmc", counter, "-d", out, "-o", "pmc", "--output-format", "csv", "--", sys.executable,
-                   os.path.abspath(__file__)] + argv_workload + ["--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--no-verify", "--traffic", "off"]
+                   os.path.abspath(__file__)] + argv_workload + ["--steps", "4", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-verify",
+                                                                 "--traffic", "off"]
             env = dict(os.environ, TMPDIR=tmp)
             try:
                 subprocess.run(cmd, cwd=tmp, env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=timeout_s, check=False)
@@ -230,6 +235,39 @@ def time_steps(fn, steps, dist_on, dev, drain=None):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     return dt
+
+
+DUMP_BUDGET_BYTES = 60 * 1000 * 1000        # what --dump-outputs writes in all stays below 64 MB
+WARMUP_MAX_S = 5.0                          # a plain run's untimed calls before the warm-up steps, at most (see main)
+
+
+def dump_outputs(out, n, path, seed=0):
+    """--dump-outputs: every tensor of `out` (what the last timed step returned) as <path>/<name>.npy, in float32, or float64
+    where float32 would not hold the values exactly (int32 / int64 indices, float64).  When the outputs exceed
+    DUMP_BUDGET_BYTES, those with one row per query point are cut to one seeded sample of rows, the same rows for all of
+    them: one row drawn from each of k equal strata of [0, n), so that two builds run with the same arguments write the
+    same rows and can be compared array for array.  Returns {name: shape written}."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v for k, v in out.items() if torch.is_tensor(v)}
+    wide = (torch.int32, torch.int64, torch.float64)
+    size = {k: (8 if v.dtype in wide else 4) * v.numel() for k, v in arrays.items()}
+    rows = [k for k, v in arrays.items() if v.dim() >= 1 and v.shape[0] == n and n > 0]
+    idx = None
+    if sum(size.values()) > DUMP_BUDGET_BYTES and rows:
+        per_row = sum(size[k] for k in rows) / n
+        k = max(1, min(n, int((DUMP_BUDGET_BYTES - sum(size[r] for r in size if r not in rows)) // per_row)))
+        start = np.arange(k, dtype=np.int64) * n // k
+        width = (np.arange(1, k + 1, dtype=np.int64) * n // k) - start
+        idx = torch.from_numpy(start + (np.random.default_rng(seed).random(k) * width).astype(np.int64))
+    shapes = {}
+    for name, v in arrays.items():
+        if idx is not None and name in rows:
+            v = v.index_select(0, idx.to(v.device))
+        a = v.detach().cpu().numpy().astype(np.float64 if v.dtype in wide else np.float32)
+        np.save(os.path.join(path, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
 
 
 def verify_against_oracle(f, pts, names, w, sc, out, sample=2000):
@@ -399,6 +437,11 @@ def main():
                     "point-to-point form of the all-gather)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend; 'gloo' lets the N>1 code path be "
                     "exercised with several ranks on ONE GPU (testing only)")
+    ap.add_argument("--full", action="store_true", help="measure and check everything besides the headline: device-event and "
+                    "fused-kernel times, roofline (--traffic), cached-order / static-map figures, the N>1 figures, the oracle check "
+                    "(--no-verify) and the CPU baseline (--no-cpu-baseline); a plain run times the K steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one returned "
+                    "as DIR/<name>.npy (rank 0; see dump_outputs)")
     args = ap.parse_args()
     if args.workload is None:
         args.workload = "c2_dense"
@@ -519,14 +562,27 @@ def main():
                 pending.append((works, (out, full)))       # inputs and outputs stay alive until the wait
         return out
 
+    last = {}
+
+    def timed_step():                   # --dump-outputs: keep what the step returned
+        last["out"] = step()
+
     with torch.no_grad():
-        # Device-side timings first (HIP events; they also bring clocks, allocator and caches to steady state), then the
-        # contract's W untimed warm-up steps immediately followed by the K timed steps.
-        compute()
-        s_avg, s_med, s_min = kernel_time_ms(compute, max(args.steps, 5), dev)          # whole step on the device
-        k_avg, k_med, k_min = fused_kernel_time_ms(compute, max(args.steps, 5), dev)   # dominant kernel only
-        extra = {}
-        if dist_on:
+        # --full: device-side timings first (HIP events; they also bring clocks, allocator and caches to steady state).  Then the
+        # W untimed warm-up steps immediately followed by the K timed steps.
+        extra, plan, gate_info, verified, verify_info = {}, None, None, None, None
+        if args.full:
+            compute()
+            s_avg, s_med, s_min = kernel_time_ms(compute, max(args.steps, 5), dev)          # whole step on the device
+            k_avg, k_med, k_min = fused_kernel_time_ms(compute, max(args.steps, 5), dev)   # dominant kernel only
+        else:
+            # the same untimed calls as the timings above, without their events (measured: W warm-up steps alone, or W steps
+            # padded to a fixed time, time the steps ~0.6 % slower); capped at WARMUP_MAX_S, whose count every rank shares
+            t1 = time_steps(compute, 1, dist_on, dev)      # the first call also loads code objects, allocates and waits for its probes
+            for _ in range(min(2 * max(args.steps, 5), int(WARMUP_MAX_S / t1))):
+                compute()
+            torch.cuda.synchronize(dev)
+        if args.full and dist_on:
             # rank 0 alone (the others wait at the barrier): the compute-only step of THIS workload on one GPU, the figure the group's
             # compute-only value divides by
             import torch.distributed as dist
@@ -536,8 +592,10 @@ def main():
         for _ in range(max(args.warmup, 1)):
             step()
         drain()
-        wall = time_steps(step, args.steps, dist_on, dev, drain)
-        if not dist_on:
+        wall = time_steps(timed_step if args.dump_outputs else step, args.steps, dist_on, dev, drain)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(last.pop("out"), n, args.dump_outputs)
+        if args.full and not dist_on:
             f.cache_point_order = True          # a static grid queried every frame: the order is built once
             compute(); compute()
             extra["points_per_s_with_cached_point_order"] = n * args.steps / time_steps(compute, args.steps, False, dev)
@@ -549,7 +607,7 @@ def main():
                 compute(); compute()
                 extra["points_per_s_with_static_maps"] = n * args.steps / time_steps(compute, args.steps, False, dev)
                 frames[0] = keep
-        if dist_on:
+        if args.full and dist_on:
             extra["compute_only_points_per_s"] = sum(counts) * args.steps / time_steps(compute, args.steps, True, dev)
             if args.gather != "full":
                 def full():
@@ -568,20 +626,19 @@ def main():
                                                "with_dist_gather": None, "with_full_field_gather": extra["value_full_field"] / (world * single),
                                                "note": "this run's group figures / (world x rank 0's single-rank compute-only figure of the same workload)"}
 
-        verified, verify_info = None, None
-        f.record_plans = True
-        out_check = compute()                   # every rank: the c5 step holds a collective (sharded softmax)
-        plan = f.last_plan()
-        f.record_plans = False
-        gate_info = None
-        if plan and plan.get("gated_window"):         # a cloud on the gated pair of launches: which side ran?
-            g = f.last_gate()
-            if g is not None:
-                gate_info = {"tiles_that_fit_of_%d" % 128: g[0], "window_side_ran": g[1]}
-                if g[1]:
-                    plan = dict(plan, **plan["window_side"])
-        if rank == 0 and not args.no_verify:      # fp16-stored maps: the oracle runs on the WIDENED maps (the contract)
-            verified, verify_info = verify_against_oracle(f, pts, names, w, sc, out_check)
+        if args.full:
+            f.record_plans = True
+            out_check = compute()                   # every rank: the c5 step holds a collective (sharded softmax)
+            plan = f.last_plan()
+            f.record_plans = False
+            if plan and plan.get("gated_window"):         # a cloud on the gated pair of launches: which side ran?
+                g = f.last_gate()
+                if g is not None:
+                    gate_info = {"tiles_that_fit_of_%d" % 128: g[0], "window_side_ran": g[1]}
+                    if g[1]:
+                        plan = dict(plan, **plan["window_side"])
+            if rank == 0 and not args.no_verify:      # fp16-stored maps: the oracle runs on the WIDENED maps (the contract)
+                verified, verify_info = verify_against_oracle(f, pts, names, w, sc, out_check)
 
     rank_devices = [torch.cuda.get_device_name(dev)]
     if dist_on:
@@ -591,28 +648,6 @@ def main():
         rank_devices = names_all
     total_pts = sum(counts) * args.steps
     value = total_pts / wall
-    bytes_alg, per_pt = algorithmic_bytes(w, n)
-    traffic, traffic_src, valu_insts = measured_traffic(args.workload, args.points if w["step"] is not None else "grid", n)
-    traffic_in_run, traffic_note = False, None
-    under_profiler = any(k.startswith(("ROCPROF", "ROCP_", "ROCTRACER")) for k in os.environ) or "rocprof" in os.environ.get("LD_PRELOAD", "")
-    if rank == 0 and world == 1 and args.traffic != "off" and not w.get("no_maps") and not under_profiler:
-        # the timed binary, this box, this command: FETCH_SIZE / WRITE_SIZE of the fused kernel from two short profiler passes
-        argv_w = ["--workload", args.workload, "--points", args.points] + (["--tuning", str(args.tuning)] if args.tuning else []) + \
-                 (["--refresh-maps"] if args.refresh_maps else [])
-        torch.cuda.synchronize(dev)
-        got, note = traffic_in_this_run(argv_w, (plan or {}).get("kernel"))
-        if got is not None:
-            traffic, traffic_src, traffic_in_run = got, note, True
-        elif args.traffic == "measure":
-            raise SystemExit("bench.py --traffic measure: " + note)
-        else:
-            traffic_note = "not measured in this run (%s): the committed copy, if its fingerprint matches" % note
-    elif args.traffic != "off" and under_profiler:
-        traffic_note = "not measured in this run (the bench itself runs under a profiler): the committed copy, if its fingerprint matches"
-    achieved = bytes_alg / (k_avg * 1e-3) / 1e9
-    # SURVEY 8d secondary figure (reported, not graded): bytes the gather requests with zero inter-point reuse
-    sumC = w["C"] + w["NI"] + w.get("color", 0)
-    b_gather = 12 + w["V"] * (4 + 16 * sumC) + 5 + 4 * sumC
     res = {
         "metric": "fused 3D query-points/sec", "value": value, "unit": "points/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -643,41 +678,64 @@ def main():
                    "gather_keys": (list(gather_keys.get("keys", ())) if dist_on else "n/a"),
                    "gather_bytes_received_per_rank": (gather_keys.get("bytes") if dist_on else "n/a"),
                    "gather_xgmi_floor_ms": ((gather_keys.get("bytes", 0) / max(world - 1, 1)) / 153e9 * 1e3 if dist_on else "n/a")},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                     "traffic_note": traffic_note,
-                     "traffic_measured_in_run": traffic_in_run,      # True: PMC passes of this command on this box (traffic_in_this_run); False: the committed copy
-                     "kernel": (plan or {}).get("kernel", "fused_eval_kernel<0>"),
-                     "kernel_ms_avg": k_avg, "kernel_ms_median": k_med,
-                     "kernel_ms_min": k_min, "algorithmic_bytes_per_launch": bytes_alg,
-                     "algorithmic_bytes_per_point": per_pt, "kernel_points_per_s": n / (k_avg * 1e-3),
-                     "step_device_ms_avg": s_avg, "logical_gather_bytes_per_point": b_gather,
-                     "logical_gather_GBps": n * b_gather / (k_avg * 1e-3) / 1e9,
-                     "traffic_GBps": (traffic / (k_avg * 1e-3) / 1e9) if traffic else None,
-                     # second roof, for the launches that are not memory-bound (dist_only): VALU wave instructions of the committed
-                     # counter pass over this run's kernel time, against one PLAIN instruction per SIMD per 2 cycles at 2.4 GHz
-                     "valu_issue": ({"insts_per_launch": valu_insts, "insts_per_point": valu_insts / n,
-                                     "frac_of_issue_peak": valu_insts / (k_avg * 1e-3) / VALU_PEAK_INST_PER_S,
-                                     "peak_inst_per_s": VALU_PEAK_INST_PER_S, "source": traffic_src} if valu_insts else None),
-                     "note": "achieved = algorithmic bytes / kernel_ms_avg (HIP events around the "
-                     "fused kernel on its launch stream); step_device_ms_avg also covers the per-step lattice probe / Hilbert ordering kernels"},
     }
-    res.update(extra)
-    res["verified"] = verified
-    res["verify"] = verify_info
-    if plan:
-        res["config"]["point_order"] = plan["point_order"]
-        res["config"]["tile_points"] = plan["tile_points"]
-    if gate_info:
-        res["config"]["device_gate"] = gate_info
-        # (VERDICT r5 residual) the library's event pair of a gated cloud brackets the probe kernel and BOTH gated launches -- the side that
-        # lost returns at once (~5 us) -- so kernel_ms_* is slightly conservative for the side `roofline.kernel` names
-        res["roofline"]["kernel_time_spans"] = "window_gate_probe_kernel + the gated window launch + the gated cell-run launch (the losing side returns at once)"
-    if dist_on and res.get("scaling_efficiency"):
-        res["scaling_efficiency"]["with_dist_gather"] = value / (world * res["single_rank_points_per_s_same_workload"])
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        maps_cpu = {k: f.curr_obs_torch[k].float().cpu() for k in names}
-        res["cpu_baseline"] = cpu_baseline(sc, w, names, maps_cpu, pts.cpu(), args.cpu_sample, args.cpu_threads)
+    if args.full:
+        bytes_alg, per_pt = algorithmic_bytes(w, n)
+        traffic, traffic_src, valu_insts = measured_traffic(args.workload, args.points if w["step"] is not None else "grid", n)
+        traffic_in_run, traffic_note = False, None
+        under_profiler = any(k.startswith(("ROCPROF", "ROCP_", "ROCTRACER")) for k in os.environ) or "rocprof" in os.environ.get("LD_PRELOAD", "")
+        if rank == 0 and world == 1 and args.traffic != "off" and not w.get("no_maps") and not under_profiler:
+            # the timed binary, this box, this command: FETCH_SIZE / WRITE_SIZE of the fused kernel from two short profiler passes
+            argv_w = ["--workload", args.workload, "--points", args.points] + (["--tuning", str(args.tuning)] if args.tuning else []) + \
+                     (["--refresh-maps"] if args.refresh_maps else [])
+            torch.cuda.synchronize(dev)
+            got, note = traffic_in_this_run(argv_w, (plan or {}).get("kernel"))
+            if got is not None:
+                traffic, traffic_src, traffic_in_run = got, note, True
+            elif args.traffic == "measure":
+                raise SystemExit("bench.py --traffic measure: " + note)
+            else:
+                traffic_note = "not measured in this run (%s): the committed copy, if its fingerprint matches" % note
+        elif args.traffic != "off" and under_profiler:
+            traffic_note = "not measured in this run (the bench itself runs under a profiler): the committed copy, if its fingerprint matches"
+        achieved = bytes_alg / (k_avg * 1e-3) / 1e9
+        # SURVEY 8d secondary figure (reported, not graded): bytes the gather requests with zero inter-point reuse
+        sumC = w["C"] + w["NI"] + w.get("color", 0)
+        b_gather = 12 + w["V"] * (4 + 16 * sumC) + 5 + 4 * sumC
+        res["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                           "traffic_note": traffic_note,
+                           "traffic_measured_in_run": traffic_in_run,      # True: PMC passes of this command on this box (traffic_in_this_run); False: the committed copy
+                           "kernel": (plan or {}).get("kernel", "fused_eval_kernel<0>"),
+                           "kernel_ms_avg": k_avg, "kernel_ms_median": k_med,
+                           "kernel_ms_min": k_min, "algorithmic_bytes_per_launch": bytes_alg,
+                           "algorithmic_bytes_per_point": per_pt, "kernel_points_per_s": n / (k_avg * 1e-3),
+                           "step_device_ms_avg": s_avg, "logical_gather_bytes_per_point": b_gather,
+                           "logical_gather_GBps": n * b_gather / (k_avg * 1e-3) / 1e9,
+                           "traffic_GBps": (traffic / (k_avg * 1e-3) / 1e9) if traffic else None,
+                           # second roof, for the launches that are not memory-bound (dist_only): VALU wave instructions of the committed
+                           # counter pass over this run's kernel time, against one PLAIN instruction per SIMD per 2 cycles at 2.4 GHz
+                           "valu_issue": ({"insts_per_launch": valu_insts, "insts_per_point": valu_insts / n,
+                                           "frac_of_issue_peak": valu_insts / (k_avg * 1e-3) / VALU_PEAK_INST_PER_S,
+                                           "peak_inst_per_s": VALU_PEAK_INST_PER_S, "source": traffic_src} if valu_insts else None),
+                           "note": "achieved = algorithmic bytes / kernel_ms_avg (HIP events around the "
+                           "fused kernel on its launch stream); step_device_ms_avg also covers the per-step lattice probe / Hilbert ordering kernels"}
+        res.update(extra)
+        res["verified"] = verified
+        res["verify"] = verify_info
+        if plan:
+            res["config"]["point_order"] = plan["point_order"]
+            res["config"]["tile_points"] = plan["tile_points"]
+        if gate_info:
+            res["config"]["device_gate"] = gate_info
+            # (VERDICT r5 residual) the library's event pair of a gated cloud brackets the probe kernel and BOTH gated launches -- the side that
+            # lost returns at once (~5 us) -- so kernel_ms_* is slightly conservative for the side `roofline.kernel` names
+            res["roofline"]["kernel_time_spans"] = "window_gate_probe_kernel + the gated window launch + the gated cell-run launch (the losing side returns at once)"
+        if dist_on and res.get("scaling_efficiency"):
+            res["scaling_efficiency"]["with_dist_gather"] = value / (world * res["single_rank_points_per_s_same_workload"])
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            maps_cpu = {k: f.curr_obs_torch[k].float().cpu() for k in names}
+            res["cpu_baseline"] = cpu_baseline(sc, w, names, maps_cpu, pts.cpu(), args.cpu_sample, args.cpu_threads)
     if rank == 0:
         print(json.dumps(res))
     if dist_on:

@@ -96,7 +96,7 @@ def test_bench_eight_ranks_dry_run_and_rccl_device_check():
     K, world = 8192, 8
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--backend", "gloo", "--workload", "c4_patch", "--points",
-           "random", "--gather", "full", "--points-per-gpu", str(K), "--ragged", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+           "random", "--gather", "full", "--points-per-gpu", str(K), "--ragged", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -118,7 +118,7 @@ def test_bench_eight_ranks_dry_run_and_rccl_device_check():
 
 
 def test_bench_line_measures_its_traffic_in_the_run():
-    """`python bench.py` (one GPU): the JSON line of the contract with `roofline` and `cpu_baseline`, verified against the oracle, and
+    """`python bench.py --full` (one GPU): the JSON line of the contract with `roofline` and `cpu_baseline`, verified against the oracle, and
     `roofline.traffic` measured IN THE RUN -- two short rocprofv3 PMC passes of the same command on this box (FETCH_SIZE x 2 +
     WRITE_SIZE of the fused kernel).  On patch-resolution maps the traffic is close to the algorithmic bytes; `--traffic off` falls
     back to the committed copy (or null)."""
@@ -127,7 +127,7 @@ def test_bench_line_measures_its_traffic_in_the_run():
     import subprocess
     if shutil.which("rocprofv3") is None and not os.path.exists("/opt/rocm/bin/rocprofv3"):
         pytest.skip("rocprofv3 not installed")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c2_patch", "--steps", "5", "--warmup", "2", "--cpu-sample", "20000"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c2_patch", "--steps", "5", "--warmup", "2", "--full", "--cpu-sample", "20000"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -146,3 +146,31 @@ def test_bench_line_measures_its_traffic_in_the_run():
     assert r2.returncode == 0, r2.stderr[-2000:]
     line2 = json.loads([ln for ln in r2.stdout.splitlines() if ln.startswith("{")][-1])
     assert line2["roofline"]["traffic_measured_in_run"] is False
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `python bench.py` times exactly --steps steps and prints the headline only (no roofline, oracle check or CPU
+    baseline: those are --full's); --dump-outputs writes what the last timed step returned, which equals a fresh batch_eval of
+    the same workload sampled the same way."""
+    import json
+    import subprocess
+    import bench
+    K = 70000
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c2_patch", "--points-per-gpu", str(K), "--steps", "3",
+           "--warmup", "1", "--dump-outputs", str(tmp_path / "bench")]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["metric"] == "fused 3D query-points/sec" and line["unit"] == "points/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "f32" and line["steps"] == 3 and line["warmup"] == 1 and line["config"]["points_per_gpu"] == K
+    assert abs(line["value"] - K / (line["ms_per_step"] * 1e-3)) <= 1e-6 * line["value"]
+    assert not {"roofline", "cpu_baseline", "verified", "points_per_s_with_cached_point_order"} & set(line)
+    dev = torch.device("cuda:0")
+    f, pts, names, w, sc = bench.build_workload("c2_patch", dev, 0, 1)
+    with torch.no_grad():
+        ref = f.batch_eval(pts[:K].contiguous(), return_names=names)
+    shapes = bench.dump_outputs(ref, K, str(tmp_path / "direct"))
+    assert sorted(shapes) == ["dino_feats", "dist", "valid_mask"] and 0 < shapes["dist"][0] < K
+    for k in shapes:
+        got = np.load(str(tmp_path / "bench" / (k + ".npy")))
+        assert got.dtype == np.float32 and np.array_equal(got, np.load(str(tmp_path / "direct" / (k + ".npy")))), k

@@ -138,6 +138,33 @@ def test_bench_roofline_numerator_matches_survey(tmp_path):
     assert bench.measured_traffic("nope", "grid", 1, path) == (None, None, None)
 
 
+def test_bench_dump_outputs_is_a_fixed_sample_under_64_mb(tmp_path):
+    """bench.py --dump-outputs: float32 files (float64 where float32 would round, e.g. int64 indices); past the byte budget the
+    per-point outputs are cut to ONE seeded sample of rows shared by all of them, the same from call to call; small outputs stay whole."""
+    import os
+    import bench
+    n = 3000000
+    ramp = torch.arange(n, dtype=torch.float32)
+    out = {"dist": ramp, "valid_mask": torch.arange(n) % 3 == 0, "dino_feats": ramp[:, None].expand(n, 8),
+           "match": torch.arange(300, dtype=torch.int64) * 10 ** 10, "grid_shape": (1, 2, 3)}
+    shapes = bench.dump_outputs(out, n, str(tmp_path / "a"))
+    assert sorted(shapes) == ["dino_feats", "dist", "match", "valid_mask"]
+    total = sum(os.path.getsize(str(tmp_path / "a" / (k + ".npy"))) for k in shapes)
+    assert total <= 64 * 1000 * 1000
+    a = {k: np.load(str(tmp_path / "a" / (k + ".npy"))) for k in shapes}
+    assert a["dist"].dtype == np.float32 and a["valid_mask"].dtype == np.float32 and a["match"].dtype == np.float64
+    rows = a["dist"].astype(np.int64)
+    assert 0 < rows.size < n and np.all(np.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < n
+    assert np.array_equal(a["valid_mask"], (rows % 3 == 0).astype(np.float32))
+    assert np.array_equal(a["dino_feats"], np.repeat(a["dist"][:, None], 8, axis=1))
+    assert np.array_equal(a["match"], np.arange(300, dtype=np.float64) * 10 ** 10)
+    bench.dump_outputs(out, n, str(tmp_path / "b"))
+    assert all(np.array_equal(a[k], np.load(str(tmp_path / "b" / (k + ".npy")))) for k in shapes)
+    small = {"dist": ramp[:1000], "valid_mask": torch.ones(1000, dtype=torch.bool)}
+    bench.dump_outputs(small, 1000, str(tmp_path / "c"))
+    assert np.array_equal(np.load(str(tmp_path / "c" / "dist.npy")), ramp[:1000].numpy())
+
+
 def test_rigid_helpers_match_restated_pytorch3d():
     """d3fields_amd.rigid (product) vs oracle/pytorch3d_restated.py (what the reference's loop ran with) on CPU tensors:
     the exponential map and the row-vector rigid transform are plain torch ops, so they can be checked without a GPU."""
