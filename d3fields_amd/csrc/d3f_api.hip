@@ -563,13 +563,26 @@ static int backward_common(const d3f_views *views, const float *pts, int64_t n, 
     P.depth = views->depth; P.K = views->K; P.pose = views->pose; P.pts = pts;
     P.grad_dist = grad_dist; P.grad_pts = grad_pts;
     P.n = n; P.V = views->V; P.H = views->H; P.W = views->W; P.n_maps = n_maps; P.mu = mu;
+    // the forward's rule (eval_common): the words are read when depth and every map carry one; eval_dist needs none (a
+    // non-finite depth texel passes no NaN there) and decides per point on its projection alone
+    P.n_words = 0;
+    if (mode == 0 && views->depth_nonfinite) {
+        bool all = true;
+        for (int s = 0; s < n_maps; ++s) all = all && maps[s].nonfinite;
+        if (all) {
+            P.words[P.n_words++] = views->depth_nonfinite;
+            for (int s = 0; s < n_maps; ++s) P.words[P.n_words++] = maps[s].nonfinite;
+        }
+    }
+    for (int k = 0; k < P.n_words; ++k)
+        if (!aligned(P.words[k], 4)) return fail(D3F_ERR_BAD_LAYOUT, "nonfinite word %d: device pointer must be 4-byte aligned", k);
     int64_t map_bytes = 0;
     for (int s = 0; s < n_maps; ++s) {
         P.grad_fused[s] = grad_fused[s];
         rc = fill_map(maps[s], s, views->V, nullptr, nullptr, grad_fused[s], P.maps[s], map_bytes);
         if (rc != D3F_OK) return rc;
     }
-    int t = 128;                       // LDS: 44 B per (point, view)
+    int t = 128;                       // LDS: 44 B per (point, view) + 8 B per point
     while (t > 16 && (long)t * views->V * 44 > 60 * 1024) t >>= 1;
     while (t > 8 && n / t < 1024) t >>= 1;     // small batches: spread over many workgroups (latency, not throughput)
     P.tile_pts = t;

@@ -116,6 +116,9 @@ struct BackwardParams {
     int32_t n_maps;
     int32_t tile_pts;
     float mu;
+    // d3f_map_check words of depth + every map (n_words = 0: unknown, every point takes the strict form)
+    const uint32_t *words[D3F_MAX_MAPS + 1];
+    int32_t n_words;
     MapDesc maps[D3F_MAX_MAPS];                // out / inter unused
 };
 hipError_t launch_fused_backward(const BackwardParams &P, int mode, hipStream_t stream);

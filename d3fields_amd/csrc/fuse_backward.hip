@@ -14,6 +14,10 @@
 // LDS), phase B 2^k lanes per point per map computing three dot products per view
 // <g, s>, <g, ds/dix>, <g, ds/diy> with a shuffle reduction inside the lane group, phase C one
 // lane per point combining the per-view scalars.
+// Non-finite inputs: a point is STRICT when depth or a map may hold a NaN / Inf (the d3f_map_check words
+// say so, or there are none) or one of its projections is non-finite.  A strict point takes every view through phases B
+// and C, multiplied by its validity like the reference's autograd, so 0 * NaN reaches the gradient where it does there;
+// the others skip their invalid views (exact for finite operands), which is the instruction stream of finite maps.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -23,14 +27,14 @@
 namespace d3f {
 
 struct BwdRec {          // 32 B per (point, view)
-    float gx, gy, wgt, valid;
+    float gx, gy, wgt, valid;   // valid: 1, +0, or -0 for a view with |zc| < 1e-4
     float zc, u, w, dist;   // dist: UNclamped d - zc
 };
 
 // HALF: the map is stored in fp16 (8 channels per 16-B load or scalar lanes), widened to fp32 on load like the forward
 template <int VW, int U, bool HALF = false>
 __device__ __forceinline__ void backward_map(const MapDesc &m, const float *__restrict__ gout, const BackwardParams &P,
-                                             const BwdRec *rec, float *dots, int64_t tile_base, int tile_n)
+                                             const BwdRec *rec, const uint32_t *strict_s, float *dots, int64_t tile_base, int tile_n)
 {
     using VT = typename Vec<VW>::T;
     constexpr int ES = HALF ? 2 : 4;
@@ -46,9 +50,10 @@ __device__ __forceinline__ void backward_map(const MapDesc &m, const float *__re
         const int p = p0 + grp;
         const bool live = p < tile_n;
         const int64_t i = tile_base + (live ? p : 0);
+        const bool strict = live && strict_s[p] != 0u;
         for (int v = 0; v < V; ++v) {
             const BwdRec r = rec[(live ? p : 0) * V + v];
-            const bool use = live && r.valid != 0.0f;
+            const bool use = live && (r.valid != 0.0f || strict);
             float ds = 0.0f, dx = 0.0f, dy = 0.0f;
             if (use) {
                 const float ix = unnormalize(r.gx, m.fw), iy = unnormalize(r.gy, m.fh);
@@ -107,15 +112,54 @@ __device__ __forceinline__ void backward_map(const MapDesc &m, const float *__re
 
 template <int VW, bool HALF = false>
 __device__ __forceinline__ void backward_map_u(const MapDesc &m, const float *gout, const BackwardParams &P,
-                                               const BwdRec *rec, float *dots, int64_t tile_base, int tile_n)
+                                               const BwdRec *rec, const uint32_t *strict_s, float *dots, int64_t tile_base, int tile_n)
 {
     switch (m.unroll < 0 ? -m.unroll : m.unroll) {
-    case 1: backward_map<VW, 1, HALF>(m, gout, P, rec, dots, tile_base, tile_n); break;
-    case 2: backward_map<VW, 2, HALF>(m, gout, P, rec, dots, tile_base, tile_n); break;
-    case 3: backward_map<VW, 3, HALF>(m, gout, P, rec, dots, tile_base, tile_n); break;
+    case 1: backward_map<VW, 1, HALF>(m, gout, P, rec, strict_s, dots, tile_base, tile_n); break;
+    case 2: backward_map<VW, 2, HALF>(m, gout, P, rec, strict_s, dots, tile_base, tile_n); break;
+    case 3: backward_map<VW, 3, HALF>(m, gout, P, rec, strict_s, dots, tile_base, tile_n); break;
     default:
-        if (!HALF) backward_map<VW, 4, false>(m, gout, P, rec, dots, tile_base, tile_n);    // fp16 maps: <= 3 vectors
+        if (!HALF) backward_map<VW, 4, false>(m, gout, P, rec, strict_s, dots, tile_base, tile_n);    // fp16 maps: <= 3 vectors
         break;
+    }
+}
+
+// Phase C of a strict point: every view, in the form of the reference's autograd (fusion.py:305-394), so that a non-finite
+// texel of an invalid view, a NaN weight or a non-finite projection reaches the gradient as 0 * NaN does there:
+//   d fused / d s_v = valid_v * wgt_v / (cnt + 1e-6)  (wgt NaN -> NaN),  grid_sample's grid gradient sums over in-bounds
+//   corners only (none: exactly 0), clamp / weight branches pass their gradient by mask, z := 1e-3 views pass none to zc.
+template <int MODE>
+__device__ void strict_point_grad(const BackwardParams &P, const BwdRec *rec, const float *dots, const float *krt, float inv, float gd,
+                                  float mu, float Wm1, float Hm1, float &gxw, float &gyw, float &gzw)
+{
+    for (int v = 0; v < P.V; ++v) {
+        const BwdRec r = rec[v];
+        const float *o = dots + v * 3;
+        bool corner = false;                       // an in-bounds corner in a map with an upstream gradient
+        for (int s = 0; MODE == 0 && s < P.n_maps; ++s) {
+            const MapDesc &m = P.maps[s];
+            if (!P.grad_fused[s]) continue;
+            const float x0 = floorf(unnormalize(r.gx, m.fw)), y0 = floorf(unnormalize(r.gy, m.fh));
+            corner = corner || in_bounds(x0, y0, m.fw, m.fh) || in_bounds(x0 + 1.0f, y0, m.fw, m.fh) ||
+                     in_bounds(x0, y0 + 1.0f, m.fw, m.fh) || in_bounds(x0 + 1.0f, y0 + 1.0f, m.fw, m.fh);
+        }
+        const float gs = inv * r.wgt * r.valid;                       // d fused / d s_v
+        const float g_gx = corner ? gs * o[1] : 0.0f, g_gy = corner ? gs * o[2] : 0.0f;
+        const float g_wgt = inv * r.valid * o[0];
+        float g_dist = (MODE == 1 || (r.dist >= -mu && r.dist <= mu)) ? gd * inv * r.valid : 0.0f;
+        if (MODE == 0 && mu - fabsf(r.dist) <= 0.0f) {
+            const float sgn = r.dist > 0.0f ? 1.0f : (r.dist < 0.0f ? -1.0f : 0.0f);
+            g_dist += g_wgt * r.wgt * (-sgn) / mu;
+        }
+        const float g_u = g_gx * 2.0f / Wm1, g_w = g_gy * 2.0f / Hm1;
+        const float g_xc = g_u / r.zc, g_yc = g_w / r.zc;
+        const bool ok = !signbit(r.valid);                            // phase A: -0 marks a view with |zc| < 1e-4
+        float g_zc = -(g_u * r.u + g_w * r.w) / r.zc - g_dist;
+        if (!ok) g_zc = 0.0f;
+        const float *M = krt + v * 12;
+        gxw += g_xc * M[0] + g_yc * M[4] + g_zc * M[8];
+        gyw += g_xc * M[1] + g_yc * M[5] + g_zc * M[9];
+        gzw += g_xc * M[2] + g_yc * M[6] + g_zc * M[10];
     }
 }
 
@@ -129,7 +173,8 @@ __global__ __launch_bounds__(kBlock) void fused_eval_backward_kernel(const Backw
     BwdRec *rec = reinterpret_cast<BwdRec *>(smem);                          // [TP*V]
     float *dots = reinterpret_cast<float *>(rec + (size_t)TP * V);           // [TP*V*3]
     float *cnt_s = dots + (size_t)TP * V * 3;                                // [TP]
-    float *krt = cnt_s + TP;                                                 // [V*12]
+    uint32_t *strict_s = reinterpret_cast<uint32_t *>(cnt_s + TP);           // [TP]
+    float *krt = reinterpret_cast<float *>(strict_s + TP);                   // [V*12]
 
     compute_krt(P.K, P.pose, V, krt, kBlock);
     for (int t = threadIdx.x; t < TP * V * 3; t += kBlock) dots[t] = 0.0f;
@@ -139,12 +184,19 @@ __global__ __launch_bounds__(kBlock) void fused_eval_backward_kernel(const Backw
     const int tile_n = (int)min((int64_t)TP, P.n - tile_base);
     const float mu = P.mu;
     const float Wm1 = (float)(P.W - 1), Hm1 = (float)(P.H - 1);
+    bool finite_maps = MODE == 1;                  // eval_dist: a non-finite depth texel passes no NaN (its view is invalid)
+    if (MODE == 0 && P.n_words > 0) {
+        uint32_t bad = 0u;
+        for (int k = 0; k < P.n_words; ++k) bad |= __builtin_nontemporal_load(P.words[k]);
+        finite_maps = bad == 0u;
+    }
 
     // phase A: recompute the forward's per-view scalars
     for (int p = threadIdx.x; p < tile_n; p += kBlock) {
         const int64_t i = tile_base + p;
         const float px = P.pts[i * 3 + 0], py = P.pts[i * 3 + 1], pz = P.pts[i * 3 + 2];
         float cnt = 0.0f;
+        bool strict = !finite_maps;
         for (int v = 0; v < V; ++v) {
             const Proj pr = project_point(krt + v * 12, px, py, pz, Wm1, Hm1);
             const float d = nearest_depth(P.depth, v, P.H, P.W, pr.gx, pr.gy);
@@ -153,12 +205,15 @@ __global__ __launch_bounds__(kBlock) void fused_eval_backward_kernel(const Backw
             float t = mu - fabsf(dist);
             t = t > 0.0f ? 0.0f : t;
             BwdRec r;
-            r.gx = pr.gx; r.gy = pr.gy; r.wgt = expf(t / mu); r.valid = valid ? 1.0f : 0.0f;
+            // valid: 1, or 0 -- -0 where |zc| < 1e-4 (z := 1e-3 passes no gradient to zc there; compares equal to 0)
+            r.gx = pr.gx; r.gy = pr.gy; r.wgt = expf(t / mu); r.valid = valid ? 1.0f : (pr.ok ? 0.0f : -0.0f);
             r.zc = pr.zc; r.u = pr.u; r.w = pr.w; r.dist = dist;
             rec[p * V + v] = r;
             cnt = cnt + r.valid;
+            strict = strict || !(isfinite(pr.gx) && isfinite(pr.gy) && isfinite(r.wgt) && isfinite(pr.zc));
         }
         cnt_s[p] = cnt;
+        strict_s[p] = strict ? 1u : 0u;
     }
     __syncthreads();
 
@@ -167,13 +222,13 @@ __global__ __launch_bounds__(kBlock) void fused_eval_backward_kernel(const Backw
         const MapDesc &m = P.maps[s];
         const float *gout = P.grad_fused[s];
         if (gout && m.esize == 2) {
-            if (m.vw == 8) backward_map_u<8, true>(m, gout, P, rec, dots, tile_base, tile_n);
-            else backward_map_u<1, true>(m, gout, P, rec, dots, tile_base, tile_n);
+            if (m.vw == 8) backward_map_u<8, true>(m, gout, P, rec, strict_s, dots, tile_base, tile_n);
+            else backward_map_u<1, true>(m, gout, P, rec, strict_s, dots, tile_base, tile_n);
         } else if (gout) {
             switch (m.vw) {
-            case 4: backward_map_u<4>(m, gout, P, rec, dots, tile_base, tile_n); break;
-            case 2: backward_map_u<2>(m, gout, P, rec, dots, tile_base, tile_n); break;
-            default: backward_map_u<1>(m, gout, P, rec, dots, tile_base, tile_n); break;
+            case 4: backward_map_u<4>(m, gout, P, rec, strict_s, dots, tile_base, tile_n); break;
+            case 2: backward_map_u<2>(m, gout, P, rec, strict_s, dots, tile_base, tile_n); break;
+            default: backward_map_u<1>(m, gout, P, rec, strict_s, dots, tile_base, tile_n); break;
             }
         }
         __syncthreads();      // the next map may assign a point to other lanes
@@ -187,6 +242,13 @@ __global__ __launch_bounds__(kBlock) void fused_eval_backward_kernel(const Backw
         // eval: an all-invalid point has dist := 1e3 (constant); eval_dist: 0/(0+1e-6), no valid view contributes
         const float gd = (P.grad_dist && cnt != 0.0f) ? P.grad_dist[i] : 0.0f;
         float gxw = 0.0f, gyw = 0.0f, gzw = 0.0f;
+        if (strict_s[p] != 0u) {
+            strict_point_grad<MODE>(P, rec + p * V, dots + p * V * 3, krt, inv, gd, mu, Wm1, Hm1, gxw, gyw, gzw);
+            P.grad_pts[i * 3 + 0] = gxw;
+            P.grad_pts[i * 3 + 1] = gyw;
+            P.grad_pts[i * 3 + 2] = gzw;
+            continue;
+        }
         for (int v = 0; v < V; ++v) {
             const BwdRec r = rec[p * V + v];
             if (r.valid == 0.0f) continue;
@@ -220,7 +282,7 @@ hipError_t launch_fused_backward(const BackwardParams &P, int mode, hipStream_t 
 {
     if (P.n == 0) return hipSuccess;
     const int64_t ntiles = (P.n + P.tile_pts - 1) / P.tile_pts;
-    const size_t lds = (size_t)P.tile_pts * P.V * (sizeof(BwdRec) + 12) + (size_t)P.tile_pts * 4 + (size_t)P.V * 48;
+    const size_t lds = (size_t)P.tile_pts * P.V * (sizeof(BwdRec) + 12) + (size_t)P.tile_pts * 8 + (size_t)P.V * 48;
     if (mode == 0)
         hipLaunchKernelGGL(fused_eval_backward_kernel<0>, dim3((unsigned)ntiles), dim3(kBlock), lds, stream, P);
     else

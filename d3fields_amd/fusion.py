@@ -700,7 +700,7 @@ class Fusion:
                 _lib.check(lib.d3f_eval_lattice(ctypes.byref(views), _lib.ptr(pts_c), dims[0], dims[1], dims[2], maps, len(names),
                                                 self.mu, flags, _lib.ptr(dist), _lib.ptr(valid), fused,
                                                 inter if return_inter else None, stream))
-                return outputs, (pts_c, keep[0], keep[1], keep[2], used_maps)
+                return outputs, (pts_c, keep[0], keep[1], keep[2], used_maps, (views.depth_nonfinite, [maps[s].nonfinite for s in range(len(names))]))
             if self.reorder_points and names and n >= 65536:
                 map_bytes = sum(m.numel() * m.element_size() for m in used_maps)
                 small = map_bytes <= (64 << 20)
@@ -739,14 +739,17 @@ class Fusion:
             _lib.check(lib.d3f_eval(ctypes.byref(views), _lib.ptr(pts_c), n, maps, len(names), self.mu, flags,
                                     _lib.ptr(dist), _lib.ptr(valid), fused, inter if return_inter else None,
                                     _lib.ptr(ws), ws_bytes, stream))
-        return outputs, (pts_c, keep[0], keep[1], keep[2], used_maps)
+        return outputs, (pts_c, keep[0], keep[1], keep[2], used_maps, (views.depth_nonfinite, [maps[s].nonfinite for s in range(len(names))]))
 
     def _backward(self, saved, grad_dist, grad_fused):
-        """d3f_eval_backward on the tensors the forward launch read."""
-        pts_c, depth, K, pose, used_maps = saved
+        """d3f_eval_backward on the tensors the forward launch read, with the forward's finiteness words (a point takes the
+        strict form where they say non-finite, or where a tensor has none).  The words are read when the backward RUNS: a
+        ring slot is handed on only _WORD_SLOTS checks later, so a backward that follows more than that many new-tensor
+        checks after its forward may read another tensor's verdict (and miss a NaN the reference would propagate)."""
+        pts_c, depth, K, pose, used_maps, (depth_word, map_words) = saved
         dev = pts_c.device
         n, V = pts_c.shape[0], depth.shape[0]
-        views = _lib.Views(V, depth.shape[1], depth.shape[2], _lib.ptr(depth), _lib.ptr(K), _lib.ptr(pose))
+        views = _lib.Views(V, depth.shape[1], depth.shape[2], _lib.ptr(depth), _lib.ptr(K), _lib.ptr(pose), depth_word)
         grad_pts = torch.empty((n, 3), dtype=torch.float32, device=dev)
         nm = len(used_maps)
         maps = (_lib.ChannelMap * max(nm, 1))()
@@ -755,7 +758,7 @@ class Fusion:
         for s, m in enumerate(used_maps):
             maps[s] = _lib.ChannelMap(m.data_ptr(), m.shape[1], m.shape[2], m.shape[3],
                                       _lib.DTYPE_F16 if m.dtype == torch.float16 else _lib.DTYPE_F32,
-                                      m.stride(0), m.stride(1), m.stride(2))
+                                      m.stride(0), m.stride(1), m.stride(2), map_words[s])
             g = grad_fused[s]
             if g is not None:
                 g = g.to(torch.float32).contiguous()

@@ -131,6 +131,9 @@ class RigidTracker:
             self.pts = torch.empty(num_inst * n, 3, device=dev)
             self.grad_feats = torch.empty(num_inst * n, C, device=dev)
             self.grad_dist = torch.empty(num_inst * n, device=dev)
+            # d3f_map_check words of the private depth / descriptors, rewritten per frame (_check_maps): the five-launch
+            # step's backward skips invalid views where they read finite and takes the strict form where not
+            self.words = torch.zeros(2, dtype=torch.int32, device=dev)
             self.opt = None
             feats = obs["dino_feats"]
             # (the same layout conditions d3f_track_step checks: a view with odd strides or an unaligned base takes the
@@ -201,6 +204,7 @@ class RigidTracker:
             _lib.check(lib.d3f_rigid_transform(_lib.ptr(self.last), I, n, _lib.ptr(self.t_params), _lib.ptr(self.log_r),
                                                _lib.ptr(self.pts), _lib.ptr(norms), stream))
             out, saved = self.shadow._launch(self.pts, ["dino_feats"], False, "eval")
+            saved = saved[:5] + ((self.words.data_ptr(), [self.words.data_ptr() + 4]),)
             _lib.check(lib.d3f_track_loss_grad(_lib.ptr(out["dino_feats"]), _lib.ptr(self.src), _lib.ptr(out["dist"]),
                                                _lib.ptr(out["valid_mask"]), N, self.src.shape[1], DIST_W, _lib.ptr(self.grad_feats),
                                                _lib.ptr(self.grad_dist), _lib.ptr(loss), stream))
@@ -217,6 +221,28 @@ class RigidTracker:
         assert iters == 1
         return _iteration(self.shadow, self.last, self.src, self.t_params, self.log_r, self.opt)
 
+    def _check_maps(self):
+        """ONE d3f_map_check_many over the private depth and descriptors into self.words (five-launch step only; the
+        single-launch step has no strict form).  Runs on the current stream, ahead of the replay that reads the words."""
+        if not self.fused or self.single:
+            return
+        from . import _lib
+        import ctypes
+        dev = self.last.device
+        obs = self.shadow.curr_obs_torch
+        d, fm = obs["depth"], obs["dino_feats"]
+        if fm.stride(3) != 1 or d.stride(2) != 1:
+            self.words.fill_(1)                 # not a layout d3f_map_check reads: the strict form (same results)
+            return
+        descs = (_lib.ChannelMap * 2)(
+            _lib.ChannelMap(d.data_ptr(), d.shape[1], d.shape[2], 1, _lib.DTYPE_F32, d.stride(0), d.stride(1), d.stride(2)),
+            _lib.ChannelMap(fm.data_ptr(), fm.shape[1], fm.shape[2], fm.shape[3],
+                            _lib.DTYPE_F16 if fm.dtype == torch.float16 else _lib.DTYPE_F32, fm.stride(0), fm.stride(1), fm.stride(2)))
+        views = (ctypes.c_int32 * 2)(d.shape[0], fm.shape[0])
+        words = (ctypes.c_void_p * 2)(self.words.data_ptr(), self.words.data_ptr() + 4)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().d3f_map_check_many(descs, views, 2, words, 0, _lib.current_stream_handle(dev)))
+
     def run(self, fusion, src_feats, last_match_pts):
         dev = self.last.device
         with torch.no_grad():
@@ -224,6 +250,7 @@ class RigidTracker:
                 t.copy_(fusion.curr_obs_torch[k])
             self.last.copy_(last_match_pts)
             self.src.copy_(src_feats)
+        self._check_maps()
         if self.graph is None:
             self._rewind()                       # (a fallback after a failed d3f_track_run: its scratch words are stale)
             side = torch.cuda.Stream(device=dev)

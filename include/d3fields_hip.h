@@ -363,7 +363,12 @@ int d3f_fps_pixels(const int32_t *pts, int64_t n, int32_t k, int64_t init_idx, i
  * the reference's rigid_tracking (fusion.py:1643-1665).  grad_dist: [n] or NULL; grad_fused: host
  * array of n_maps device pointers ([n,C_k], entries may be NULL); grad_pts [n,3] is overwritten.
  * Differentiable paths: projection -> bilinear coordinates, exp weight, clamped distance;
- * nearest-depth lookup, validity and the view count carry no gradient (as in torch). */
+ * nearest-depth lookup, validity and the view count carry no gradient (as in torch).
+ * Non-finite inputs: like d3f_eval, the call reads views->depth_nonfinite and every maps[k].nonfinite when ALL are
+ * set; a point takes the strict form (every view, multiplied by its validity: 0 * NaN reaches grad_pts as in the
+ * reference's autograd) where those words say non-finite, where they are absent, or where its projection is non-finite.
+ * With all words zero the other points skip their invalid views (exact for finite operands).  Same signature and structs
+ * as before (the words are the ABI 4 fields d3f_eval reads). */
 int d3f_eval_backward(const d3f_views *views, const float *pts, int64_t n, const d3f_channel_map *maps,
                       int32_t n_maps, float mu, const float *grad_dist, const float *const *grad_fused,
                       float *grad_pts, void *stream);
