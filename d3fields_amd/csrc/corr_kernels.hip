@@ -209,7 +209,7 @@ __device__ __forceinline__ void pairwise_dist_body(const float *__restrict__ src
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 v[q] = (FULL || 16 * q < rows_left) ? -dv[q][w] * stat_scale : -INFINITY;
-                m = fmaxf(m, v[q]);                    // NaN rows are caught by the sum below
+                m = fmaxf(m, v[q]);                    // fmaxf skips NaN: NaN rows never win, the sum below turns NaN
             }
             m = fmaxf(m, __shfl_xor(m, 16, 64));
             m = fmaxf(m, __shfl_xor(m, 32, 64));
@@ -218,7 +218,7 @@ __device__ __forceinline__ void pairwise_dist_body(const float *__restrict__ src
 #pragma unroll
             for (int q = 3; q >= 0; --q)
                 if (FULL || 16 * q < rows_left) {
-                    sum += expf(v[q] - m);             // exp(-inf - -inf) cannot occur: a live row makes m finite or NaN
+                    sum += expf(v[q] - m);             // m == -inf (every live v is -inf or NaN): NaN, as the reference's softmax
                     if (v[q] == m) arg = ty + 16 * q;  // descending q: the smallest row index wins
                 }
             sum += __shfl_xor(sum, 16, 64);
@@ -560,11 +560,13 @@ __global__ __launch_bounds__(kBlock) void softmax_stats_kernel(const float *__re
 // 18.6 us for 1563 chunks x 300 columns; 256 lanes in this layout 16.3 us (13 rounds of four loads); 1024 lanes 4 rounds.
 
 // `in` [nchunks, cols] -> `out` [cols]; arg_offset shifts the winning row index (a rank's first global row when
-// the rows are sharded over GPUs; 0 otherwise).  nchunks == 0 writes the identity (-inf, 0, INT64_MAX).
+// the rows are sharded over GPUs; 0 otherwise).  nchunks == 0 writes the identity (-inf, 0, INT64_MAX), and so does a column
+// whose every logit is NaN (no row equals the max).  `final`: the merge that produces the best match -- there a column
+// without a winner gets row 0 (what the reference's argmax of an all-NaN column gives), never the INT64_MAX sentinel.
 constexpr int kMergeCols = 8, kMergeBlock = 1024;
 __global__ __launch_bounds__(kMergeBlock) void softmax_merge_kernel(const ColStat *__restrict__ in, int64_t nchunks,
                                                               int64_t cols, ColStat *__restrict__ out,
-                                                              int64_t *__restrict__ argmax_out, int64_t arg_offset)
+                                                              int64_t *__restrict__ argmax_out, int64_t arg_offset, bool final)
 {
     __shared__ ColStat red[kMergeBlock / 64][kMergeCols];
     constexpr int kLanes = kMergeBlock / kMergeCols;             // chunk lanes per column: 128
@@ -604,6 +606,7 @@ __global__ __launch_bounds__(kMergeBlock) void softmax_merge_kernel(const ColSta
             merge_stat(t.m, t.s, t.arg, u.m, u.s, u.arg);
         }
         if (t.arg != 0x7fffffffffffffffLL) t.arg += arg_offset;
+        else if (final) t.arg = 0;
         out[j] = t;
         if (argmax_out) argmax_out[j] = t.arg;
     }
@@ -667,10 +670,10 @@ static void apply_launch(float *x, int64_t total, int64_t cols, float scale, con
 }
 
 static void merge_launch(const ColStat *in, int64_t nchunks, int64_t cols, ColStat *out, int64_t *argmax_out,
-                         int64_t arg_offset, hipStream_t s)
+                         int64_t arg_offset, bool final, hipStream_t s)
 {
     hipLaunchKernelGGL(softmax_merge_kernel, dim3((unsigned)((cols + kMergeCols - 1) / kMergeCols)), dim3(kMergeBlock), 0, s, in,
-                       nchunks, cols, out, argmax_out, arg_offset);
+                       nchunks, cols, out, argmax_out, arg_offset, final);
 }
 
 // have_stats: ws[chunk][column] was already filled by the producer of x (pairwise_dist_kernel's epilogue)
@@ -682,7 +685,7 @@ static hipError_t softmax_impl(float *x, int64_t rows, int64_t cols, float scale
     const unsigned gx = (unsigned)((cols + kBlock - 1) / kBlock);
     if (!have_stats)
         hipLaunchKernelGGL(softmax_stats_kernel, dim3((unsigned)nchunks, gx), dim3(kBlock), 0, s, x, rows, cols, scale, ws);
-    merge_launch(ws, nchunks, cols, ws + nchunks * cols, argmax_out, 0, s);
+    merge_launch(ws, nchunks, cols, ws + nchunks * cols, argmax_out, 0, true, s);
     if (normalise) {
         apply_launch(x, rows * cols, cols, scale, ws + nchunks * cols, s);
     }
@@ -700,7 +703,7 @@ hipError_t launch_softmax_local_stats(const float *x, int64_t rows, int64_t cols
         const unsigned gx = (unsigned)((cols + kBlock - 1) / kBlock);
         hipLaunchKernelGGL(softmax_stats_kernel, dim3((unsigned)nchunks, gx), dim3(kBlock), 0, s, x, rows, cols, scale, ws);
     }
-    merge_launch(ws, nchunks, cols, stats_out, nullptr, row_offset, s);
+    merge_launch(ws, nchunks, cols, stats_out, nullptr, row_offset, false, s);
     return hipGetLastError();
 }
 
@@ -709,7 +712,7 @@ hipError_t launch_softmax_merge(const ColStat *parts, int64_t nparts, int64_t co
                                 hipStream_t s)
 {
     if (cols == 0) return hipSuccess;
-    merge_launch(parts, nparts, cols, merged, argmax_out, 0, s);
+    merge_launch(parts, nparts, cols, merged, argmax_out, 0, true, s);
     return hipGetLastError();
 }
 
@@ -736,7 +739,7 @@ hipError_t launch_argmin_dim0(const float *x, int64_t rows, int64_t cols, int64_
 // ---- k nearest descriptors per target column (k <= 8) ------------------------------------------------------------------
 // The north star names a "KNN correspondence lookup"; the reference has none: its best match is
 // compute_similarity_tensor_multi(...).argmax(0), i.e. the smallest distance of a column.  The k-NN extension keeps that
-// definition: per column of the [rows, cols] DISTANCE matrix the k smallest entries, ties -> lower row index, NaN last;
+// definition: per column of the [rows, cols] DISTANCE matrix the k smallest entries, ties -> lower row index, NaN last (after +Inf);
 // selection happens on the distances, before exp()/softmax can round neighbours into ties.
 // Two steps, both reading the matrix row-wise (lanes = consecutive columns, coalesced):
 //   topk_chunk_kernel  64 columns x 256 rows per workgroup; thread (c, r) scans rows r, r+4, ... with an 8-entry sorted
@@ -750,7 +753,13 @@ struct Cand {
     int32_t i;
 };
 
-__device__ __forceinline__ bool cand_before(float v, int32_t i, const Cand &o) { return v < o.v || (v == o.v && i < o.i); }
+// (value, row) order with NaN after +Inf: a NaN value only precedes another NaN of a higher row
+__device__ __forceinline__ bool val_before(float v, int64_t i, float ov, int64_t oi)
+{
+    if (ov != ov) return v == v || i < oi;
+    return v < ov || (v == ov && i < oi);
+}
+__device__ __forceinline__ bool cand_before(float v, int32_t i, const Cand &o) { return val_before(v, i, o.v, o.i); }
 
 __device__ __forceinline__ void cand_insert(Cand (&best)[kTopK], float v, int32_t i)
 {
@@ -774,15 +783,14 @@ __global__ __launch_bounds__(kBlock) void topk_chunk_kernel(const float *__restr
     const int64_t row0 = (int64_t)blockIdx.y * kTopkRows, row1 = min(rows, row0 + kTopkRows);
     Cand best[kTopK];
 #pragma unroll
-    for (int j = 0; j < kTopK; ++j) { best[j].v = INFINITY; best[j].i = 0x7fffffff; }
+    for (int j = 0; j < kTopK; ++j) { best[j].v = NAN; best[j].i = 0x7fffffff; }          // after every real row
     if (col < cols) {
         for (int64_t r = row0 + r_lane; r < row1; r += 4) {
             float v;
             int32_t i;
             if (dist) { v = dist[r * cols + col]; i = (int32_t)r; }
             else { const Cand cnd = cand_in[r * cols + col]; v = cnd.v; i = cnd.i; }
-            if (v != v) v = INFINITY;               // NaN sorts last (by row index among the infinities)
-            cand_insert(best, v, i);
+            cand_insert(best, v, i);                // NaN sorts last, after +Inf (by row index among the NaNs)
         }
     }
 #pragma unroll
@@ -866,12 +874,11 @@ __global__ __launch_bounds__(kBlock) void topk_merge_parts_kernel(const int64_t 
     int64_t bi[kTopK];
 #pragma unroll
     for (int j = 0; j < kTopK; ++j) { bv[j] = INFINITY; bi[j] = -1; }
-    auto before = [](float v, int64_t i, float ov, int64_t oi) { return oi < 0 || v < ov || (v == ov && i < oi); };
+    auto before = [](float v, int64_t i, float ov, int64_t oi) { return oi < 0 || val_before(v, i, ov, oi); };
     for (int64_t t = 0; t < n_parts * k; ++t) {
         const int64_t i = pidx[t * cols + col];
         if (i < 0) continue;
-        float v = pval[t * cols + col];
-        if (v != v) v = INFINITY;
+        const float v = pval[t * cols + col];
         if (!before(v, i, bv[kTopK - 1], bi[kTopK - 1])) continue;
         bv[kTopK - 1] = v; bi[kTopK - 1] = i;
 #pragma unroll

@@ -429,8 +429,14 @@ int d3f_similarity_to_target(const float *src, int64_t B, int64_t inner, int32_t
 /* compute_similarity_tensor_multi (corr_utils.py:63-106): src [B1,C], tgt [B2,C] ->
  * out [B1,B2]; the [B1,B2,C] difference tensor of the reference (and its OOM retry,
  * corr_utils.py:84-94) never exists.  `scale` is ignored by D3F_SIM_DIST.
- * argmax_out: NULL or [B2] int64, the row index of the best match of each target (largest
- * similarity == smallest distance; first wins).
+ * argmax_out: NULL or [B2] int64, the row index of the best match of each target, always in [0, B1).  In
+ *   D3F_SIM_DIST / D3F_SIM_EXP mode the smallest distance (scale unused); in D3F_SIM_SOFTMAX_DIM0 mode
+ *   the largest logit -scale*d in float32, first (lowest) row wins; a row whose logit is NaN never wins, and a column
+ *   where every logit is NaN gives row 0 (the reference's argmax of an all-NaN softmax column).  For scale > 0 that is
+ *   the smallest distance (+Inf before NaN, ties to the lower row) -- k-NN's first neighbour -- up to the rounding of
+ *   d*scale (distances whose logits round equal tie).  For scale < 0 it is the largest distance; for scale == 0 the
+ *   first row whose distance is finite.  Distances come from a guarded contraction when B1 >= 512 and C % 32 == 0
+ *   (INTEGRATION.md): within 2e-6 relative of float64, so near-equal distances may rank either way.
  * workspace: >= d3f_softmax_workspace_bytes(B1, B2) bytes when mode is D3F_SIM_SOFTMAX_DIM0 or
  * argmax_out is given; only read/written inside the call. */
 int d3f_pairwise_similarity(const float *src, const float *tgt, int64_t B1, int64_t B2, int32_t C,
@@ -441,7 +447,7 @@ int d3f_pairwise_similarity(const float *src, const float *tgt, int64_t B1, int6
 /* k-nearest-descriptor lookup (k <= 8): d3f_pairwise_similarity plus, per target column, the rows of the k SMALLEST
  * distances -- the k-NN generalisation of the reference's best match, compute_similarity_tensor_multi(...).argmax(0)
  * (the reference has no KNN of its own; this is what the north star's "KNN correspondence lookup" maps
- * to).  Neighbours are chosen on the raw distances (ties -> lower row index, NaN last), before exp / softmax can round
+ * to).  Neighbours are chosen on the raw distances (ties -> lower row index, NaN last: after +Inf, NaN rows by index), before exp / softmax can round
  * close values into ties.  topk_idx [k,B2] int64 (row j = the j-th nearest; -1 where B1 < k), topk_val [k,B2] or NULL:
  * the entries of `out` (in `mode`) at those rows.  workspace >= d3f_pairwise_topk_workspace_bytes(B1, B2), 16-B aligned. */
 int64_t d3f_pairwise_topk_workspace_bytes(int64_t B1, int64_t B2);
@@ -451,9 +457,9 @@ int d3f_pairwise_similarity_topk(const float *src, const float *tgt, int64_t B1,
 
 /* The two halves of the k-NN lookup for ROW-SHARDED sources (d3fields_amd/sharding.py: sharded_knn_descriptors):
  *   d3f_topk_smallest  per column of a [rows, cols] matrix (a rank's raw distances) the rows of the k smallest entries (ties ->
- *                      lower row, NaN last): idx_out [k,cols] int64 (-1 where rows < k), val_out [k,cols] or NULL;
+ *                      lower row, NaN last: after +Inf): idx_out [k,cols] int64 (-1 where rows < k), val_out [k,cols] or NULL;
  *                      workspace >= d3f_pairwise_topk_workspace_bytes(rows, cols), 16-byte aligned.
- *   d3f_topk_merge     n_parts such lists (indices already GLOBAL rows) -> the k best per column by (value, index);
+ *   d3f_topk_merge     n_parts such lists (indices already GLOBAL rows) -> the k best per column by (value, index), NaN after +Inf;
  *                      parts_idx / parts_val [n_parts, k, cols]; entries with index < 0 are padding. */
 int d3f_topk_smallest(const float *x, int64_t rows, int64_t cols, int32_t k, int64_t *idx_out, float *val_out,
                       void *workspace, int64_t workspace_bytes, void *stream);
@@ -465,9 +471,11 @@ int d3f_topk_merge(const int64_t *parts_idx, const float *parts_val, int64_t n_p
  * rows split over ranks each rank runs
  *   1. d3f_pairwise_softmax_local : raw distances of ITS rows into out [B1_local,B2] and, per target
  *      column, the running statistics of -d*scale over its rows -> stats [B2]
- *      (argmax = row_offset + local row of the first maximum; B1_local == 0 gives (-inf, 0, INT64_MAX));
+ *      (argmax = row_offset + local row of the first maximum; B1_local == 0, or a column whose every logit is NaN,
+ *      gives (-inf, *, INT64_MAX), which loses every merge);
  *   2. an all-gather of the 16-B records (the only exchange step; host side, RCCL);
- *   3. d3f_softmax_merge : [n_parts,B2] records in rank order -> merged [B2] (+ global argmax, first wins);
+ *   3. d3f_softmax_merge : [n_parts,B2] records in rank order -> merged [B2] (+ global argmax, first wins; a column
+ *      without a winner gets 0, as d3f_pairwise_similarity's argmax_out);
  *   4. d3f_softmax_apply : out = exp(-out*scale - max) / sum in place.
  * workspace of step 1: >= d3f_softmax_workspace_bytes(B1_local, B2). */
 typedef struct d3f_col_stat {

@@ -293,11 +293,9 @@ def test_driver_sequence_segment_select_track(dev):
 
 # ---- k nearest descriptors (the north star's "KNN correspondence lookup"; extension of argmax(0)) ---------------------
 def _knn_reference(dist, k):
-    """numpy: per column the k smallest distances, ties -> lower row, NaN last"""
-    d = np.where(np.isnan(dist), np.inf, dist)
-    rows = np.arange(d.shape[0])
-    idx = np.stack([np.lexsort((rows, d[:, c]))[:k] for c in range(d.shape[1])], axis=1)
-    return idx
+    """numpy: per column the k smallest distances, ties -> lower row, NaN last (after +Inf): the header's order"""
+    from oracle.corr_ref import rank_order
+    return rank_order(dist, k)
 
 
 @pytest.mark.parametrize("B1,B2,C,k", [(700, 37, 24, 5), (100000, 300, 384, 8), (5, 3, 16, 8), (257, 65, 8, 1), (70000, 2, 32, 3)])
@@ -320,6 +318,8 @@ def test_knn_descriptors_matches_numpy(dev, B1, B2, C, k):
     assert np.array_equal(cpu(val)[:kk], np.take_along_axis(cpu(sim), want[:kk], axis=0))
     assert np.array_equal(got[0], cpu(cu.nearest_descriptor(src.to(dev), tgt.to(dev), 1.3)[1]))   # k = 1 == the fused argmax
     assert got[0, 0] == 0 and (B1 < 2 or k < 2 or got[1, 0] == B1 // 2)
+    from oracle import corr_ref as R                           # float64: an admissible order of every column
+    R.check_ranked(got, R.pairwise(src.numpy(), tgt.numpy(), "l2"))
 
 
 def test_knn_descriptors_vs_reference_golden(dev):

@@ -192,6 +192,12 @@ def test_seeded_pairwise_against_oracle(dev, seed):
         clear = np.ones(B2, bool) if B1 == 1 else (best[1] - best[0] > 1e-4 * np.maximum(best[1], 1e-30))
         assert np.array_equal(cpu(idx)[clear], am[clear]), what
         assert idx[B2 // 2].item() == B1 // 3 or not clear[B2 // 2], what
+    # float64, per entry (oracle/corr_ref.py): every softmax entry, and the best match of every column as an admissible row
+    from oracle import corr_ref as R
+    D = R.pairwise(src.numpy(), tgt.numpy(), dist_type)
+    R.check_softmax(cpu(sim), D, scale, str(what))
+    if dist_type == "l2":
+        R.check_ranked(cpu(idx), D, scale=scale, what=str(what))
 
 
 @pytest.mark.parametrize("seed", range(10))

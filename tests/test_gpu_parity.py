@@ -561,6 +561,14 @@ def test_pairwise_guarded_contraction_near_duplicates(dev, B1, B2, C, dist_type,
     assert np.array_equal(cpu(idx)[okc][clear], am[okc][clear])
     for k in range(5):
         assert idx[k].item() == rows[k]
+    # float64, per entry (oracle/corr_ref.py): every distance, every softmax entry and the best match of every column
+    from oracle import corr_ref as R
+    D = R.pairwise(src.numpy(), tgt.numpy(), dist_type)
+    R.check_dist(dgot, D)
+    R.check_softmax(got, D, scale)
+    R.check_ranked(cpu(idx), D, scale=scale, what="best match")
+    if B2 >= 300:
+        assert idx[201].item() == 0                              # the all-NaN column: row 0, never an out-of-range sentinel
 
 
 @pytest.mark.parametrize("B1,splits", [(5000, (0, 1700, 1700, 5000)), (257, (0, 256, 257)), (1000, (0, 333, 1000))])
@@ -590,6 +598,10 @@ def test_row_sharded_softmax_steps(dev, B1, splits, dist_type):
     assert rel_err(cpu(rows), ref) <= TOL
     assert np.array_equal(cpu(am), ref_am) and am[3].item() == B1 - 1
     assert torch.allclose(rows.sum(0), torch.ones(B2, device=dev), atol=1e-5)
+    from oracle import corr_ref as R
+    D = R.pairwise(src.numpy(), tgt.numpy(), dist_type)
+    R.check_softmax(cpu(rows), D, 0.7, "sharded softmax")
+    R.check_ranked(cpu(am), D, scale=0.7, what="sharded best match")
 
 
 def test_point_order_probe_and_unordered_walk(dev):

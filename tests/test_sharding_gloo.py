@@ -112,6 +112,7 @@ class _NumpySoftmaxKernels:
         out = np.zeros(rec.shape[1], _REC)
         out["m"], out["s"] = M, (rec["s"] * w).sum(0, dtype=np.float32)
         out["a"] = np.where(rec["m"] == M, rec["a"], np.iinfo(np.int64).max).min(0)
+        out["a"][out["a"] == np.iinfo(np.int64).max] = 0                 # no winner (every logit NaN): row 0 (header)
         return torch.from_numpy(out.view(np.uint8).reshape(-1, 16).copy()), torch.from_numpy(out["a"].copy())
 
     @staticmethod
@@ -125,14 +126,12 @@ class _NumpyTopkKernels:
 
     @staticmethod
     def local_topk(dist_local, k):
+        from oracle.corr_ref import rank_order
         d = dist_local.numpy()
-        rows, cols = d.shape
-        idx = np.full((k, cols), -1, np.int64)
-        val = np.full((k, cols), np.nan, np.float32)
-        for c in range(cols):
-            order = np.lexsort((np.arange(rows), d[:, c]))[:k]            # value ascending, ties -> lower row
-            idx[:len(order), c] = order
-            val[:len(order), c] = d[order, c]
+        idx = rank_order(d, k)                                            # value ascending, +Inf before NaN, ties -> lower row
+        val = np.full(idx.shape, np.nan, np.float32)
+        if d.shape[0]:
+            val = np.where(idx >= 0, np.take_along_axis(d, np.maximum(idx, 0), 0), np.nan).astype(np.float32)
         return torch.from_numpy(idx), torch.from_numpy(val)
 
     @staticmethod
@@ -143,7 +142,8 @@ class _NumpyTopkKernels:
         val = np.full((k, cols), np.nan, np.float32)
         for c in range(cols):
             live = pi[:, c] >= 0
-            order = np.lexsort((pi[live, c], pv[live, c]))[:k]
+            v = pv[live, c]
+            order = np.lexsort((pi[live, c], np.where(np.isnan(v), 0, v), np.isnan(v)))[:k]     # NaN after +Inf
             idx[:len(order), c] = pi[live, c][order]
             val[:len(order), c] = pv[live, c][order]
         return torch.from_numpy(idx), torch.from_numpy(val)
