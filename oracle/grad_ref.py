@@ -143,6 +143,37 @@ def _field64(obs, p64, dec, H, W, mu, maps, mode, sl):
     return out, dict(M=M, z=z, uvx=uvx, uvy=uvy, weight=weight, livef=livef, count=count, empty=empty)
 
 
+def corner_terms(m, c, sl, aux, H, W, vv):
+    """The sizes a bound on one map is built from, per (view, point[, channel]) of the rows `sl` (no autograd): the float64
+    sampling position ix, iy and fractions tx, ty (clamped to [0, 1]); va, the |texels| of the four corners (0 where out
+    of bounds or non-finite); s = sum_q |w_q| |T_q|; dx, dy: bounds of d/dtx and d/dty of the bilinear value from the
+    |texels| (what its derivatives are made of), ddx, ddy: |d/dtx| and |d/dty| of the value itself; px, py:
+    the float32 rounding of the sampling position in units of eps (~ |ix| + fw)."""
+    fh, fw = int(m.shape[1]), int(m.shape[2])
+    gx = aux["uvx"] / (W - 1) * 2 - 1
+    gy = aux["uvy"] / (H - 1) * 2 - 1
+    ix, iy = ((gx + 1) / 2) * (fw - 1), ((gy + 1) / 2) * (fh - 1)
+    tx = torch.nan_to_num(ix - c["x0"][:, sl].to(F64)).clamp(0, 1)
+    ty = torch.nan_to_num(iy - c["y0"][:, sl].to(F64)).clamp(0, 1)
+    x0, y0 = c["x0"][:, sl], c["y0"][:, sl]
+    xs, ys = (x0, x0 + 1, x0, x0 + 1), (y0, y0, y0 + 1, y0 + 1)
+    va = [torch.nan_to_num(_gather(m, vv, ys[q], xs[q], c["inb"][q][:, sl]), nan=0.0, posinf=0.0, neginf=0.0).abs()
+          * c["inb"][q][:, sl][..., None] for q in range(4)]
+    wts = ((1 - tx) * (1 - ty), tx * (1 - ty), (1 - tx) * ty, tx * ty)
+    s = va[0] * wts[0][..., None] + va[1] * wts[1][..., None] + va[2] * wts[2][..., None] + va[3] * wts[3][..., None]
+    dx = (va[0] + va[1]) * (1 - ty)[..., None] + (va[2] + va[3]) * ty[..., None]
+    dy = (va[0] + va[2]) * (1 - tx)[..., None] + (va[1] + va[3]) * tx[..., None]
+    # |d/dtx|, |d/dty| of the bilinear value itself (signed corner differences; the value is linear in tx, ty in a cell)
+    t = [torch.nan_to_num(_gather(m, vv, ys[q], xs[q], c["inb"][q][:, sl]), nan=0.0, posinf=0.0, neginf=0.0)
+         * c["inb"][q][:, sl][..., None] for q in range(4)]
+    ddx = ((t[1] - t[0]) * (1 - ty)[..., None] + (t[3] - t[2]) * ty[..., None]).abs()
+    ddy = ((t[2] - t[0]) * (1 - tx)[..., None] + (t[3] - t[1]) * tx[..., None]).abs()
+    # float32 rounding of the sampling position (ix, iy: ~eps * (|ix| + fw)) moves the corner differences and weights
+    px = (torch.nan_to_num(ix).abs() + fw).clamp(max=1e6)
+    py = (torch.nan_to_num(iy).abs() + fh).clamp(max=1e6)
+    return dict(fh=fh, fw=fw, ix=ix, iy=iy, tx=tx, ty=ty, va=va, wts=wts, s=s, dx=dx, dy=dy, ddx=ddx, ddy=ddy, px=px, py=py)
+
+
 def _scale(obs, dec, H, W, mu, maps, mode, sl, gd, gks, aux):
     """Per (point, coordinate): sum over views / terms / channels of |contribution| (no autograd)."""
     with torch.no_grad():
@@ -158,25 +189,9 @@ def _scale(obs, dec, H, W, mu, maps, mode, sl, gd, gks, aux):
         for k, m in enumerate(maps):
             if m is None or gks[k] is None:
                 continue
-            c = dec["cells"][k]
-            fh, fw = int(m.shape[1]), int(m.shape[2])
-            gx = aux["uvx"] / (W - 1) * 2 - 1
-            gy = aux["uvy"] / (H - 1) * 2 - 1
-            ix, iy = ((gx + 1) / 2) * (fw - 1), ((gy + 1) / 2) * (fh - 1)
-            tx = torch.nan_to_num(ix - c["x0"][:, sl].to(F64)).clamp(0, 1)
-            ty = torch.nan_to_num(iy - c["y0"][:, sl].to(F64)).clamp(0, 1)
-            x0, y0 = c["x0"][:, sl], c["y0"][:, sl]
-            xs, ys = (x0, x0 + 1, x0, x0 + 1), (y0, y0, y0 + 1, y0 + 1)
-            va = [torch.nan_to_num(_gather(m, vv, ys[q], xs[q], c["inb"][q][:, sl]), nan=0.0, posinf=0.0, neginf=0.0).abs()
-                  * c["inb"][q][:, sl][..., None] for q in range(4)]
+            ct = corner_terms(m, dec["cells"][k], sl, aux, H, W, vv)
+            fh, fw, va, s, dx, dy, px, py = ct["fh"], ct["fw"], ct["va"], ct["s"], ct["dx"], ct["dy"], ct["px"], ct["py"]
             g = gks[k].to(F64).abs()[None]                                       # [1,n,C]
-            s = (va[0] * ((1 - tx) * (1 - ty))[..., None] + va[1] * (tx * (1 - ty))[..., None]
-                 + va[2] * ((1 - tx) * ty)[..., None] + va[3] * (tx * ty)[..., None])
-            dx = (va[0] + va[1]) * (1 - ty)[..., None] + (va[2] + va[3]) * ty[..., None]
-            dy = (va[0] + va[2]) * (1 - tx)[..., None] + (va[1] + va[3]) * tx[..., None]
-            # float32 rounding of the sampling position (ix, iy: ~eps * (|ix| + fw)) moves the corner differences and weights
-            px = (torch.nan_to_num(ix).abs() + fw).clamp(max=1e6)
-            py = (torch.nan_to_num(iy).abs() + fh).clamp(max=1e6)
             cross = (g * (va[0] + va[1] + va[2] + va[3])).sum(-1)
             sdx, sdy = (g * dx).sum(-1), (g * dy).sum(-1)
             g_wgt = g_wgt + (g * s).sum(-1) * A * livef
