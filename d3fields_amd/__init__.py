@@ -8,6 +8,8 @@ this package is the host-side mirror of the reference's Python interface.
 """
 from .fusion import Fusion, create_init_grid, fps, instance2onehot, onehot2instance  # noqa: F401
 from . import corr_utils  # noqa: F401
+from . import mesh  # noqa: F401
+from .mesh import Mesh  # noqa: F401
 from . import pcd_utils  # noqa: F401
 from . import rigid  # noqa: F401
 from . import sharding  # noqa: F401

@@ -9,7 +9,7 @@ import os
 
 from . import build as _build
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 # status codes (include/d3fields_hip.h)
 OK = 0
@@ -28,6 +28,7 @@ CHECK_WORDS_ARE_ZERO = 1
 TRACK_STALL_SENTINEL = 0x57A11ED
 MAX_VIEWS = 64
 MAX_MAPS = 8
+GAUSSIAN_MAX_RADIUS = 64
 DTYPE_F32 = 0
 DTYPE_F16 = 1
 DIST_L2, DIST_SQUARE = 0, 1
@@ -95,6 +96,11 @@ SIGNATURES = {
     "d3f_lattice_probe": (ctypes.c_int, [_vp, _i64, _vp, _vp]),
     "d3f_grid_shell_workspace_bytes": (_i64, [ctypes.POINTER(Grid)]),
     "d3f_grid_shell": (ctypes.c_int, [ctypes.POINTER(Views), ctypes.POINTER(Grid), _f32, _f32, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "d3f_mesh_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "d3f_mesh_count": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _i64, _vp]),
+    "d3f_mesh_extract": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _f32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "d3f_volume_gaussian_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "d3f_volume_gaussian": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _f32, _f32, _vp, _i64, _vp]),
     "d3f_fps_workspace_bytes": (_i64, [_i64]),
     "d3f_fps_pixels_workspace_bytes": (_i64, [_i64]),
     "d3f_farthest_point_sampling": (ctypes.c_int, [_vp, _i64, _i32, _i64, _vp, _vp, _vp, _vp]),

@@ -2,6 +2,7 @@
 // Validates arguments, picks the lane mapping of every channel map and enqueues the kernels on
 // the caller's stream.  No allocation, no synchronisation, no state besides the thread-local
 // error text.
+#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -530,6 +531,88 @@ int d3f_grid_shell(const d3f_views *views, const d3f_grid *grid, float mu, float
                                           reinterpret_cast<unsigned long long *>(count_out), workspace, static_cast<hipStream_t>(stream),
                                           tiled);
     return e == hipSuccess ? D3F_OK : hip_fail(e, "grid_shell launch");
+}
+
+// ---- iso-surface extraction and volume smoothing (mesh_kernels.hip) ----
+static int check_mesh(const char *who, const float *volume, int32_t nx, int32_t ny, int32_t nz, const int64_t *counts_out, const void *workspace,
+                      int64_t workspace_bytes)
+{
+    if (nx < 2 || ny < 2 || nz < 2) return fail(D3F_ERR_BAD_SHAPE, "%s: nx=%d ny=%d nz=%d, every extent must be >= 2", who, nx, ny, nz);
+    if ((int64_t)nx * ny * nz > 0x7fffffffLL / 3)
+        return fail(D3F_ERR_BAD_SHAPE, "%s: %lld points exceed (2^31 - 1) / 3 (32-bit vertex and triangle indices)", who, (long long)nx * ny * nz);
+    if (!volume || !counts_out) return fail(D3F_ERR_INVALID_ARG, "%s: volume / counts_out must be non-NULL", who);
+    if (!aligned(volume, 4) || !aligned(counts_out, 8)) return fail(D3F_ERR_BAD_LAYOUT, "%s: volume / counts_out must be aligned to their element size", who);
+    if (!workspace || workspace_bytes < d3f_mesh_workspace_bytes(nx, ny, nz))
+        return fail(D3F_ERR_WORKSPACE, "%s: needs %lld workspace bytes", who, (long long)d3f_mesh_workspace_bytes(nx, ny, nz));
+    if (!aligned(workspace, 4)) return fail(D3F_ERR_BAD_LAYOUT, "%s: workspace must be 4-byte aligned", who);
+    return D3F_OK;
+}
+
+int64_t d3f_mesh_workspace_bytes(int32_t nx, int32_t ny, int32_t nz)
+{
+    if (nx < 2 || ny < 2 || nz < 2) return 0;
+    return d3f::mesh_workspace_bytes((int64_t)nx * ny * nz);
+}
+
+int d3f_mesh_count(const float *volume, const uint8_t *valid, int32_t nx, int32_t ny, int32_t nz, float iso, int64_t *counts_out,
+                   void *workspace, int64_t workspace_bytes, void *stream)
+{
+    const int rc = check_mesh("mesh_count", volume, nx, ny, nz, counts_out, workspace, workspace_bytes);
+    if (rc != D3F_OK) return rc;
+    if (iso != iso) return fail(D3F_ERR_INVALID_ARG, "mesh_count: iso is NaN");
+    hipError_t e = d3f::launch_mesh(volume, valid, nx, ny, nz, iso, 0, 0, nullptr, nullptr, nullptr, counts_out, workspace, false,
+                                    static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "mesh_count launch");
+}
+
+int d3f_mesh_extract(const float *volume, const uint8_t *valid, int32_t nx, int32_t ny, int32_t nz, float iso,
+                     int64_t vertex_capacity, int64_t triangle_capacity, int64_t *keys_out, float *t_out, int32_t *triangles_out,
+                     int64_t *counts_out, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    const int rc = check_mesh("mesh_extract", volume, nx, ny, nz, counts_out, workspace, workspace_bytes);
+    if (rc != D3F_OK) return rc;
+    if (iso != iso) return fail(D3F_ERR_INVALID_ARG, "mesh_extract: iso is NaN");
+    if (vertex_capacity < 0 || triangle_capacity < 0) return fail(D3F_ERR_INVALID_ARG, "mesh_extract: negative capacity");
+    if ((vertex_capacity > 0 && (!keys_out || !t_out)) || (triangle_capacity > 0 && !triangles_out))
+        return fail(D3F_ERR_INVALID_ARG, "mesh_extract: keys_out / t_out / triangles_out must be non-NULL for a positive capacity");
+    if (!aligned(keys_out, 8) || !aligned(t_out, 4) || !aligned(triangles_out, 4))
+        return fail(D3F_ERR_BAD_LAYOUT, "mesh_extract: outputs must be aligned to their element size");
+    hipError_t e = d3f::launch_mesh(volume, valid, nx, ny, nz, iso, vertex_capacity, triangle_capacity, keys_out, t_out, triangles_out,
+                                    counts_out, workspace, true, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "mesh_extract launch");
+}
+
+int64_t d3f_volume_gaussian_workspace_bytes(int32_t nx, int32_t ny, int32_t nz)
+{
+    if (nx < 1 || ny < 1 || nz < 1) return 0;
+    return (int64_t)nx * ny * nz * 4;
+}
+
+int d3f_volume_gaussian(const float *src, float *dst, int32_t nx, int32_t ny, int32_t nz, float sigma, float truncate,
+                        void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (nx < 1 || ny < 1 || nz < 1 || (int64_t)nx * ny * nz > 0x7fffffffLL)
+        return fail(D3F_ERR_BAD_SHAPE, "volume_gaussian: nx=%d ny=%d nz=%d", nx, ny, nz);
+    if (!(sigma > 0.0f) || !(truncate > 0.0f) || sigma * truncate > 1e6f) return fail(D3F_ERR_INVALID_ARG, "volume_gaussian: sigma and truncate must be > 0 and finite");
+    // scipy: lw = int(truncate * sd + 0.5), in double on the double values of the arguments
+    const int radius = (int)((double)truncate * (double)sigma + 0.5);
+    if (radius > D3F_GAUSSIAN_MAX_RADIUS)
+        return fail(D3F_ERR_BAD_SHAPE, "volume_gaussian: radius %d exceeds D3F_GAUSSIAN_MAX_RADIUS = %d", radius, D3F_GAUSSIAN_MAX_RADIUS);
+    if (!src || !dst || src == dst) return fail(D3F_ERR_INVALID_ARG, "volume_gaussian: src / dst must be distinct non-NULL volumes");
+    if (!workspace || workspace_bytes < d3f_volume_gaussian_workspace_bytes(nx, ny, nz))
+        return fail(D3F_ERR_WORKSPACE, "volume_gaussian: needs %lld workspace bytes", (long long)d3f_volume_gaussian_workspace_bytes(nx, ny, nz));
+    if (!aligned(src, 4) || !aligned(dst, 4) || !aligned(workspace, 4)) return fail(D3F_ERR_BAD_LAYOUT, "volume_gaussian: pointers must be 4-byte aligned");
+    // scipy _gaussian_kernel1d: phi = exp(-0.5 / sigma^2 * x^2), phi / phi.sum(), float64
+    double w[D3F_GAUSSIAN_MAX_RADIUS + 1], sum = 0.0;
+    const double sd = (double)sigma;
+    for (int k = 0; k <= radius; ++k) {
+        w[k] = exp(-0.5 / (sd * sd) * (double)k * (double)k);
+        sum += k == 0 ? w[k] : 2.0 * w[k];
+    }
+    float wf[D3F_GAUSSIAN_MAX_RADIUS + 1];
+    for (int k = 0; k <= radius; ++k) wf[k] = (float)(w[k] / sum);
+    hipError_t e = d3f::launch_volume_gaussian(src, dst, nx, ny, nz, wf, radius, static_cast<float *>(workspace), static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_gaussian launch");
 }
 
 int64_t d3f_fps_workspace_bytes(int64_t n) { return n > 0 ? d3f::fps_workspace_bytes(n, 4) : 0; }

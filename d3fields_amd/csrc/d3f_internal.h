@@ -151,6 +151,15 @@ hipError_t launch_fps(const float *pts, int64_t n, int k, int64_t init_idx, int6
                       void *workspace, hipStream_t s);
 int64_t fps_workspace_bytes(int64_t n, int dist_bytes);     // n distances + two arrays of per-workgroup maxima
 
+// mesh_kernels.hip
+int64_t mesh_workspace_bytes(int64_t n);
+hipError_t launch_mesh(const float *vol, const uint8_t *valid, int nx, int ny, int nz, float iso, int64_t vertex_capacity,
+                       int64_t triangle_capacity, int64_t *keys, float *ts, int32_t *tris, int64_t *counts_out, void *workspace,
+                       bool extract, hipStream_t s);
+constexpr int kGaussMaxRadius = D3F_GAUSSIAN_MAX_RADIUS;
+hipError_t launch_volume_gaussian(const float *src, float *dst, int nx, int ny, int nz, const float *weights, int radius, float *tmp,
+                                  hipStream_t s);
+
 // pcd_kernels.hip
 hipError_t launch_backproject(const double *depth, const uint8_t *mask, int H, int W, const double *cam, const double *T,
                               const double *bounds, int64_t capacity, double *out_pts, int32_t *out_pixel, int64_t *count,

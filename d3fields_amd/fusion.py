@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import mesh as _mesh
 
 __all__ = ["Fusion", "create_init_grid", "instance2onehot", "onehot2instance", "fps", "_init_low_level_memory", "erode"]
 
@@ -867,6 +868,94 @@ class Fusion:
         ixy = idx // grid.nz
         pts = torch.stack((axes[0][ixy // grid.ny], axes[1][ixy % grid.ny], axes[2][iz]), dim=1)
         return idx, pts
+
+    # ---- the mesh of the surface (reference fusion.py:1313-1416) --------------------------------
+    def _smoothed(self, dist, shape, smooth, sigma):
+        if smooth is None:
+            return dist
+        if smooth == "gaussian":
+            return _mesh.gaussian_filter(dist, shape, sigma=sigma)
+        if callable(smooth):                     # a host function volume(numpy) -> numpy, e.g. mcubes.smooth where it is installed
+            out = np.ascontiguousarray(smooth(dist.detach().cpu().numpy().reshape(tuple(shape))), dtype=np.float32)
+            return torch.from_numpy(out).to(dist.device).view(-1)
+        raise ValueError("smooth must be None, 'gaussian' or a callable, not %r" % (smooth,))
+
+    def _extract(self, res, grid_shape, coords, smooth, sigma, use_valid_mask, snap, as_numpy, iso):
+        dev = self.device
+        dist = _as_device_tensor(res["dist"], torch.float32, dev).detach().contiguous().view(-1)
+        dist = self._smoothed(dist, grid_shape, smooth, sigma)
+        valid = _as_device_tensor(res["valid_mask"], torch.bool, dev).contiguous() if use_valid_mask else None
+        keys, t, triangles = _mesh.marching_cubes(dist, grid_shape, iso=iso, valid=valid)
+        vertices = _mesh.mesh_vertices(keys, t, grid_shape, coords, snap=snap)
+        if as_numpy:
+            return vertices.detach().cpu().numpy(), triangles.cpu().numpy()
+        return vertices.to(dev), triangles
+
+    def extract_mesh(self, pts, res, grid_shape, *, smooth=None, sigma=1.0, use_valid_mask=False, snap=True, as_numpy=True, iso=0.0):
+        """Reference Fusion.extract_mesh (fusion.py:1313-1330) with the volume, the vertices and the triangles on the device:
+        (vertices_coords [Nv, 3], triangles [M, 3] int32).  With the defaults vertex i is pts[flat(lower endpoint of its
+        edge)] (the upper endpoint where the crossing sits exactly on it), as numpy arrays, like the reference -- minus its
+        mcubes.smooth: `smooth` is None, "gaussian" (d3f_volume_gaussian with `sigma`) or a host callable
+        volume -> volume.  snap=False: the interpolated positions.  as_numpy=False: device tensors.  use_valid_mask: cells
+        with a corner outside res['valid_mask'] emit nothing (INTEGRATION.md says when that matters)."""
+        if isinstance(pts, np.ndarray):
+            pts = torch.from_numpy(pts)
+        pts = pts.detach()
+        return self._extract(res, grid_shape, lambda idx: pts[idx.to(pts.device)], smooth, sigma, use_valid_mask, snap, as_numpy, iso)
+
+    def mesh_from_grid(self, boundaries, step_size, **kw):
+        """extract_mesh(create_init_grid(boundaries, step_size)[0], batch_eval(that grid, []), shape, **kw) without ever
+        materialising the grid points: eval_grid makes the volume, vertex coordinates come from the three axis arrays."""
+        names = ("smooth", "sigma", "use_valid_mask", "snap", "as_numpy", "iso")
+        bad = [k for k in kw if k not in names]
+        if bad:
+            raise TypeError("mesh_from_grid: unexpected keyword %s" % bad)
+        res = self.eval_grid(boundaries, step_size, return_names=[])
+        nx, ny, nz = res["grid_shape"]
+        axes = [a.to(self.device) for a in _grid_axes(boundaries, step_size)]
+
+        def coords(idx):
+            ixy = idx // nz
+            return torch.stack((axes[0][ixy // ny], axes[1][ixy % ny], axes[2][idx % nz]), dim=1)
+
+        opts = dict(smooth=None, sigma=1.0, use_valid_mask=False, snap=True, as_numpy=True, iso=0.0)
+        opts.update(kw)
+        return self._extract(res, res["grid_shape"], coords, **opts)
+
+    def create_color_mesh(self, vertices, triangles, res):
+        """Reference create_color_mesh (fusion.py:1411-1416): a trimesh.Trimesh where trimesh is installed, else mesh.Mesh."""
+        return _mesh.color_mesh(vertices, triangles, res)
+
+    def create_descriptor_mesh(self, vertices, triangles, res, params, mask_out_bg):
+        """Reference create_descriptor_mesh (fusion.py:1386-1409); params['pca']: any object with mean_ and components_."""
+        return _mesh.descriptor_mesh(vertices, triangles, res, params, mask_out_bg)
+
+    def create_mask_mesh(self, vertices, triangles, res):
+        """Reference create_mask_mesh (fusion.py:1332-1345): the colours are trimesh's own 'viridis' map."""
+        try:
+            import trimesh
+        except ImportError:
+            raise NotImplementedError("create_mask_mesh maps scalars through trimesh.visual.interpolate; trimesh is not installed")
+        query_masks = res["query_masks"].detach().cpu().numpy()
+        v, tri = _mesh._host(vertices), _mesh._host(triangles)
+        return [trimesh.Trimesh(vertices=v, faces=tri[..., ::-1],
+                                vertex_colors=trimesh.visual.interpolate(query_masks[:, i], color_map="viridis"))
+                for i in range(query_masks.shape[1])]
+
+    def create_instance_mask_mesh(self, vertices, triangles, res):
+        """Reference create_instance_mask_mesh (fusion.py:1347-1373): the colours are trimesh's own 'jet' map."""
+        try:
+            import trimesh
+        except ImportError:
+            raise NotImplementedError("create_instance_mask_mesh maps scalars through trimesh.visual.interpolate; trimesh is not installed")
+        v, tri = _mesh._host(vertices), _mesh._host(triangles)
+        out = []
+        for k in res.keys():
+            if k.startswith("mask"):
+                mask = res[k].detach().cpu().numpy()
+                colors = trimesh.visual.interpolate(onehot2instance(mask) / mask.shape[1], color_map="jet")
+                out.append(trimesh.Trimesh(vertices=v, faces=tri[..., ::-1], vertex_colors=colors))
+        return out
 
     def select_features_rand(self, boundaries, N, per_instance=False, res=None, init_idx=-1):
         """Reference Fusion.select_features_rand (fusion.py:1418-1475): N farthest-point-sampled keypoints per

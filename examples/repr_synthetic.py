@@ -5,9 +5,10 @@
                                                   with dropped, split and spurious masks); the multi-view association
                                                   (align_instance_mask_v3, fusion.py:1065-1098) runs here
     batch_eval(grid, return_names=[])             the signed-distance volume of the workspace   (vis_repr.py:88-93)
-    surface points                                where the reference runs marching cubes (fusion.py:1313-1330) this takes the
-                                                  grid points of the surface shell -- meshing is out of scope
-    batch_eval(surface, ['dino_feats','mask','color_tensor'])      the reference's feature query   (vis_repr.py:97-103)
+    mesh_from_grid(box, step, use_valid_mask=True)   the surface mesh of that volume (fusion.py:1313-1330: marching cubes),
+                                                  extracted on the device; vertices and triangles stay there
+    batch_eval(vertices, ['dino_feats','mask','color_tensor'])     the reference's feature query   (vis_repr.py:97-103)
+    create_color_mesh(vertices, triangles, out)   vertex colours as the reference builds them (fusion.py:1411-1416)
 
     python examples/repr_synthetic.py [--step 0.004]
 """
@@ -64,7 +65,14 @@ def main():
         t_vol = time.perf_counter() - t0
         print("distance volume: %d x %d x %d = %d points in %.2f ms (%.2e points/s), %.1f %% valid"
               % (*shape, grid.shape[0], 1e3 * t_vol, grid.shape[0] / t_vol, 100.0 * float(vol["valid_mask"].float().mean())))
-        _, surface = f.grid_shell(box, args.step, dist_threshold=args.step)
+        f.mesh_from_grid(box, args.step, use_valid_mask=True, as_numpy=False)   # warm-up
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        surface, triangles = f.mesh_from_grid(box, args.step, use_valid_mask=True, as_numpy=False)
+        torch.cuda.synchronize()
+        t_mesh = time.perf_counter() - t0
+        print("surface mesh: %d vertices, %d triangles in %.2f ms (distance volume + extraction, on the device)"
+              % (surface.shape[0], triangles.shape[0], 1e3 * t_mesh))
         names = ["dino_feats", "mask", "color_tensor"]
         f.record_plans = True
         f.batch_eval(surface, return_names=names)
@@ -75,10 +83,12 @@ def main():
         t_q = time.perf_counter() - t0
     inst = onehot2instance(out["mask"])
     hist = torch.bincount(inst.to(torch.int64), minlength=f.get_inst_num()).tolist()
-    print("feature query: %d surface points x (%d-d features + %d-instance mask + colour) in %.2f ms (%.2e points/s)"
+    print("feature query: %d mesh vertices x (%d-d features + %d-instance mask + colour) in %.2f ms (%.2e points/s)"
           % (surface.shape[0], C, f.get_inst_num(), 1e3 * t_q, surface.shape[0] / t_q))
     print("surface points per instance:", dict(zip(["%d:%s" % (k, n) for k, n in enumerate(f.curr_obs_torch["consensus_mask_label"])], hist)))
     print("launch:", (f.last_plan() or {}).get("kernel"))
+    colour_mesh = f.create_color_mesh(surface, triangles, out)
+    print("colour mesh: %s with %d faces" % (type(colour_mesh).__name__, len(colour_mesh.faces)))
     return f, out
 
 

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define D3F_ABI_VERSION 6
+#define D3F_ABI_VERSION 7
 
 #define D3F_OK 0
 #define D3F_ERR_INVALID_ARG (-1)  /* null pointer, negative count, bad enum               */
@@ -272,6 +272,41 @@ int d3f_lattice_probe(const float *pts, int64_t n, int32_t *out_dims, void *stre
 int64_t d3f_grid_shell_workspace_bytes(const d3f_grid *grid);
 int d3f_grid_shell(const d3f_views *views, const d3f_grid *grid, float mu, float dist_thr, int64_t capacity,
                    int64_t *idx_out, int64_t *count_out, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* (ABI 7) Iso-surface extraction: what fusion.py:1313-1330 does on the host with mcubes.marching_cubes, on the device.
+ * volume: float32 [nx, ny, nz], z fastest (the `dist` of a grid query, flat index (ix*ny + iy)*nz + iz); valid: NULL, or one
+ * byte per point (the `valid_mask` of the same query).  A corner is INSIDE when value < iso.  A cell emits when all eight corners
+ * are finite and (with `valid`) valid; an edge whose endpoint is non-finite or invalid carries no vertex.
+ *   vertices   exactly one per grid edge whose endpoints straddle iso and that belongs to at least one emitting cell:
+ *              keys_out[i] = 3*flat(lower endpoint) + axis (0 x, 1 y, 2 z), t_out[i] = (iso - va) / (vb - va) in fp32 with the IEEE
+ *              division (va = the value at the lower endpoint), a finite number in [0, 1]; stored in ASCENDING key order;
+ *   triangles  int32 [M, 3] indices into the vertex array, ordered by cell (flat index of its lowest corner), inside a cell in
+ *              the order of the case table (csrc/mc_table.h, generated by scripts/gen_mc_table.py: ambiguous faces cut inside
+ *              corners off separately, so the mesh is closed wherever cells emit on both sides of a face); a triangle's normal
+ *              points to the side where value > iso.  Degenerate triangles (a value equal to iso gives t = 0 on several edges)
+ *              are emitted as the table says, NOT filtered.
+ * Two runs on the same input give byte-identical arrays (no floating-point atomics, no order that depends on the dispatcher).
+ * counts_out: TWO device int64, the true numbers of vertices and triangles -- also when they exceed the capacities: then
+ * nothing is written beyond the capacities, what was written is unspecified, and the caller re-runs with the counts.
+ * Vertex and triangle counts are 32-bit inside: nx*ny*nz <= 715827882 ((2^31 - 1) / 3 points, so neither 3 vertices per point
+ * nor 5 triangles per cell can wrap), every extent >= 2, else D3F_ERR_BAD_SHAPE.  workspace: d3f_mesh_workspace_bytes, 8 bytes
+ * per 1024 points plus the scan's scratch -- nothing per cell; 256-byte aligned like a hipMalloc'ed pointer (>= 4 needed). */
+int64_t d3f_mesh_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
+int d3f_mesh_count(const float *volume, const uint8_t *valid, int32_t nx, int32_t ny, int32_t nz, float iso, int64_t *counts_out,
+                   void *workspace, int64_t workspace_bytes, void *stream);
+int d3f_mesh_extract(const float *volume, const uint8_t *valid, int32_t nx, int32_t ny, int32_t nz, float iso,
+                     int64_t vertex_capacity, int64_t triangle_capacity, int64_t *keys_out, float *t_out, int32_t *triangles_out,
+                     int64_t *counts_out, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* (ABI 7) scipy.ndimage.gaussian_filter(src, sigma, mode='reflect', truncate=truncate) of a float32 volume [nx, ny, nz] in fp32:
+ * three axis passes (x, y, z), weights exp(-k^2 / (2 sigma^2)) normalised to sum 1 (formed in double on the host), radius
+ * int(truncate*sigma + 0.5), boundary by reflection (d c b a | a b c d | d c b a), as often as the radius needs.  src != dst;
+ * sigma > 0, truncate > 0; radius <= D3F_GAUSSIAN_MAX_RADIUS, every extent >= 1 and nx*ny*nz < 2^31, else D3F_ERR_BAD_SHAPE.
+ * workspace: one more volume (d3f_volume_gaussian_workspace_bytes = 4*nx*ny*nz), 4-byte aligned. */
+#define D3F_GAUSSIAN_MAX_RADIUS 64
+int64_t d3f_volume_gaussian_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
+int d3f_volume_gaussian(const float *src, float *dst, int32_t nx, int32_t ny, int32_t nz, float sigma, float truncate,
+                        void *workspace, int64_t workspace_bytes, void *stream);
 
 /* fps_np (utils/my_utils.py:478-497): k samples of pts[n,3] starting from init_idx, float32 Euclidean distances,
  * first maximum wins -> out_idx[k] (int64, device), out_maxdist (device float, may be NULL).  k may exceed n: like
