@@ -9,7 +9,7 @@ import os
 
 from . import build as _build
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 # status codes (include/d3fields_hip.h)
 OK = 0
@@ -28,6 +28,7 @@ CHECK_WORDS_ARE_ZERO = 1
 TRACK_STALL_SENTINEL = 0x57A11ED
 MAX_VIEWS = 64
 MAX_MAPS = 8
+KERNEL_NAME_MAX = 80
 GAUSSIAN_MAX_RADIUS = 64
 DTYPE_F32 = 0
 DTYPE_F16 = 1
@@ -66,7 +67,8 @@ class EvalPlan(ctypes.Structure):
     """struct d3f_eval_plan"""
     _fields_ = [("tile_points", _i32), ("reorder", _i32), ("lds_bytes", _i32), ("reserved", _i32), ("workgroups", _i64),
                 ("vector_floats", _i32 * MAX_MAPS), ("lanes_per_point", _i32 * MAX_MAPS),
-                ("vectors_per_lane", _i32 * MAX_MAPS), ("staged", _i32 * MAX_MAPS), ("gated_window", _i32), ("reserved2", _i32), ("family", _i32), ("reserved3", _i32)]
+                ("vectors_per_lane", _i32 * MAX_MAPS), ("staged", _i32 * MAX_MAPS), ("gated_window", _i32), ("reserved2", _i32), ("family", _i32), ("reserved3", _i32),
+                ("kernel", ctypes.c_char * KERNEL_NAME_MAX), ("window_kernel", ctypes.c_char * KERNEL_NAME_MAX)]
 
 
 # name -> (restype, argtypes); every symbol include/d3fields_hip.h declares

@@ -227,21 +227,31 @@ int eval_common(const d3f_views *views, const float *pts, int64_t n, const d3f_c
     if (ntiles > 0x7fffffffLL) return fail(D3F_ERR_BAD_SHAPE, "n=%lld needs more than 2^31 workgroups", (long long)n);
     // the window and the channel-sliced kernels keep a point's global index in 32 bits of LDS (their rows already require
     // n < 2^31; this is the guard that says so)
-    if ((pl.window || pl.rows || P.sl_slices > 0) && n > 0x7fffffffLL) return fail(D3F_ERR_BAD_SHAPE, "n=%lld: 32-bit point indices", (long long)n);
+    if ((pl.family == kFamWindow || pl.family == kFamRows || pl.family == kFamSliced) && n > 0x7fffffffLL) return fail(D3F_ERR_BAD_SHAPE, "n=%lld: 32-bit point indices", (long long)n);
+    // the distance-only pass over a big batch in caller order, with scratch: the depth maps are tiled first (a plan query: would be)
+    const bool tile_depth = n_maps == 0 && n >= d3f::kDistTiledMin && !P.order && P.walk_nx <= 0 && !P.grid_x && views->V <= 8 && tune.dist >= 0 &&
+                            !(tune.dist & 32) && (workspace || plan_only) && workspace_bytes >= d3f::depth_tiled_bytes(views->V, views->H, views->W) &&
+                            d3f::depth_tiled_bytes(views->V, views->H, views->W) < (1LL << 32);         // (32-bit pixel indices in the tiled copy)
+    // (depth_tw > 0 is what selects the TILED instances, launch_dist; P.depth_tiled itself is set below, once the copy is enqueued)
+    if (tile_depth) { P.depth_tw = (views->W + 3) / 4; P.depth_th = (views->H + 7) / 8; }
     if (plan_only) {
-        plan_out->gated_window = 0; plan_out->reserved2 = 0;
+        plan_out->gated_window = 0; plan_out->reserved2 = 0; plan_out->window_kernel[0] = 0;
         if (cloud_side == 0 && !lattice && !grid) {       // would d3f_eval's first pass take the window side?  (its plan: the lattice's)
             d3f_eval_plan side;
             if (eval_common(views, pts, n, maps, n_maps, mu, flags, out_dist, out_valid, out_fused, out_inter, workspace, workspace_bytes,
                             stream, mode, &side, grid, lattice, 1) == D3F_OK)
                 for (int s = 0; s < n_maps; ++s)
-                    if (side.staged[s] == 3 && side.reorder == 1) { plan_out->gated_window = 1; plan_out->reserved2 = side.reserved; }
+                    if (side.staged[s] == 3 && side.reorder == 1) {
+                        plan_out->gated_window = 1; plan_out->reserved2 = side.reserved;
+                        snprintf(plan_out->window_kernel, sizeof(plan_out->window_kernel), "%s", side.kernel);
+                    }
         }
         report_plan(P, pl, caller_map, n_maps, ntiles, plan_out);
+        (void)d3f::launch_fused_eval(P, pl.family, mode, d3f::Launch{ntiles, nullptr, plan_out});      // names the instance, launches nothing
         return D3F_OK;
     }
     // a cloud on the gated pair of launches: the window side (this pass) and the cell-run side (the next) read one device word
-    const bool gated_window = cloud_side == 1 && pl.window && !pl.walk && P.order != nullptr;
+    const bool gated_window = cloud_side == 1 && pl.family == kFamWindow && !pl.walk && P.order != nullptr;
     const bool gated_runs = cloud_side == 2;
     if (gated_window || gated_runs) {
         P.gate = d3f::order_gate_words(workspace, n);
@@ -258,16 +268,12 @@ int eval_common(const d3f_views *views, const float *pts, int64_t n, const d3f_c
         hipError_t ep = d3f::launch_window_gate_probe(P, d3f::order_gate_words(workspace, n), d3f::kGateSamples, hs);
         if (ep != hipSuccess) return hip_fail(ep, "window gate probe");
     }
-    // the distance-only pass over a big batch in caller order, with scratch: the depth maps are tiled first (inside the timed pair)
-    if (n_maps == 0 && n >= d3f::kDistTiledMin && !P.order && P.walk_nx <= 0 && !P.grid_x && views->V <= 8 && tune.dist >= 0 && !(tune.dist & 32) &&
-        workspace && workspace_bytes >= d3f::depth_tiled_bytes(views->V, views->H, views->W) &&
-        d3f::depth_tiled_bytes(views->V, views->H, views->W) < (1LL << 32)) {         // (32-bit pixel indices in the tiled copy)
-        P.depth_tw = (views->W + 3) / 4; P.depth_th = (views->H + 7) / 8;
+    if (tile_depth) {                                  // (inside the timed pair)
         hipError_t et = d3f::launch_depth_tiles(P, static_cast<float *>(workspace), hs);
         if (et != hipSuccess) return hip_fail(et, "depth tiling");
         P.depth_tiled = static_cast<const float *>(workspace);
     }
-    hipError_t e = d3f::launch_fused_eval(P, mode, hs);
+    hipError_t e = d3f::launch_fused_eval(P, pl.family, mode, d3f::Launch{ntiles, hs, nullptr});
     if (ev1) (void)hipEventRecord(ev1, hs);
     if (e != hipSuccess) return hip_fail(e, "fused_eval launch");
     return gated_window ? kGatedSecondPass : D3F_OK;

@@ -2,8 +2,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 
 #include "../../include/d3fields_hip.h"
+
+// the planner's kernel families (d3f_plan.h: kFamilies; the value of d3f_eval_plan.family)
+enum FamilyId { kFamDistOnly = 0, kFamWindow, kFamRuns, kFamSliced, kFamDirect, kFamRows };
 
 namespace d3f {
 
@@ -91,15 +95,47 @@ struct EvalParams {
 
 // LDS bytes in front of the stage buffers: records, cnt/flag/idx, KRt, per-view windows
 inline int fused_lds_base(int tile_pts, int V) { return ((tile_pts * V * 24 + tile_pts * 12 + V * 48 + V * 16) + 15) / 16 * 16; }
-hipError_t launch_fused_eval(const EvalParams &P, int mode, hipStream_t stream);      // fuse_launch.hip: dispatch on the plan
-hipError_t launch_direct(const EvalParams &P, int mode, hipStream_t stream);          // fuse_direct.hip
+
+// ---- which kernel instance a plan launches ----------------------------------------------------------------------------------------
+// The planner (d3f_plan.h) decides the family; inside a family ONE list next to its launcher (fuse_<family>.hip) holds the built
+// instances, one row each: D3F_VARIANT(condition on EvalParams, legacy code, instance), walked top down.  The first row whose
+// condition holds launches its instance -- or, for a plan query, only reports it: the printed name is the row's own text, so what
+// d3f_eval_plan.kernel names is what runs, and d3f_eval_plan.reserved is the row's code.
+struct Launch {
+    int64_t workgroups;        // plan_workgroups (d3f_plan.h)
+    hipStream_t stream;
+    d3f_eval_plan *describe;   // a plan query: the row fills kernel / reserved here and nothing is launched; nullptr: launch
+};
+template <typename K>
+inline hipError_t take_variant(const Launch &L, K kernel, const char *name, int code, size_t lds, const EvalParams &P, bool opt_in_lds)
+{
+    if (L.describe) {
+        snprintf(L.describe->kernel, sizeof(L.describe->kernel), "%s", name);
+        L.describe->reserved = code;
+        return hipSuccess;
+    }
+    if (opt_in_lds && lds > 64 * 1024) {
+        hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (ea != hipSuccess) return ea;
+    }
+    hipLaunchKernelGGL(kernel, dim3((unsigned)L.workgroups), dim3(kBlock), lds, L.stream, P);
+    return hipGetLastError();
+}
+// (expects `L`, `lds` and `P` in scope; returns from the launcher when the row is taken.  A row is a bare `if`, and the families'
+//  own row macros expand to several: statement position only, never under an unbraced if / else)
+#define D3F_VARIANT_LDS(OPT_IN, COND, CODE, ...) if (COND) return take_variant(L, __VA_ARGS__, #__VA_ARGS__, CODE, lds, P, OPT_IN)
+#define D3F_VARIANT(COND, CODE, ...) D3F_VARIANT_LDS(false, COND, CODE, __VA_ARGS__)
+
+hipError_t launch_fused_eval(const EvalParams &P, FamilyId family, int mode, const Launch &L);      // fuse_launch.hip: the family's launcher
+hipError_t launch_direct(const EvalParams &P, const Launch &L);                       // fuse_direct.hip
+hipError_t launch_dist(const EvalParams &P, int mode, const Launch &L);               // fuse_direct.hip: the distance-only pass
 hipError_t launch_depth_tiles(const EvalParams &P, float *tiled, hipStream_t stream);  // fuse_direct.hip: fills EvalParams::depth_tiled's buffer
 inline int64_t depth_tiled_bytes(int V, int H, int W) { return (int64_t)V * ((H + 7) / 8) * ((W + 3) / 4) * 128; }
 constexpr int64_t kDistTiledMin = 1LL << 22;      // the distance-only pass tiles the depth maps first from this many points on
-hipError_t launch_runs(const EvalParams &P, hipStream_t stream);                      // fuse_runs.hip
-hipError_t launch_sliced(const EvalParams &P, hipStream_t stream);                    // fuse_sliced.hip
-hipError_t launch_window(const EvalParams &P, hipStream_t stream);                    // fuse_window.hip
-hipError_t launch_rows(const EvalParams &P, hipStream_t stream);                      // fuse_rows.hip
+hipError_t launch_runs(const EvalParams &P, const Launch &L);                         // fuse_runs.hip
+hipError_t launch_sliced(const EvalParams &P, const Launch &L);                       // fuse_sliced.hip
+hipError_t launch_window(const EvalParams &P, const Launch &L);                       // fuse_window.hip
+hipError_t launch_rows(const EvalParams &P, const Launch &L);                         // fuse_rows.hip
 constexpr int kGateSamples = D3F_GATE_SAMPLES;            // tiles the probe looks at (evenly spaced over the order)
 hipError_t launch_window_gate_probe(const EvalParams &P, uint32_t *gate, int nsamples, hipStream_t stream);
 int64_t order_gate_offset(int64_t n);

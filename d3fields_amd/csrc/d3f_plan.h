@@ -1,7 +1,9 @@
 // d3f_plan.h -- the launch planner of the field query (host logic only; included by d3f_api.hip).
 //
 // Which kernel family gathers a query, in which point order, with which geometry.  d3f_eval_plan_query reports exactly what
-// this file decides (no device work happens here), and tests/test_abi.py holds one assertion per row and threshold.
+// this file decides (no device work happens here), and tests/test_abi.py holds one assertion per row and threshold.  The launch
+// dispatches on Plan::family (fuse_launch.hip); which INSTANCE of the family runs, and its name in d3f_eval_plan.kernel, is the
+// business of the variant list next to the family's launcher (fuse_<family>.hip, D3F_VARIANT in d3f_internal.h).
 //
 //   THE FAMILY TABLE (kFamilies below; walked top down, the first row whose predicate holds takes the query)
 //   family           kernel (fuse_<family>.hip)        takes the query when                                                  point order
@@ -166,14 +168,12 @@ struct Query {
     }
 };
 
-// What the planner decided besides the fields of EvalParams.
-enum FamilyId { kFamDistOnly = 0, kFamWindow, kFamRuns, kFamSliced, kFamDirect, kFamRows };
+// What the planner decided besides the fields of EvalParams (FamilyId: d3f_internal.h; the launch dispatches on `family`).
 struct Plan {
     FamilyId family = kFamDirect;
     bool walk = false;              // closed-form brick walk of a lattice
     bool reorder = false;           // walk, or the Hilbert order of a cloud
     bool xcd_remap = false;         // XCD k takes the k-th contiguous eighth of the tiles
-    bool window = false, runs = false, sliced = false, rows = false;
 };
 
 // ---- predicates on one map -----------------------------------------------------------------------------------------------------------
@@ -432,7 +432,7 @@ inline void direct_geometry(const Query &q, d3f::EvalParams &P, Plan &pl)
             const bool forced = (q.flags & ((1u << 26) | (1u << 27))) != 0;
             if (!forced && m.unroll < 0 && (m.C / m.vw) <= 3 * 64) {
                 const bool a16 = m.vw == 4, a8 = m.vw >= 2;
-                pick_mapping(m, a16, a8, true, pl.runs ? 1 : 4);
+                pick_mapping(m, a16, a8, true, pl.family == kFamRuns ? 1 : 4);
             }
         }
         // one point per lane group: 8 points when every map takes 32 lanes per point, else 16
@@ -450,7 +450,7 @@ inline void direct_geometry(const Query &q, d3f::EvalParams &P, Plan &pl)
         // to give a random cloud L1 locality and the big tiles of the caller-order path stay best
         // (C2 patch, random cloud: caller order 1.93 ms, walk with 8-point tiles 1.07, with 128-point tiles 0.76)
         if (q.map_bytes <= kCacheResidentBytes && !pl.walk) P.tile_pts = tile_points_for(views->V);
-    } else if (q.map_bytes > kBeyondLlcBytes && P.tile_pts > 64 && q.n >= kSmallBatch && !pl.runs) {
+    } else if (q.map_bytes > kBeyondLlcBytes && P.tile_pts > 64 && q.n >= kSmallBatch && pl.family != kFamRuns) {
         P.tile_pts = 64; P.lds_pad = 64 * 1024;
     }
     // small batches (keypoints, tracking): a 128-point tile is 16-32 serial rounds per lane group, so a few hundred
@@ -485,8 +485,8 @@ inline bool sliced_row(const Query &q, d3f::EvalParams &P, const Plan &pl)
     if (automatic) sl = half_sl ? 2 : 3;
     if (half_sl && sl != 2) sl = 0;
     // ... or the Hilbert order of a cloud on maps beyond the caches (tiles of 16 / 32 consecutive points of the order)
-    const bool cloud = pl.reorder && !pl.walk && !pl.runs && q.map_bytes > kCacheResidentBytes && q.tune.sliced_cloud >= 0;
-    bool ok = (pl.walk || cloud) && !pl.window && !q.direct && (sl >= 1 && sl <= 3) && q.mode == 0 && q.n_maps >= 1 &&
+    const bool cloud = pl.reorder && !pl.walk && pl.family != kFamRuns && q.map_bytes > kCacheResidentBytes && q.tune.sliced_cloud >= 0;
+    bool ok = (pl.walk || cloud) && pl.family != kFamWindow && !q.direct && (sl >= 1 && sl <= 3) && q.mode == 0 && q.n_maps >= 1 &&
               ((P.maps[0].esize == 4 && P.maps[0].vw == 4) || (half_sl && P.maps[0].vw == 8 && P.maps[0].fold)) && !q.want_inter[0] && q.tl == 0;
     const int lg = sl + 2, lanes = 1 << lg;      // 1: 8 lanes (128-byte slices), 2: 16 lanes, 3: 32 lanes (512 bytes)
     P.sl_vc = q.tune.sliced_vc > 0 ? q.tune.sliced_vc : (automatic ? 2 : 4);
@@ -549,23 +549,18 @@ inline const FamilyRow &family_row(FamilyId id) { return kFamilies[(int)id]; }
 // the geometry of the order first and is decided in part 2, with `direct` as what is left.
 inline void plan_family_and_order(const Query &q, d3f::EvalParams &P, Plan &pl)
 {
-    if (q.n_maps == 0) {
-        pl.family = kFamDistOnly;
-    } else if (rows_row(q, P) && (q.views->V > 4 || !(pl.window = window_row(q, P)))) {
-        // 1024-channel patch maps: the register rows with more than four views (config 4: 1.47 vs 1.68 ms on the lattice, 2.18 vs
-        // 2.66 on the cloud) and wherever the windows do not apply (small clouds: the 71 k surface points 0.125 vs 0.137 ms); four
-        // views on a lattice or a big cloud keep the windows (the reference's shape: 2.07 vs 2.37 ms)
-        pl.rows = true; pl.window = false; P.win_slices = 0;
-        pl.family = kFamRows;
-    } else if (pl.window || (pl.window = window_row(q, P))) {
-        pl.family = kFamWindow;
-    } else if ((pl.runs = runs_row(q, P, false))) {
-        pl.family = kFamRuns;
-    }
+    // 1024-channel patch maps: the register rows with more than four views (config 4: 1.47 vs 1.68 ms on the lattice, 2.18 vs
+    // 2.66 on the cloud) and wherever the windows do not apply (small clouds: the 71 k surface points 0.125 vs 0.137 ms); four
+    // views on a lattice or a big cloud keep the windows (the reference's shape: 2.07 vs 2.37 ms)
+    const bool rows = rows_row(q, P);
+    if (q.n_maps == 0) pl.family = kFamDistOnly;
+    else if (!(rows && q.views->V > 4) && window_row(q, P)) pl.family = kFamWindow;
+    else if (rows) { pl.family = kFamRows; P.win_slices = 0; }
+    else if (runs_row(q, P, false)) pl.family = kFamRuns;
     // Points on a regular lattice (a d3f_grid, or d3f_eval_lattice's dims): the brick walk is closed form -- no keys, no
     // sort, no index array, no scratch -- and replaces the Hilbert sort wherever that would be used.  (With the cell-run
     // gather the caller's z-fastest order is the one wanted: a grid column is one long run.)
-    pl.walk = q.walk_possible() && !pl.runs && ((q.flags & D3F_TUNE_FORCE_REORDER) || q.map_bytes > kCacheResidentBytes || pl.window || pl.rows);
+    pl.walk = q.walk_possible() && pl.family != kFamRuns && ((q.flags & D3F_TUNE_FORCE_REORDER) || q.map_bytes > kCacheResidentBytes || pl.family == kFamWindow || pl.family == kFamRows);
     pl.reorder = pl.walk || q.reorder_cloud();
     if (pl.walk) { P.walk_nx = q.lattice[0]; P.walk_ny = q.lattice[1]; P.walk_nz = q.lattice[2]; }
 }
@@ -574,10 +569,10 @@ inline void plan_family_and_order(const Query &q, d3f::EvalParams &P, Plan &pl)
 inline void plan_geometry(const Query &q, d3f::EvalParams &P, Plan &pl)
 {
     direct_geometry(q, P, pl);
-    if (pl.runs) runs_geometry(q, P);
-    if (pl.family == kFamDirect && !pl.rows && (pl.sliced = sliced_row(q, P, pl))) pl.family = kFamSliced;
-    if (pl.window) window_geometry(q, P, pl);
-    if (pl.rows) rows_geometry(q, P, pl);
+    if (pl.family == kFamRuns) runs_geometry(q, P);
+    if (pl.family == kFamDirect && sliced_row(q, P, pl)) pl.family = kFamSliced;
+    if (pl.family == kFamWindow) window_geometry(q, P, pl);
+    if (pl.family == kFamRows) rows_geometry(q, P, pl);
     // walks: all eight XCDs stay inside one macro-brick of ~32 k points at a time (its texel footprint stays in
     // the 256 MiB Infinity Cache), each taking a contiguous eighth of it (C2 dense 1.97 -> 1.74 ms, C4 patch 4.75 -> 4.17)
     P.xcd_chunk = (pl.reorder && pl.xcd_remap) ? (int)((32768 / P.tile_pts + 7) / 8 * 8) : 0;
@@ -607,37 +602,27 @@ inline void plan_geometry(const Query &q, d3f::EvalParams &P, Plan &pl)
         }
 }
 
+// workgroups of the launch (the launchers take this number; d3f_eval_plan.workgroups reports it)
 inline int64_t plan_workgroups(const d3f::EvalParams &P, const Plan &pl, int64_t n)
 {
+    if (pl.family == kFamSliced) return (((P.sl_chunks * P.sl_slices + 7) / 8 + P.sl_ilv - 1) / P.sl_ilv * P.sl_ilv) * 8 * P.sl_unit;
     if (pl.walk)
         return (int64_t)((P.walk_nx + P.walk_tx - 1) / P.walk_tx) * ((P.walk_ny + P.walk_ty - 1) / P.walk_ty) * ((P.walk_nz + P.walk_tz - 1) / P.walk_tz);
     return (n + P.tile_pts - 1) / P.tile_pts;
 }
 
-// what d3f_eval_plan_query reports (the maps in the caller's order)
-inline void report_plan(const d3f::EvalParams &P, const Plan &pl, const int *caller_map, int n_maps, int64_t ntiles, d3f_eval_plan *out)
+// what d3f_eval_plan_query reports besides the kernel instance (the maps in the caller's order); `kernel` and the legacy code in
+// `reserved` are filled by the row of the family's variant list that takes the launch (eval_common: launch_fused_eval, describing)
+inline void report_plan(const d3f::EvalParams &P, const Plan &pl, const int *caller_map, int n_maps, int64_t workgroups, d3f_eval_plan *out)
 {
     out->family = (int32_t)pl.family; out->reserved3 = 0;
     out->tile_points = P.tile_pts;
     out->reorder = pl.walk ? 2 : (pl.reorder ? 1 : 0);
+    out->workgroups = workgroups;
     out->lds_bytes = P.crec_offset + P.n_pre * P.tile_pts * P.V * 32 + P.lds_pad;
-    out->workgroups = P.sl_slices > 0 ? (((P.sl_chunks * P.sl_slices + 7) / 8 + P.sl_ilv - 1) / P.sl_ilv * P.sl_ilv) * 8 * P.sl_unit : ntiles;
-    if (P.win_slices > 0) {
-        out->lds_bytes = P.win_pool_offset + (2 + P.win_pool_texels) * (P.maps[0].esize == 2 ? 256 : 512) * P.win_u;
-        out->workgroups = ntiles;
-    }
+    if (P.win_slices > 0) out->lds_bytes = P.win_pool_offset + (2 + P.win_pool_texels) * (P.maps[0].esize == 2 ? 256 : 512) * P.win_u;
     if (P.rows > 0) out->lds_bytes = 24 * 1024;          // static: ops, cells, view records, keys (fuse_rows.hip)
-    // 2UVW: the window kernel's template arguments (W: workgroups per CU the pool is sized for); 1LV: sliced launch, L = log2(lanes
-    // per point), V = views in flight; cell runs: waves per SIMD the chosen variant is built for
-    out->reserved = P.sl_slices > 0 ? 100 + P.sl_lg * 10 + P.sl_vc
-                                    : (P.win_slices > 0 ? 2000 + 100 * P.win_u + 10 * (P.win_u == 1 ? (P.win_lpp == 16 ? P.win_vc : 4) : (P.win_u == 4 ? 1 : P.win_vc)) +
-                                                              (P.win_u == 1 ? (P.win_occ >= 4 ? 4 : (P.win_lpp == 16 ? 3 : P.win_occ)) : 2)
-                                                        : 0);
-    for (int s = 0; s < n_maps; ++s)
-        if (P.maps[s].runs > 0) {
-            const int ru = P.maps[s].unroll, rk = P.maps[s].runs;
-            out->reserved = (ru == 1 && rk == 4) ? (P.runs_occ == 6 ? 6 : 7) : (ru == 1 ? ((P.runs_occ == 4 || P.runs_occ == 6) ? P.runs_occ : 5) : ((ru == 2 && rk == 8 && P.runs_occ != 4) ? 3 : 4));
-        }
+    out->reserved = 0; out->kernel[0] = 0;
     for (int s = 0; s < D3F_MAX_MAPS; ++s) {
         const bool on = s < n_maps;
         const int c = on ? caller_map[s] : s;

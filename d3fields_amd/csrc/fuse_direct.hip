@@ -141,45 +141,43 @@ __global__ __launch_bounds__(kBlock, OCC) void fused_eval_dist_kernel(const Eval
     }
 }
 
-// Waves per SIMD the entry point is held to: KRt's 48 SGPRs (three or four views) do not fit beside the rest at eight waves (~80
-// SGPRs: 32-47 spilled to VGPR lanes and read back per point); held to six the allocator has 102 and the kernel still runs seven
-// waves (1.185 vs 1.235 ms on the 123 M-point grid, session 47).  One or two views fit at eight.  occ8: experiments (D3F_EXP_DIST=8).
-template <int MODE, bool TILED, bool GRID>
-static void launch_dist_v(const EvalParams &P, dim3 grid, dim3 block, hipStream_t stream, bool occ8)
+// The built instances of the distance-only pass and when each is taken.  Waves per SIMD the entry point is held to: KRt's 48 SGPRs
+// (three or four views) do not fit beside the rest at eight waves (~80 SGPRs: 32-47 spilled to VGPR lanes and read back per
+// point); held to six the allocator has 102 and the kernel still runs seven waves (1.185 vs 1.235 ms on the 123 M-point grid,
+// session 47).  One or two views fit at eight.  Eight with more views too: experiments (D3F_EXP_DIST=8).
+#ifdef D3F_EXPERIMENTS
+#define D3F_DIST_OCC8(COND, MODE, TILED, GRID)                                                                                     \
+    D3F_VARIANT((COND) && (P.dist_variant & 15) == 8 && nv == 3, 0, fused_eval_dist_kernel<MODE, 3, 8, TILED, GRID>);                                    \
+    D3F_VARIANT((COND) && (P.dist_variant & 15) == 8 && nv == 4, 0, fused_eval_dist_kernel<MODE, 4, 8, TILED, GRID>);                                    \
+    D3F_VARIANT((COND) && (P.dist_variant & 15) == 8 && nv == 0, 0, fused_eval_dist_kernel<MODE, 0, 8, TILED, GRID>);
+#else
+#define D3F_DIST_OCC8(COND, MODE, TILED, GRID)
+#endif
+#define D3F_DIST_VARIANTS(COND, MODE, TILED, GRID)                                                                                 \
+    D3F_VARIANT((COND) && nv == 1, 0, fused_eval_dist_kernel<MODE, 1, 8, TILED, GRID>);                                            \
+    D3F_VARIANT((COND) && nv == 2, 0, fused_eval_dist_kernel<MODE, 2, 8, TILED, GRID>);                                            \
+    D3F_DIST_OCC8(COND, MODE, TILED, GRID)                                                                                         \
+    D3F_VARIANT((COND) && nv == 3, 0, fused_eval_dist_kernel<MODE, 3, 6, TILED, GRID>);                                            \
+    D3F_VARIANT((COND) && nv == 4, 0, fused_eval_dist_kernel<MODE, 4, 6, TILED, GRID>);                                            \
+    D3F_VARIANT(COND, 0, fused_eval_dist_kernel<MODE, 0, 6, TILED, GRID>)
+hipError_t launch_dist(const EvalParams &P, int mode, const Launch &L)
 {
-    switch (P.V <= 4 ? P.V : 0) {
-    case 1: hipLaunchKernelGGL((fused_eval_dist_kernel<MODE, 1, 8, TILED, GRID>), grid, block, 0, stream, P); break;
-    case 2: hipLaunchKernelGGL((fused_eval_dist_kernel<MODE, 2, 8, TILED, GRID>), grid, block, 0, stream, P); break;
-    case 3:
-#ifdef D3F_EXPERIMENTS
-        if (occ8) { hipLaunchKernelGGL((fused_eval_dist_kernel<MODE, 3, 8, TILED, GRID>), grid, block, 0, stream, P); break; }
-#endif
-        hipLaunchKernelGGL((fused_eval_dist_kernel<MODE, 3, 6, TILED, GRID>), grid, block, 0, stream, P);
-        break;
-    case 4:
-#ifdef D3F_EXPERIMENTS
-        if (occ8) { hipLaunchKernelGGL((fused_eval_dist_kernel<MODE, 4, 8, TILED, GRID>), grid, block, 0, stream, P); break; }
-#endif
-        hipLaunchKernelGGL((fused_eval_dist_kernel<MODE, 4, 6, TILED, GRID>), grid, block, 0, stream, P);
-        break;
-    default:
-#ifdef D3F_EXPERIMENTS
-        if (occ8) { hipLaunchKernelGGL((fused_eval_dist_kernel<MODE, 0, 8, TILED, GRID>), grid, block, 0, stream, P); break; }
-#endif
-        hipLaunchKernelGGL((fused_eval_dist_kernel<MODE, 0, 6, TILED, GRID>), grid, block, 0, stream, P);
-        break;
+    if (P.V > 8 || P.dist_variant < 0) {        // more than eight views, or D3F_EXP_DIST=-1: the branch of fused_eval_kernel (rounds 1-5)
+        const size_t lds = (size_t)P.crec_offset + (size_t)P.n_pre * P.tile_pts * P.V * 32 + (size_t)P.lds_pad;
+        D3F_VARIANT(mode == 0, 0, fused_eval_kernel<0>);
+        D3F_VARIANT(true, 0, fused_eval_kernel<1>);
     }
+    // its own entry point (KRt in SGPRs, the views of a point in flight together), in caller order; no dynamic LDS
+    const size_t lds = 0;
+    const int nv = P.V <= 4 ? P.V : 0;          // the view count as a template argument, 0 = five to eight
+    D3F_DIST_VARIANTS(mode == 0 && P.depth_tw > 0, 0, true, false);         // the depth maps tiled first (eval_common sets depth_tw and, before the launch, depth_tiled)
+    D3F_DIST_VARIANTS(mode == 0 && P.grid_x, 0, false, true);               // (d3f_eval_grid has no scratch parameter)
+    D3F_DIST_VARIANTS(mode == 0, 0, false, false);
+    D3F_DIST_VARIANTS(true, 1, false, false);   // (eval_dist, MODE 1, has no scratch or grid parameter: keypoint batches)
+    return hipErrorInvalidValue;
 }
-template <int MODE>
-static void launch_dist(const EvalParams &P, dim3 grid, dim3 block, hipStream_t stream)
-{
-    const bool occ8 = (P.dist_variant & 15) == 8;
-    if constexpr (MODE == 0) {          // (eval_dist, MODE 1, has no scratch or grid parameter: keypoint batches)
-        if (P.depth_tiled) { launch_dist_v<MODE, true, false>(P, grid, block, stream, occ8); return; }      // (d3f_eval_grid has no scratch parameter either)
-        if (P.grid_x) { launch_dist_v<MODE, false, true>(P, grid, block, stream, occ8); return; }
-    }
-    launch_dist_v<MODE, false, false>(P, grid, block, stream, occ8);
-}
+#undef D3F_DIST_VARIANTS
+#undef D3F_DIST_OCC8
 
 // The depth maps in tiles of 4 x 8 pixels -- one 128-byte line each -- for the distance-only pass over a big batch.  Its lookups are
 // nearest-pixel gathers whose four lanes of a quad are four consecutive points of the caller's order: a lattice's z column, i.e.
@@ -211,34 +209,19 @@ hipError_t launch_depth_tiles(const EvalParams &P, float *tiled, hipStream_t str
     return hipGetLastError();
 }
 
-hipError_t launch_direct(const EvalParams &P, int mode, hipStream_t stream)
+// The direct entry points and when each is taken.
+hipError_t launch_direct(const EvalParams &P, const Launch &L)
 {
-    int64_t ntiles = (P.n + P.tile_pts - 1) / P.tile_pts;
-    if (P.walk_nx > 0)
-        ntiles = (int64_t)((P.walk_nx + P.walk_tx - 1) / P.walk_tx) * ((P.walk_ny + P.walk_ty - 1) / P.walk_ty) *
-                 ((P.walk_nz + P.walk_tz - 1) / P.walk_tz);
     const size_t lds = (size_t)P.crec_offset + (size_t)P.n_pre * P.tile_pts * P.V * 32 + (size_t)P.lds_pad;
-    dim3 grid((unsigned)ntiles), block(kBlock);
-    if (P.n_maps == 0 && P.walk_nx <= 0 && P.order == nullptr && P.V <= 8 && P.dist_variant >= 0) {
-        // the distance-only pass in caller order: its own entry point (KRt in SGPRs, the views of a point in flight together)
-        if (mode == 0) launch_dist<0>(P, grid, block, stream);
-        else launch_dist<1>(P, grid, block, stream);
-        return hipGetLastError();
-    }
     bool wide = false, f16 = false;
     for (int s = 0; s < P.n_maps; ++s) {
         wide |= (P.maps[s].unroll == -4);
         f16 |= (P.maps[s].esize == 2);
     }
-    if (mode == 0 && f16)
-        hipLaunchKernelGGL((fused_eval_f16_kernel<0>), grid, block, lds, stream, P);
-    else if (mode == 0 && wide)
-        hipLaunchKernelGGL((fused_eval_wide_kernel<0>), grid, block, lds, stream, P);
-    else if (mode == 0)
-        hipLaunchKernelGGL((fused_eval_kernel<0>), grid, block, lds, stream, P);
-    else
-        hipLaunchKernelGGL((fused_eval_kernel<1>), grid, block, lds, stream, P);
-    return hipGetLastError();
+    D3F_VARIANT(f16, 0, fused_eval_f16_kernel<0>);
+    D3F_VARIANT(wide, 0, fused_eval_wide_kernel<0>);
+    D3F_VARIANT(true, 0, fused_eval_kernel<0>);
+    return hipErrorInvalidValue;
 }
 
 }  // namespace d3f

@@ -5,20 +5,18 @@
 
 namespace d3f {
 
-hipError_t launch_fused_eval(const EvalParams &P, int mode, hipStream_t stream)
+hipError_t launch_fused_eval(const EvalParams &P, FamilyId family, int mode, const Launch &L)
 {
-    if (P.n == 0) return hipSuccess;
-    bool wide = false, f16 = false, runs = false;
-    for (int s = 0; s < P.n_maps; ++s) {
-        wide |= (P.maps[s].unroll == -4);
-        f16 |= (P.maps[s].esize == 2);
-        runs |= (P.maps[s].runs > 0);
+    if (P.n == 0 && !L.describe) return hipSuccess;
+    switch (family) {
+    case kFamDistOnly: return launch_dist(P, mode, L);
+    case kFamWindow: return launch_window(P, L);
+    case kFamRuns: return launch_runs(P, L);
+    case kFamSliced: return launch_sliced(P, L);
+    case kFamRows: return launch_rows(P, L);
+    case kFamDirect: return launch_direct(P, L);
     }
-    if (mode == 0 && P.rows > 0) return launch_rows(P, stream);
-    if (mode == 0 && P.win_slices > 0) return launch_window(P, stream);
-    if (mode == 0 && P.sl_slices > 0) return launch_sliced(P, stream);
-    if (mode == 0 && runs && !f16 && !wide) return launch_runs(P, stream);
-    return launch_direct(P, mode, stream);
+    return hipErrorInvalidValue;
 }
 
 }  // namespace d3f

@@ -673,17 +673,13 @@ __global__ __launch_bounds__(kBlock, D3F_ROWS_WAVES) __attribute__((amdgpu_num_v
 #undef D3F_STAMP
 }
 
-hipError_t launch_rows(const EvalParams &P, hipStream_t stream)
+hipError_t launch_rows(const EvalParams &P, const Launch &L)
 {
     if (P.tile_pts != kRowsPts || P.maps[0].C != 1024 || P.maps[0].esize != 4 || P.V > 8) return hipErrorInvalidValue;
-    int64_t ntiles = (P.n + P.tile_pts - 1) / P.tile_pts;
-    if (P.walk_nx > 0) {
-        if (P.walk_tx * P.walk_ty * P.walk_tz != kRowsPts) return hipErrorInvalidValue;
-        ntiles = (int64_t)((P.walk_nx + P.walk_tx - 1) / P.walk_tx) * ((P.walk_ny + P.walk_ty - 1) / P.walk_ty) *
-                 ((P.walk_nz + P.walk_tz - 1) / P.walk_tz);
-    }
-    hipLaunchKernelGGL(fused_eval_rows_kernel, dim3((unsigned)ntiles), dim3(kBlock), 0, stream, P);
-    return hipGetLastError();
+    if (P.walk_nx > 0 && P.walk_tx * P.walk_ty * P.walk_tz != kRowsPts) return hipErrorInvalidValue;
+    const size_t lds = 0;                       // static LDS only
+    D3F_VARIANT(true, 0, fused_eval_rows_kernel);       // one instance
+    return hipErrorInvalidValue;
 }
 
 }  // namespace d3f

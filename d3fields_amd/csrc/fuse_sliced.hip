@@ -248,30 +248,26 @@ __global__ __launch_bounds__(kBlock, WAVES) void fused_eval_sliced_kernel(const 
     fused_eval_sliced_body<LG, VC, HALF>(P);
 }
 
-hipError_t launch_sliced(const EvalParams &P, hipStream_t stream)
+// The built instances and when each is taken (code: 100 + 10 * LG + VC, d3f_eval_plan.reserved).
+#define D3F_SLICED_VARIANT(COND, LG, VC, WAVES) D3F_VARIANT(COND, 100 + 10 * LG + VC, fused_eval_sliced_kernel<LG, VC, WAVES>)
+hipError_t launch_sliced(const EvalParams &P, const Launch &L)
 {
-    dim3 block(kBlock);
-    const int64_t units = (int64_t)P.sl_chunks * P.sl_slices;
-    const int64_t wgs = ((units + 7) / 8 + P.sl_ilv - 1) / P.sl_ilv * P.sl_ilv * 8 * P.sl_unit;
-    const size_t lds_s = (size_t)P.crec_offset + (size_t)P.tile_pts * P.V * 32 + (size_t)P.lds_pad;
-    const dim3 gs((unsigned)wgs);
+    const size_t lds = (size_t)P.crec_offset + (size_t)P.tile_pts * P.V * 32 + (size_t)P.lds_pad;
     if (P.maps[0].esize == 2) {                 // fp16-stored map: 16 lanes x 8 channels = 128-channel (256-byte) slices
-        if (P.sl_lg != 4 || P.sl_vc != 2) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((fused_eval_sliced_kernel<4, 2, 7, true>), gs, block, lds_s, stream, P);
-        return hipGetLastError();
+        D3F_VARIANT(P.sl_lg == 4 && P.sl_vc == 2, 142, fused_eval_sliced_kernel<4, 2, 7, true>);
+        return hipErrorInvalidValue;
     }
-    if (P.sl_lg == 5 && P.sl_vc == 2) hipLaunchKernelGGL((fused_eval_sliced_kernel<5, 2, 7>), gs, block, lds_s, stream, P);
-#ifndef D3F_EXPERIMENTS
-    else return hipErrorInvalidValue;          // (other slice widths / views in flight: experiments builds only)
-#else
-    else if (P.sl_lg == 5) hipLaunchKernelGGL((fused_eval_sliced_kernel<5, 4, 5>), gs, block, lds_s, stream, P);
-    else if (P.sl_lg == 4 && P.sl_vc == 2) hipLaunchKernelGGL((fused_eval_sliced_kernel<4, 2, 7>), gs, block, lds_s, stream, P);
-    else if (P.sl_lg == 4 && P.sl_vc == 1) hipLaunchKernelGGL((fused_eval_sliced_kernel<4, 1, 8>), gs, block, lds_s, stream, P);
-    else if (P.sl_lg == 4) hipLaunchKernelGGL((fused_eval_sliced_kernel<4, 4, 5>), gs, block, lds_s, stream, P);
-    else if (P.sl_vc == 2) hipLaunchKernelGGL((fused_eval_sliced_kernel<3, 2, 7>), gs, block, lds_s, stream, P);
-    else hipLaunchKernelGGL((fused_eval_sliced_kernel<3, 4, 5>), gs, block, lds_s, stream, P);
+    D3F_SLICED_VARIANT(P.sl_lg == 5 && P.sl_vc == 2, 5, 2, 7);
+#ifdef D3F_EXPERIMENTS                          // (other slice widths / views in flight: experiments builds only)
+    D3F_SLICED_VARIANT(P.sl_lg == 5, 5, 4, 5);
+    D3F_SLICED_VARIANT(P.sl_lg == 4 && P.sl_vc == 2, 4, 2, 7);
+    D3F_SLICED_VARIANT(P.sl_lg == 4 && P.sl_vc == 1, 4, 1, 8);
+    D3F_SLICED_VARIANT(P.sl_lg == 4, 4, 4, 5);
+    D3F_SLICED_VARIANT(P.sl_vc == 2, 3, 2, 7);
+    D3F_SLICED_VARIANT(true, 3, 4, 5);
 #endif
-    return hipGetLastError();
+    return hipErrorInvalidValue;
 }
+#undef D3F_SLICED_VARIANT
 
 }  // namespace d3f

@@ -916,32 +916,19 @@ hipError_t launch_window_gate_probe(const EvalParams &P, uint32_t *gate, int nsa
     return hipGetLastError();
 }
 
-hipError_t launch_window(const EvalParams &P, hipStream_t stream)
+// The built instances and when each is taken: <U, VC, W, 256, LPP, VF, SPARSE[, HALF]> -- vectors per lane, views with corner reads
+// in flight, workgroups per CU the variant is held to, block size, lanes per point, the view count as a compile-time constant (4 / 8:
+// software-pipelined point loop, 0: free), touched-texel pool, fp16-stored map.  Code (d3f_eval_plan.reserved): 2000 + 100 * U +
+// 10 * VC + workgroups per CU -- of the variant, and for the 16-lane variants the number the POOL is sized for (4, or 3 and fewer).
+#define D3F_WIN_CODE(U, VC, W, LPP) (2000 + 100 * U + 10 * VC + (LPP == 16 ? (P.win_occ >= 4 ? 4 : 3) : W))
+#define D3F_WIN_VARIANT(COND, U, VC, W, LPP, VF)                                                                                            \
+    D3F_VARIANT_LDS(true, (COND) && P.win_sparse, D3F_WIN_CODE(U, VC, W, LPP), fused_eval_window_kernel<U, VC, W, 256, LPP, VF, true>);    \
+    D3F_VARIANT_LDS(true, COND, D3F_WIN_CODE(U, VC, W, LPP), fused_eval_window_kernel<U, VC, W, 256, LPP, VF, false>)
+hipError_t launch_window(const EvalParams &P, const Launch &L)
 {
-    int64_t ntiles = (P.n + P.tile_pts - 1) / P.tile_pts;
-    if (P.walk_nx > 0)
-        ntiles = (int64_t)((P.walk_nx + P.walk_tx - 1) / P.walk_tx) * ((P.walk_ny + P.walk_ty - 1) / P.walk_ty) *
-                 ((P.walk_nz + P.walk_tz - 1) / P.walk_tz);
-    dim3 block(kBlock);
+    static_assert(kBlock == 256, "the instances below are named with the block size");
     const bool half = P.maps[0].esize == 2;        // fp16-stored map: 256-byte slices (lattices only, 16 lanes per point)
-    const size_t lds_w = (size_t)P.win_pool_offset + (size_t)(2 + P.win_pool_texels) * (half ? 256 : 512) * P.win_u;
-    dim3 gw((unsigned)((P.n + P.tile_pts - 1) / P.tile_pts));
-    if (P.walk_nx > 0) gw = dim3((unsigned)ntiles);
-#define D3F_WIN_LAUNCH_S(U_, VC_, W_, LPP_, VF_, SP_)                                                                          \
-    do {                                                                                                                       \
-        if (lds_w > 64 * 1024) {                                                                                               \
-            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(&fused_eval_window_kernel<U_, VC_, W_, kBlock, LPP_, VF_, SP_>), \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_w);                      \
-            if (ea != hipSuccess) return ea;                                                                                   \
-        }                                                                                                                      \
-        hipLaunchKernelGGL((fused_eval_window_kernel<U_, VC_, W_, kBlock, LPP_, VF_, SP_>), gw, block, lds_w, stream, P);      \
-    } while (0)
-#define D3F_WIN_LAUNCH_F(U_, VC_, W_, LPP_, VF_)                                                                               \
-    do {                                                                                                                       \
-        if (P.win_sparse) D3F_WIN_LAUNCH_S(U_, VC_, W_, LPP_, VF_, true);                                                      \
-        else D3F_WIN_LAUNCH_S(U_, VC_, W_, LPP_, VF_, false);                                                                  \
-    } while (0)
-#define D3F_WIN_LAUNCH(U_, VC_, W_, LPP_) D3F_WIN_LAUNCH_F(U_, VC_, W_, LPP_, 0)
+    const size_t lds = (size_t)P.win_pool_offset + (size_t)(2 + P.win_pool_texels) * (half ? 256 : 512) * P.win_u;
     // the product library holds the variants the planner picks by itself: 16 lanes x two vectors per point, at 4 or 3
     // workgroups per CU, with the view count fixed at 4 / 8 (software-pipelined point loop) or free; the others exist in
     // experiments builds only (measured and dropped)
@@ -949,51 +936,36 @@ hipError_t launch_window(const EvalParams &P, hipStream_t stream)
     const int vfix = (P.win_pipe && P.tile_pts == 64) ? (P.V == 4 ? 4 : (P.V == 8 ? 8 : 0)) : 0;
 #ifdef D3F_EXPERIMENTS
     // win_vc 2: two views' corner reads in flight in the plain view loop (round 3's form)
-    if (lpp16 && vfix == 0 && P.win_occ == 6) D3F_WIN_LAUNCH_F(1, 1, 6, 16, 0);          // plain loop at 6 / 5 workgroups per CU (smaller pools)
-    else if (lpp16 && vfix == 0 && P.win_occ == 5) D3F_WIN_LAUNCH_F(1, 1, 5, 16, 0);
-    else if (lpp16 && vfix == 0 && P.win_vc == 2 && P.win_occ >= 4) D3F_WIN_LAUNCH_F(1, 2, 4, 16, 0);
-    else if (lpp16 && vfix == 0 && P.win_vc == 2) D3F_WIN_LAUNCH_F(1, 2, 3, 16, 0);
-    else
+    D3F_WIN_VARIANT(lpp16 && vfix == 0 && P.win_occ == 6, 1, 1, 6, 16, 0);          // plain loop at 6 / 5 workgroups per CU (smaller pools)
+    D3F_WIN_VARIANT(lpp16 && vfix == 0 && P.win_occ == 5, 1, 1, 5, 16, 0);
+    D3F_WIN_VARIANT(lpp16 && vfix == 0 && P.win_vc == 2 && P.win_occ >= 4, 1, 2, 4, 16, 0);
+    D3F_WIN_VARIANT(lpp16 && vfix == 0 && P.win_vc == 2, 1, 2, 3, 16, 0);
 #endif
     // ONE register budget (<= 128 VGPRs: four waves per SIMD) serves every pool size: the workgroups per CU follow from the
     // dynamic LDS of the launch (win_occ sized the pool), not from the kernel variant -- up to round 4 a second set held to
     // __launch_bounds__(256, 3) existed and allocated 121 instead of 125 registers, the same occupancy step
-#define D3F_WIN_LAUNCH_H(VF_)                                                                                                 \
-    do {                                                                                                                       \
-        if (lds_w > 64 * 1024) {                                                                                               \
-            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(&fused_eval_window_kernel<1, 1, 4, kBlock, 16, VF_, false, true>), \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_w);                      \
-            if (ea != hipSuccess) return ea;                                                                                   \
-        }                                                                                                                      \
-        hipLaunchKernelGGL((fused_eval_window_kernel<1, 1, 4, kBlock, 16, VF_, false, true>), gw, block, lds_w, stream, P);    \
-    } while (0)
     if (half) {
         if (!lpp16 || P.win_sparse) return hipErrorInvalidValue;
-        if (vfix == 4) D3F_WIN_LAUNCH_H(4);
-        else if (vfix == 8) D3F_WIN_LAUNCH_H(8);
-        else D3F_WIN_LAUNCH_H(0);
-        return hipGetLastError();
+        D3F_VARIANT_LDS(true, vfix == 4, D3F_WIN_CODE(1, 1, 4, 16), fused_eval_window_kernel<1, 1, 4, 256, 16, 4, false, true>);
+        D3F_VARIANT_LDS(true, vfix == 8, D3F_WIN_CODE(1, 1, 4, 16), fused_eval_window_kernel<1, 1, 4, 256, 16, 8, false, true>);
+        D3F_VARIANT_LDS(true, true, D3F_WIN_CODE(1, 1, 4, 16), fused_eval_window_kernel<1, 1, 4, 256, 16, 0, false, true>);
     }
-#undef D3F_WIN_LAUNCH_H
-    if (lpp16 && vfix == 4) D3F_WIN_LAUNCH_F(1, 1, 4, 16, 4);
-    else if (lpp16 && vfix == 8) D3F_WIN_LAUNCH_F(1, 1, 4, 16, 8);
-    else if (lpp16) D3F_WIN_LAUNCH(1, 1, 4, 16);
+    D3F_WIN_VARIANT(lpp16 && vfix == 4, 1, 1, 4, 16, 4);
+    D3F_WIN_VARIANT(lpp16 && vfix == 8, 1, 1, 4, 16, 8);
+    D3F_WIN_VARIANT(lpp16, 1, 1, 4, 16, 0);
 #ifdef D3F_EXPERIMENTS
-    else if (P.win_u == 1 && P.win_occ >= 4) D3F_WIN_LAUNCH(1, 4, 4, 32);
-    else if (P.win_u == 1 && P.win_occ == 3) D3F_WIN_LAUNCH(1, 4, 3, 32);
-    else if (P.win_u == 1) D3F_WIN_LAUNCH(1, 4, 2, 32);
-    else if (P.win_u == 2 && P.win_vc == 2) D3F_WIN_LAUNCH(2, 2, 2, 32);
-    else if (P.win_u == 2) D3F_WIN_LAUNCH(2, 1, 2, 32);
-    else if (P.win_u == 3 && P.win_vc == 2) D3F_WIN_LAUNCH(3, 2, 2, 32);
-    else if (P.win_u == 3) D3F_WIN_LAUNCH(3, 1, 2, 32);
-    else D3F_WIN_LAUNCH(4, 1, 2, 32);
-#else
-    else return hipErrorInvalidValue;
+    D3F_WIN_VARIANT(P.win_u == 1 && P.win_occ >= 4, 1, 4, 4, 32, 0);
+    D3F_WIN_VARIANT(P.win_u == 1 && P.win_occ == 3, 1, 4, 3, 32, 0);
+    D3F_WIN_VARIANT(P.win_u == 1, 1, 4, 2, 32, 0);
+    D3F_WIN_VARIANT(P.win_u == 2 && P.win_vc == 2, 2, 2, 2, 32, 0);
+    D3F_WIN_VARIANT(P.win_u == 2, 2, 1, 2, 32, 0);
+    D3F_WIN_VARIANT(P.win_u == 3 && P.win_vc == 2, 3, 2, 2, 32, 0);
+    D3F_WIN_VARIANT(P.win_u == 3, 3, 1, 2, 32, 0);
+    D3F_WIN_VARIANT(true, 4, 1, 2, 32, 0);
 #endif
-#undef D3F_WIN_LAUNCH
-#undef D3F_WIN_LAUNCH_F
-#undef D3F_WIN_LAUNCH_S
-    return hipGetLastError();
+    return hipErrorInvalidValue;
 }
+#undef D3F_WIN_VARIANT
+#undef D3F_WIN_CODE
 
 }  // namespace d3f

@@ -554,53 +554,24 @@ class Fusion:
                                                1 if want_inter else 0, ctypes.byref(plan))
         if rc != 0:
             return
-        runs = any(plan.staged[s] >= 16 for s in range(n_maps))
-        wide = any(plan.vectors_per_lane[s] == -4 for s in range(n_maps))
-        f16 = any(maps[s].dtype == _lib.DTYPE_F16 for s in range(n_maps))
-        kernel = ("fused_eval_f16_kernel<0>" if f16 else "fused_eval_wide_kernel<0>" if wide else "fused_eval_kernel<0>")
-        if n_maps == 0 and int(plan.reorder) == 0 and int(views.V) <= 8:
-            # the distance-only pass (fuse_direct.hip): <mode, view count (0: five to eight), waves per SIMD, depth maps tiled first?, points from grid axes?>
-            tiled = have_ws and n >= (1 << 22)
-            kernel = "fused_eval_dist_kernel<0, %d, %d, %s, false>" % (int(views.V) if int(views.V) <= 4 else 0, 8 if int(views.V) <= 2 else 6, "true" if tiled else "false")
-        window = 2000 <= plan.reserved < 3000
-        if window:
-            r = plan.reserved - 2000
-            w0 = [s for s in range(n_maps) if plan.staged[s] == 3][0]           # the windowed map (any position in the call)
-            # (the last template argument: the view count as a compile-time constant, 4 / 8 -> software-pipelined point loop)
-            vfix = int(views.V) if (int(views.V) in (4, 8) and int(plan.tile_points) == 64 and plan.lanes_per_point[w0] == 16) else 0
-            # (third argument: the register budget the variant is built for -- 4 waves per SIMD for every 16-lane variant; the plan's
-            #  last digit is the workgroups per CU the POOL is sized for)
-            kernel = "fused_eval_window_kernel<%d, %d, %d, 256, %d, %d, %s%s>" % (r // 100, r // 10 % 10, 4 if plan.lanes_per_point[w0] == 16 else r % 10, plan.lanes_per_point[w0], vfix,
-                                                                                "false" if lattice is not None else "true",
-                                                                                ", true" if maps[w0].dtype == _lib.DTYPE_F16 else "")
-        elif any(plan.staged[s] == 5 for s in range(n_maps)):                  # the rows of a 32-point brick in registers (fuse_rows.hip)
-            kernel = "fused_eval_rows_kernel"
-        elif plan.reserved >= 100:
-            lg, vc = (plan.reserved - 100) // 10, (plan.reserved - 100) % 10
-            kernel = "fused_eval_sliced_kernel<%d, %d, %d%s>" % (lg, vc, {1: 8, 2: 7, 4: 5}.get(vc, 5), ", true" if f16 else "")
-        elif runs and not f16 and not wide:
-            s0 = [s for s in range(n_maps) if plan.staged[s] >= 16][0]
-            kernel = "fused_eval_runs_kernel<0, %d, %d, %d>" % (plan.vectors_per_lane[s0], plan.staged[s0] - 16, plan.reserved)
-        sliced = 100 <= plan.reserved < 200
+        family = (self._lib.d3f_plan_family_name(int(plan.family)) or b"?").decode()
         order = {2: "closed-form brick walk of the lattice (no keys, no sort)", 1: "Hilbert-cell order (512^3 key grid over the cloud's box, counting sort by a key prefix + exact rank inside, hand-written)",
                  0: "caller order"}[int(plan.reorder)]
-        order += "; channel-sliced over the XCDs" if sliced else ""
-        if window:
+        order += "; channel-sliced over the XCDs" if family == "channel-sliced" else ""
+        if family == "lds-window":
             order += "; %d-point bricks through texel windows in LDS" % int(plan.tile_points)
-        elif kernel == "fused_eval_rows_kernel":
+        elif family == "register-rows":
             order += "; 32-point bricks, their fused rows in registers, walked cell by cell"
-        elif runs:
+        elif family == "cell-runs":
             order += "; cell runs of %d consecutive points" % (max(plan.staged[s] for s in range(n_maps)) - 16)
-        self._last_plan = {"kernel": kernel, "tile_points": int(plan.tile_points), "point_order": order,
-                           "workgroups": int(plan.workgroups), "lattice": lattice, "gated_window": bool(plan.gated_window),
-                           "family": (self._lib.d3f_plan_family_name(int(plan.family)) or b"?").decode()}
+        # (kernel: the instance's entry point and template arguments, named by the library -- csrc/fuse_<family>.hip)
+        self._last_plan = {"kernel": plan.kernel.decode(), "tile_points": int(plan.tile_points), "point_order": order,
+                           "workgroups": int(plan.workgroups), "lattice": lattice, "gated_window": bool(plan.gated_window), "family": family}
         if plan.gated_window:
             # a cloud on the gated pair of launches (ABI 5): the fields above describe the cell-run side; the window side is the
             # sparse-pool window kernel on 64-point tiles of the same order.  last_gate() says which one ran.
-            r = int(plan.reserved2) - 2000
             self._last_plan["window_side"] = {
-                "kernel": "fused_eval_window_kernel<%d, %d, 4, 256, 16, %d, true>" % (r // 100, r // 10 % 10, int(views.V) if int(views.V) in (4, 8) else 0),
-                "tile_points": 64,
+                "kernel": plan.window_kernel.decode(), "tile_points": 64,
                 "point_order": order.split(";")[0] + "; 64-point tiles through touched-texel windows in LDS (device-gated against the cell runs)"}
 
     def last_gate(self):

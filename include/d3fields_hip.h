@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define D3F_ABI_VERSION 7
+#define D3F_ABI_VERSION 8
 
 #define D3F_OK 0
 #define D3F_ERR_INVALID_ARG (-1)  /* null pointer, negative count, bad enum               */
@@ -194,14 +194,20 @@ void d3f_profile_next_eval(void *start_event, void *stop_event);
 
 /* What d3f_eval would launch for these shapes (no device work; usable without a GPU): the launch
  * geometry and the per-map lane mapping the host logic picked.  For tests and tuning. */
+#define D3F_KERNEL_NAME_MAX 80
 typedef struct d3f_eval_plan {
     int32_t tile_points;                    /* query points per 256-thread workgroup                  */
     int32_t reorder;                        /* 1: points are walked in Hilbert order (sorted keys); 2: closed-form brick
                                                walk of a lattice (d3f_eval_grid / d3f_eval_lattice)    */
     int32_t lds_bytes;                      /* dynamic LDS per workgroup                              */
-    int32_t reserved;                       /* cell-run gather: waves per SIMD its kernel variant is built for; channel-sliced
-                                               launch: 100 + 10*log2(lanes per point) + views in flight; LDS texel-window
-                                               kernel: 2000 + 100*U + 10*VC + W (its template arguments); else 0 */
+    int32_t reserved;                       /* legacy code of the instance `kernel` names (read `kernel` instead).  Cell-run
+                                               gather: waves per SIMD the instance is built for; channel-sliced launch:
+                                               100 + 10*log2(lanes per point) + views in flight; LDS texel-window kernel:
+                                               2000 + 100*U + 10*VC + workgroups per CU (16 lanes per point: the number the
+                                               pool is sized for); else 0.  The digits are the INSTANCE's
+                                               template arguments: an experiments build whose knob asks for views in flight that no
+                                               built instance has (D3F_EXP_WINDOW_VC=2 with 4 / 8 views, D3F_EXP_SLICED_VC=1 with 32 or
+                                               8 lanes) reports the instance launched, where ABI 7 echoed the knob */
     int64_t workgroups;
     int32_t vector_floats[D3F_MAX_MAPS];    /* 4 / 2 / 1 floats per load                              */
     int32_t lanes_per_point[D3F_MAX_MAPS];
@@ -217,6 +223,11 @@ typedef struct d3f_eval_plan {
                                                2 cell-runs, 3 channel-sliced, 4 direct, 5 register-rows (d3f_plan_family_name;
                                                csrc/d3f_plan.h)                                                                    */
     int32_t reserved3;
+    char kernel[D3F_KERNEL_NAME_MAX];       /* ABI 8.  the kernel instance the launch takes, as its symbol prints: entry point and
+                                               template arguments, e.g. "fused_eval_sliced_kernel<5, 2, 7>" (written by the row of the
+                                               family's variant list that also launches it, csrc/fuse_<family>.hip); "" when no
+                                               built instance takes these parameters (d3f_eval would return D3F_ERR_HIP)          */
+    char window_kernel[D3F_KERNEL_NAME_MAX];/* ABI 8.  gated_window: the instance on the window side of the gate; else ""          */
 } d3f_eval_plan;
 int d3f_eval_plan_query(const d3f_views *views, int64_t n, const d3f_channel_map *maps, int32_t n_maps,
                         uint32_t flags, int32_t have_workspace, int32_t want_inter, d3f_eval_plan *plan);

@@ -48,6 +48,11 @@ def test_struct_layouts_match_header():
     hdr = open(os.path.join(ROOT, "include", "d3fields_hip.h")).read()
     assert re.search(r"const float \*pose;[^}]*const uint32_t \*depth_nonfinite;[^}]*\} d3f_views;", hdr)
     assert re.search(r"int64_t stride_v, stride_y, stride_x;\s*const uint32_t \*nonfinite;[^}]*\} d3f_channel_map;", hdr)
+    # d3f_eval_plan (ABI 8): the numeric fields of ABI 5-7 in place, then the two kernel names
+    assert ctypes.sizeof(_lib.EvalPlan) == 168 + 2 * _lib.KERNEL_NAME_MAX and _lib.EvalPlan.family.offset == 160
+    assert _lib.EvalPlan.kernel.offset == 168 and _lib.EvalPlan.window_kernel.offset == 168 + _lib.KERNEL_NAME_MAX
+    assert int(re.search(r"#define D3F_KERNEL_NAME_MAX (\d+)", hdr).group(1)) == _lib.KERNEL_NAME_MAX
+    assert re.search(r"int32_t reserved3;\s*char kernel\[D3F_KERNEL_NAME_MAX\];[^}]*char window_kernel\[D3F_KERNEL_NAME_MAX\];[^}]*\} d3f_eval_plan;", hdr)
     # d3f_col_stat travels between ranks as raw bytes: float, float, int64 = 16 B (tests/test_sharding_gloo.py uses it)
     hdr = open(os.path.join(ROOT, "include", "d3fields_hip.h")).read()
     assert re.search(r"typedef struct d3f_col_stat \{\s*float max_logit;[^}]*float sum_exp;[^}]*int64_t argmax;[^}]*\} d3f_col_stat;", hdr)
