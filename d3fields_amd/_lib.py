@@ -9,7 +9,7 @@ import os
 
 from . import build as _build
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 # status codes (include/d3fields_hip.h)
 OK = 0
@@ -28,6 +28,7 @@ CHECK_WORDS_ARE_ZERO = 1
 TRACK_STALL_SENTINEL = 0x57A11ED
 MAX_VIEWS = 64
 MAX_MAPS = 8
+MAX_PROJECTION = 64
 KERNEL_NAME_MAX = 80
 GAUSSIAN_MAX_RADIUS = 64
 DTYPE_F32 = 0
@@ -81,6 +82,7 @@ SIGNATURES = {
                                 _vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _i64, _vp]),
     "d3f_map_check": (ctypes.c_int, [ctypes.POINTER(ChannelMap), _i32, _vp, _vp]),
     "d3f_map_check_many": (ctypes.c_int, [ctypes.POINTER(ChannelMap), ctypes.POINTER(_i32), _i32, ctypes.POINTER(_vp), _u32, _vp]),
+    "d3f_project_maps": (ctypes.c_int, [ctypes.POINTER(ChannelMap), _i32, _vp, _i32, _vp, _vp]),
     "d3f_eval_workspace_bytes": (_i64, [_i64]),
     "d3f_eval_dist_workspace_bytes": (_i64, [ctypes.POINTER(Views), _i64]),
     "d3f_eval_gate_offset": (_i64, [_i64]),

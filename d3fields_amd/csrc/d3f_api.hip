@@ -782,6 +782,21 @@ int d3f_map_check_many(const d3f_channel_map *maps, const int32_t *views, int32_
     return e == hipSuccess ? D3F_OK : hip_fail(e, "map_check_many launch");
 }
 
+int d3f_project_maps(const d3f_channel_map *src, int32_t V, const float *W, int32_t k, float *dst, void *stream)
+{
+    if (!src || !W || !dst) return fail(D3F_ERR_INVALID_ARG, "project_maps: NULL pointer");
+    if (!src->data) return fail(D3F_ERR_INVALID_ARG, "project_maps: data pointer is NULL");
+    if (k < 1 || k > D3F_MAX_PROJECTION) return fail(D3F_ERR_BAD_SHAPE, "project_maps: k=%d outside [1,%d]", k, D3F_MAX_PROJECTION);
+    if (V < 1 || src->fh < 1 || src->fw < 1 || src->C < 1) return fail(D3F_ERR_BAD_SHAPE, "project_maps: V=%d fh=%d fw=%d C=%d", V, src->fh, src->fw, src->C);
+    if (src->dtype != D3F_DTYPE_F32 && src->dtype != D3F_DTYPE_F16) return fail(D3F_ERR_BAD_DTYPE, "project_maps: dtype %d unsupported", src->dtype);
+    const int es = src->dtype == D3F_DTYPE_F16 ? 2 : 4;
+    if (!aligned(src->data, es) || !aligned(W, 4) || !aligned(dst, 4)) return fail(D3F_ERR_BAD_LAYOUT, "project_maps: pointers must be aligned to their element size");
+    if (src->stride_x < src->C || src->stride_y < 0 || src->stride_v < 0) return fail(D3F_ERR_BAD_LAYOUT, "project_maps: strides do not describe a channels-last map");
+    hipError_t e = d3f::launch_project_maps(src->data, V, src->fh, src->fw, src->C, src->stride_v, src->stride_y, src->stride_x, es == 2, W, k, dst,
+                                            static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "project_maps launch");
+}
+
 int d3f_onehot2instance(const float *onehot, int64_t n, int32_t NI, uint8_t *out, void *stream)
 {
     if (n < 0 || NI < 1 || NI > 256) return fail(D3F_ERR_BAD_SHAPE, "onehot2instance: n=%lld NI=%d (NI must be in [1,256])", (long long)n, NI);

@@ -229,6 +229,10 @@ hipError_t launch_map_check_many(const void *const *data, const int64_t *nbytes,
 hipError_t launch_onehot2instance(const float *onehot, int64_t n, int NI, uint8_t *out, hipStream_t s);
 hipError_t launch_instance2onehot(const uint8_t *inst, int64_t n, int NI, uint8_t *out, hipStream_t s);
 
+// proj_kernels.hip
+hipError_t launch_project_maps(const void *data, int V, int fh, int fw, int C, int64_t sv, int64_t sy, int64_t sx, bool half, const float *W,
+                               int k, float *dst, hipStream_t s);
+
 // corr_kernels.hip
 struct ColStat {   // running softmax statistics of one column (16 B)
     float m;       // max of -d*scale

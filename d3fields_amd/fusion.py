@@ -11,6 +11,7 @@ There is no CPU or torch-op fallback: query points must live on the ROCm device 
 shared library must load, otherwise an exception is raised.
 """
 import ctypes
+import weakref
 
 import numpy as np
 import torch
@@ -260,6 +261,8 @@ class Fusion:
         self._last_plan = None
         self.record_plans = False               # last_plan(): query the launch plan of every eval (bench.py, tests)
         self.detect_lattice = True              # probe new query tensors for create_init_grid's layout (brick walk, no sort)
+        self._projections = {}                  # add_projection: name -> linear head (source key, W [k,C] fp32, b = mean W^T [k] fp32)
+        self._projected = {}                    # name -> (weakref(source tensor), signature, projected map [V,fh,fw,k]); never in curr_obs_torch
         self._lib = _lib.load()                 # fail at construction if the HIP library is missing
 
     # ---- observation state (reference fusion.py:686-714) --------------------------------
@@ -283,6 +286,113 @@ class Fusion:
             self.curr_obs_torch[k] = _as_device_tensor(obs[k], torch.float32, self.device)
         _, self.H, self.W = obs["depth"].shape
         self._finite_cache.clear()
+        self._projected.clear()
+
+    # ---- descriptors through a linear head (a fitted PCA, a policy's 16..64-d head) ---------------------------------------
+    # Fusion is linear in the channel vector: with s_v = valid_v * wgt_v / (cnt + 1e-6),
+    #     (sum_v s_v bilinear(map_v) - mean) W^T  =  sum_v s_v bilinear(map_v W^T)  -  mean W^T,
+    # so the MAPS are projected once per observation (d3f_project_maps, csrc/proj_kernels.hip), the k-channel map is queried
+    # through the ordinary kernel families, and the constant b = mean W^T is subtracted from the [N,k] result.  No C-wide row
+    # is ever written.
+    def add_projection(self, name, source="dino_feats", components=None, mean=None, pca=None):
+        """Registers `name` as a valid entry of return_names in eval / batch_eval / eval_grid: [N,k] float32, equal to
+        pca.transform(fused `source` row) -- (row - mean) @ components.T, all-invalid points give -mean @ components.T, the
+        transform of the reference's zero row; '<name>_inter' is [V,N,k], also minus the constant.
+
+        pca: any object with mean_ and components_ (sklearn's whiten / explained_variance_ are folded into the rows of W, as
+        mesh.pca_project applies them); or components [k,C] and an optional mean [C].  W is rounded to float32 once;
+        b = mean W^T is computed in float64 on the host and rounded to float32."""
+        if not isinstance(name, str) or not name:
+            raise ValueError("add_projection: name must be a non-empty string")
+        if name in self.curr_obs_torch:
+            raise ValueError("add_projection: %r is a key of curr_obs_torch; a projection needs a name of its own" % name)
+        if name.endswith("_inter") or name in ("dist", "valid_mask", "grid_shape"):
+            raise ValueError("add_projection: %r would collide with an output key of eval" % name)
+        if pca is not None:
+            if components is not None or mean is not None:
+                raise ValueError("add_projection: pass either pca or components / mean")
+            comp = np.asarray(pca.components_, dtype=np.float64)
+            mu = np.asarray(pca.mean_, dtype=np.float64)
+            if getattr(pca, "whiten", False):
+                comp = comp / np.sqrt(np.asarray(pca.explained_variance_, dtype=np.float64))[:, None]
+        else:
+            if components is None:
+                raise ValueError("add_projection: pass pca or components")
+            host = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else x
+            comp = np.asarray(host(components), dtype=np.float64)
+            mu = None if mean is None else np.asarray(host(mean), dtype=np.float64)
+        if comp.ndim != 2:
+            raise ValueError("add_projection: components must be [k,C], got shape %s" % (comp.shape,))
+        k, C = comp.shape
+        if not 1 <= k <= _lib.MAX_PROJECTION or C < 1:
+            raise ValueError("add_projection: k=%d outside 1..%d (C=%d)" % (k, _lib.MAX_PROJECTION, C))
+        if mu is None:
+            mu = np.zeros(C, dtype=np.float64)
+        if mu.shape != (C,):
+            raise ValueError("add_projection: mean has shape %s, components are [%d,%d]" % (mu.shape, k, C))
+        W = np.ascontiguousarray(comp.astype(np.float32))
+        b = (W.astype(np.float64) @ mu).astype(np.float32)
+        self._projections[name] = {"source": source, "k": k, "C": C, "W": torch.from_numpy(W), "b": torch.from_numpy(b), "dev": {}}
+        self._projected.pop(name, None)
+
+    def remove_projection(self, name):
+        del self._projections[name]
+        self._projected.pop(name, None)
+        self._finite_cache.pop(name, None)
+
+    def projections(self):
+        """name -> (source key, k) of every registered head"""
+        return {n: (p["source"], p["k"]) for n, p in self._projections.items()}
+
+    def _head_on(self, name, dev):
+        """(W [k,C], b [k]) of a head on `dev` (copied there once)"""
+        p = self._projections[name]
+        if dev not in p["dev"]:
+            p["dev"][dev] = (p["W"].to(dev), p["b"].to(dev))
+        return p["dev"][dev]
+
+    def _projected_map(self, name, dev):
+        """The [V,fh,fw,k] float32 map of head `name`: d3f_project_maps on the caller's stream on the first query that names
+        it, reused while the source tensor OBJECT, its version counter and the head are unchanged (update(), a new
+        curr_obs_torch[source] and invalidate_map_checks() drop it)."""
+        p = self._projections[name]
+        if name in self.curr_obs_torch:
+            raise ValueError("projection %r: the name has become a key of curr_obs_torch" % name)
+        src = self.curr_obs_torch[p["source"]]          # KeyError for an unknown source, like any unknown name
+        if not isinstance(src, torch.Tensor) or src.dim() != 4:
+            raise ValueError("curr_obs_torch[%r] must be a (V,h,w,C) tensor" % p["source"])
+        if src.device != dev or src.dtype not in (torch.float32, torch.float16):
+            raise RuntimeError("curr_obs_torch[%r] must be float32 or float16 on %s" % (p["source"], dev))
+        if src.shape[3] != p["C"]:
+            raise ValueError("projection %r has C=%d but curr_obs_torch[%r] has %d channels" % (name, p["C"], p["source"], src.shape[3]))
+        sig = (src._version, tuple(src.shape), tuple(src.stride()), src.data_ptr())
+        hit = self._projected.get(name)
+        if hit is not None and hit[0]() is src and hit[1] == sig:
+            return hit[2]
+        m = src if (src.stride(3) == 1 and src.stride(2) >= src.shape[3] and min(src.stride()) >= 0) else src.contiguous()
+        W, _ = self._head_on(name, dev)
+        out = torch.empty(tuple(src.shape[:3]) + (p["k"],), dtype=torch.float32, device=dev)
+        desc = _lib.ChannelMap(m.data_ptr(), m.shape[1], m.shape[2], m.shape[3], _lib.DTYPE_F16 if m.dtype == torch.float16 else _lib.DTYPE_F32,
+                               m.stride(0), m.stride(1), m.stride(2), None)
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.d3f_project_maps(ctypes.byref(desc), m.shape[0], _lib.ptr(W), p["k"], _lib.ptr(out), _lib.current_stream_handle(dev)))
+        self._projected[name] = (weakref.ref(src), sig, out)
+        return out
+
+    def _query_map(self, name, dev):
+        """The tensor a query reads for `name`: curr_obs_torch[name], or the projected map of a registered head."""
+        if name in self._projections:
+            return self._projected_map(name, dev)
+        return self.curr_obs_torch[name]
+
+    def _subtract_offsets(self, outputs, names, dev, return_inter=False):
+        """out[name] -= b for every projected name (and its '_inter'): tiny [N,k] passes on the caller's stream"""
+        for k in names:
+            if k in self._projections:
+                b = self._head_on(k, dev)[1]
+                outputs[k] -= b
+                if return_inter:
+                    outputs[k + "_inter"] -= b
 
     # ---- the hot path ---------------------------------------------------------------------
     def _check_query(self, pts):
@@ -433,8 +543,10 @@ class Fusion:
 
     def invalidate_map_checks(self):
         """Forget the device-side 'this map holds only finite values' verdicts: call after writing into a curr_obs_torch
-        tensor in place from outside torch (the next query re-checks the tensors it reads, ~0.35 ms per 1.9 GB)."""
+        tensor in place from outside torch (the next query re-checks the tensors it reads, ~0.35 ms per 1.9 GB, and projects
+        the sources of add_projection's heads again)."""
         self._finite_cache.clear()
+        self._projected.clear()
 
     def _probe_now(self, pts_c, stream):
         """(lattice dims or None, unordered?) of a query tensor from ONE d3f_points_probe launch and ONE host sync (round 6; rounds
@@ -631,7 +743,7 @@ class Fusion:
                 views.depth_nonfinite = self._finite_word("depth", self.curr_obs_torch["depth"], batch=checks)
             used_maps = []
             for s, k in enumerate(names):
-                m = self.curr_obs_torch[k]                 # KeyError for unknown names, like the reference
+                m = self._query_map(k, dev)                # KeyError for unknown names, like the reference
                 if not isinstance(m, torch.Tensor) or m.dim() != 4 or m.shape[0] != V:
                     raise ValueError("curr_obs_torch[%r] must be a (V,h,w,C) tensor" % k)
                 if m.device != dev or m.dtype not in (torch.float32, torch.float16):
@@ -672,6 +784,7 @@ class Fusion:
                 _lib.check(lib.d3f_eval_lattice(ctypes.byref(views), _lib.ptr(pts_c), dims[0], dims[1], dims[2], maps, len(names),
                                                 self.mu, flags, _lib.ptr(dist), _lib.ptr(valid), fused,
                                                 inter if return_inter else None, stream))
+                self._subtract_offsets(outputs, names, dev, return_inter)
                 return outputs, (pts_c, keep[0], keep[1], keep[2], used_maps, (views.depth_nonfinite, [maps[s].nonfinite for s in range(len(names))]))
             if self.reorder_points and names and n >= 65536:
                 map_bytes = sum(m.numel() * m.element_size() for m in used_maps)
@@ -711,6 +824,7 @@ class Fusion:
             _lib.check(lib.d3f_eval(ctypes.byref(views), _lib.ptr(pts_c), n, maps, len(names), self.mu, flags,
                                     _lib.ptr(dist), _lib.ptr(valid), fused, inter if return_inter else None,
                                     _lib.ptr(ws), ws_bytes, stream))
+            self._subtract_offsets(outputs, names, dev, return_inter)
         return outputs, (pts_c, keep[0], keep[1], keep[2], used_maps, (views.depth_nonfinite, [maps[s].nonfinite for s in range(len(names))]))
 
     def _backward(self, saved, grad_dist, grad_fused):
@@ -789,7 +903,7 @@ class Fusion:
         if words:
             views.depth_nonfinite = self._finite_word("depth", self.curr_obs_torch["depth"])
         for s, k in enumerate(names):
-            m = self.curr_obs_torch[k]
+            m = self._query_map(k, dev)
             if m.device != dev or m.dtype not in (torch.float32, torch.float16):
                 raise RuntimeError("curr_obs_torch[%r] must be float32 or float16 on %s" % (k, dev))
             m_caller = m
@@ -806,6 +920,7 @@ class Fusion:
         with torch.cuda.device(dev):
             _lib.check(lib.d3f_eval_grid(ctypes.byref(views), ctypes.byref(grid), maps, len(names), self.mu, flags,
                                          _lib.ptr(dist), _lib.ptr(valid), fused, _lib.current_stream_handle(dev)))
+            self._subtract_offsets(out, names, dev)
         return out
 
     def grid_shell(self, boundaries, step_size, dist_threshold=0.005):

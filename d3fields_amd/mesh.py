@@ -11,7 +11,7 @@ import torch
 
 from . import _lib
 
-__all__ = ["Mesh", "marching_cubes", "gaussian_filter", "mesh_vertices", "color_mesh", "descriptor_mesh"]
+__all__ = ["Mesh", "marching_cubes", "gaussian_filter", "mesh_vertices", "color_mesh", "descriptor_mesh", "descriptor_colors"]
 
 Mesh = collections.namedtuple("Mesh", ["vertices", "faces", "vertex_colors"])
 Mesh.__doc__ = """What trimesh.Trimesh(vertices=, faces=, vertex_colors=) receives in the reference, as arrays (returned where trimesh is not
@@ -144,6 +144,26 @@ def descriptor_rgb(res, params):
     rgb[:, :proj.shape[1]] = (proj - lo) / (hi - lo)
     rgb[bg.to(rgb.device)] = 0.8
     return torch.flip(rgb, dims=(-1,))
+
+
+def descriptor_colors(proj, mask, mask_out_bg=False):
+    """uint8 [N,4] vertex colours from ALREADY-PROJECTED descriptors (Fusion.add_projection with a 3-component head) and the
+    fused mask [N,NI], where the inputs live: the colour rule of create_descriptor_mesh (fusion.py:1394-1407) -- per-component
+    min / max normalisation over all rows, background rows (instance 0) 0.8, BGR order, (x * 255) truncated, alpha 255 -- in
+    float32, without the wide rows and the float64 pca_project of descriptor_rgb.  mask_out_bg: both branches are the same
+    lines in the reference."""
+    from .fusion import onehot2instance
+    proj = torch.as_tensor(proj).detach().to(torch.float32)
+    mask = torch.as_tensor(mask).detach()
+    if proj.dim() != 2 or not 1 <= proj.shape[1] <= 3 or mask.dim() != 2 or mask.shape[0] != proj.shape[0]:
+        raise ValueError("descriptor_colors: proj must be [N,<=3] and mask [N,NI], got %s and %s" % (tuple(proj.shape), tuple(mask.shape)))
+    inst = onehot2instance(mask) if mask.is_cuda else torch.from_numpy(onehot2instance(mask.numpy()))
+    bg = (inst == 0).to(proj.device)
+    lo, hi = proj.min(dim=0).values, proj.max(dim=0).values
+    rgb = torch.zeros((proj.shape[0], 3), dtype=torch.float32, device=proj.device)
+    rgb[:, :proj.shape[1]] = (proj - lo) / (hi - lo)
+    rgb[bg] = 0.8
+    return _alpha((torch.flip(rgb, dims=(-1,)) * 255).to(torch.uint8))
 
 
 def descriptor_mesh(vertices, triangles, res, params, mask_out_bg):

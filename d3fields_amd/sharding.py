@@ -172,8 +172,9 @@ def broadcast_observation(fusion, src=0, group=None, keys=None):
     """Replicates rank `src`'s curr_obs_torch tensors (maps, depth, K, pose) to every rank: the
     once-per-update setup cost of the sharded mode (dense C4 maps: 30 GB per rank -- pass `keys` to re-send only
     what the update changed, e.g. ('depth', 'mask') while the feature maps of a static scene stay).  Returns the
-    bytes this rank received.  The in-place overwrite invalidates the shim's cached "maps are finite" verdicts and
-    the cached point-order probe, so the next query re-checks the new data."""
+    bytes this rank received.  The in-place overwrite does not move the tensors' version counters, so the shim's cached
+    "maps are finite" verdicts and the projected maps of add_projection's heads are dropped here by hand: the next query
+    re-checks and re-projects the new data."""
     rank, world = _world(group)
     if world == 1:
         return 0
@@ -186,6 +187,8 @@ def broadcast_observation(fusion, src=0, group=None, keys=None):
                 received += t.numel() * t.element_size()
     if hasattr(fusion, "_finite_cache"):
         fusion._finite_cache.clear()
+    if hasattr(fusion, "_projected"):
+        fusion._projected.clear()
     return received
 
 

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define D3F_ABI_VERSION 8
+#define D3F_ABI_VERSION 9
 
 #define D3F_OK 0
 #define D3F_ERR_INVALID_ARG (-1)  /* null pointer, negative count, bad enum               */
@@ -138,6 +138,19 @@ int d3f_map_check(const d3f_channel_map *map, int32_t V, uint32_t *word_out, voi
 #define D3F_CHECK_WORDS_ARE_ZERO 1u
 int d3f_map_check_many(const d3f_channel_map *maps, const int32_t *views, int32_t n, uint32_t *const *words_out, uint32_t flags,
                        void *stream);
+
+/* ABI 9.  A channel map through a linear head: dst[v,y,x,j] = sum_c src[v,y,x,c] * W[j,c], so that a query of k projected
+ * channels (a PCA of the descriptors, a policy's 16..64-d head) reads a k-channel map instead of writing C-wide rows: fusion
+ * is linear in the channel vector, (sum_v s_v bilinear(map_v) - mean) W^T = sum_v s_v bilinear(map_v W^T) - mean W^T.
+ * src is read as stored (fp32, or fp16 widened exactly, explicit strides, texel stride >= C); W is [k,C] row-major fp32 on
+ * the device, dst a contiguous [V,fh,fw,k] fp32 buffer, 1 <= k <= D3F_MAX_PROJECTION, any C >= 1.  Dense
+ * multiply-accumulate over all C channels in a fixed order: fp32 products in short fp32 fmaf chains (4 or 16 channels), whose
+ * sums are added in float64 and rounded to fp32 once.  No term is skipped for a zero weight (a NaN texel makes its k outputs
+ * NaN), no atomics: two runs are bit-identical.  A source whose base pointer is not 16-byte aligned (8 for fp16) or whose
+ * strides are not multiples of 4 elements is read by scalar loads: correct, but well below the streaming rate.  Enqueued on
+ * `stream`, no host synchronisation. */
+#define D3F_MAX_PROJECTION 64
+int d3f_project_maps(const d3f_channel_map *src, int32_t V, const float *W, int32_t k, float *dst, void *stream);
 
 /* ---- library ---------------------------------------------------------------------- */
 int d3f_abi_version(void);
