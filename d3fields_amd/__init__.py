@@ -10,6 +10,7 @@ from .fusion import Fusion, create_init_grid, fps, instance2onehot, onehot2insta
 from . import corr_utils  # noqa: F401
 from . import mesh  # noqa: F401
 from .mesh import Mesh  # noqa: F401
+from . import pca  # noqa: F401
 from . import pcd_utils  # noqa: F401
 from . import rigid  # noqa: F401
 from . import sharding  # noqa: F401

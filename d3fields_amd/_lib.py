@@ -9,7 +9,7 @@ import os
 
 from . import build as _build
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 # status codes (include/d3fields_hip.h)
 OK = 0
@@ -29,6 +29,7 @@ TRACK_STALL_SENTINEL = 0x57A11ED
 MAX_VIEWS = 64
 MAX_MAPS = 8
 MAX_PROJECTION = 64
+MAX_MOMENT_CHANNELS = 2048
 KERNEL_NAME_MAX = 80
 GAUSSIAN_MAX_RADIUS = 64
 DTYPE_F32 = 0
@@ -83,6 +84,8 @@ SIGNATURES = {
     "d3f_map_check": (ctypes.c_int, [ctypes.POINTER(ChannelMap), _i32, _vp, _vp]),
     "d3f_map_check_many": (ctypes.c_int, [ctypes.POINTER(ChannelMap), ctypes.POINTER(_i32), _i32, ctypes.POINTER(_vp), _u32, _vp]),
     "d3f_project_maps": (ctypes.c_int, [ctypes.POINTER(ChannelMap), _i32, _vp, _i32, _vp, _vp]),
+    "d3f_row_moments_workspace_bytes": (_i64, [_i64, _i32]),
+    "d3f_row_moments": (ctypes.c_int, [_vp, _i32, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "d3f_eval_workspace_bytes": (_i64, [_i64]),
     "d3f_eval_dist_workspace_bytes": (_i64, [ctypes.POINTER(Views), _i64]),
     "d3f_eval_gate_offset": (_i64, [_i64]),

@@ -797,6 +797,30 @@ int d3f_project_maps(const d3f_channel_map *src, int32_t V, const float *W, int3
     return e == hipSuccess ? D3F_OK : hip_fail(e, "project_maps launch");
 }
 
+int64_t d3f_row_moments_workspace_bytes(int64_t M, int32_t C)
+{
+    if (M < 1 || C < 1 || C > D3F_MAX_MOMENT_CHANNELS) return 0;
+    return d3f::row_moments_workspace_bytes(M, C);
+}
+
+int d3f_row_moments(const void *rows, int32_t dtype, int64_t M, int32_t C, int64_t row_stride, const float *weights, double *wsum_out,
+                    double *mean_out, double *scatter_out, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (C < 1 || C > D3F_MAX_MOMENT_CHANNELS) return fail(D3F_ERR_BAD_SHAPE, "row_moments: C=%d outside [1,%d]", C, D3F_MAX_MOMENT_CHANNELS);
+    if (M < 1) return fail(D3F_ERR_BAD_SHAPE, "row_moments: M=%lld (at least one row)", (long long)M);
+    if (dtype != D3F_DTYPE_F32 && dtype != D3F_DTYPE_F16) return fail(D3F_ERR_BAD_DTYPE, "row_moments: dtype %d unsupported", dtype);
+    if (row_stride < C) return fail(D3F_ERR_BAD_LAYOUT, "row_moments: row_stride=%lld below C=%d", (long long)row_stride, C);
+    if (!rows || !wsum_out || !mean_out || !scatter_out) return fail(D3F_ERR_INVALID_ARG, "row_moments: NULL pointer");
+    if (!aligned(rows, dtype == D3F_DTYPE_F16 ? 2 : 4) || !aligned(weights, 4) || !aligned(wsum_out, 8) || !aligned(mean_out, 8) || !aligned(scatter_out, 8))
+        return fail(D3F_ERR_BAD_LAYOUT, "row_moments: pointers must be aligned to their element size");
+    const int64_t need = d3f::row_moments_workspace_bytes(M, C);
+    if (!workspace || workspace_bytes < need) return fail(D3F_ERR_WORKSPACE, "row_moments: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)need);
+    if (!aligned(workspace, 16)) return fail(D3F_ERR_BAD_LAYOUT, "row_moments: workspace must be 16-byte aligned");
+    hipError_t e = d3f::launch_row_moments(rows, dtype == D3F_DTYPE_F16, M, C, row_stride, weights, wsum_out, mean_out, scatter_out, workspace,
+                                           static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "row_moments launch");
+}
+
 int d3f_onehot2instance(const float *onehot, int64_t n, int32_t NI, uint8_t *out, void *stream)
 {
     if (n < 0 || NI < 1 || NI > 256) return fail(D3F_ERR_BAD_SHAPE, "onehot2instance: n=%lld NI=%d (NI must be in [1,256])", (long long)n, NI);

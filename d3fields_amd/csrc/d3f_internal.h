@@ -233,6 +233,11 @@ hipError_t launch_instance2onehot(const uint8_t *inst, int64_t n, int NI, uint8_
 hipError_t launch_project_maps(const void *data, int V, int fh, int fw, int C, int64_t sv, int64_t sy, int64_t sx, bool half, const float *W,
                                int k, float *dst, hipStream_t s);
 
+// moment_kernels.hip
+int64_t row_moments_workspace_bytes(int64_t M, int C);
+hipError_t launch_row_moments(const void *rows, bool half, int64_t M, int C, int64_t row_stride, const float *weights, double *wsum_out,
+                              double *mean_out, double *scatter_out, void *workspace, hipStream_t s);
+
 // corr_kernels.hip
 struct ColStat {   // running softmax statistics of one column (16 B)
     float m;       // max of -d*scale

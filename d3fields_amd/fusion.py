@@ -335,6 +335,26 @@ class Fusion:
         self._projections[name] = {"source": source, "k": k, "C": C, "W": torch.from_numpy(W), "b": torch.from_numpy(b), "dev": {}}
         self._projected.pop(name, None)
 
+    def fit_projection(self, name, source="dino_feats", n_components=3, weights=None, whiten=False):
+        """Fits a PCA on the texels of curr_obs_torch[source] where they live (pca.fit_pca: d3f_row_moments on the device, a
+        float64 eigen-problem of size C on the host) and registers it as add_projection(name, source, pca=fitted).  weights:
+        None or [V,fh,fw] (bool / uint8 / float >= 0), e.g. a foreground selection.  Returns the FittedPCA."""
+        from . import pca as _pca
+        if not isinstance(name, str) or not name:
+            raise ValueError("fit_projection: name must be a non-empty string")
+        if name in self.curr_obs_torch:
+            raise ValueError("fit_projection: %r is a key of curr_obs_torch; a projection needs a name of its own" % name)
+        if name.endswith("_inter") or name in ("dist", "valid_mask", "grid_shape"):
+            raise ValueError("fit_projection: %r would collide with an output key of eval" % name)
+        if not 1 <= int(n_components) <= _lib.MAX_PROJECTION:
+            raise ValueError("fit_projection: n_components=%s outside 1..%d" % (n_components, _lib.MAX_PROJECTION))
+        src = self.curr_obs_torch[source]               # KeyError for an unknown source, like any unknown name
+        if not isinstance(src, torch.Tensor) or src.dim() != 4:
+            raise ValueError("curr_obs_torch[%r] must be a (V,h,w,C) tensor" % source)
+        fitted = _pca.fit_pca(src, n_components=n_components, weights=weights, whiten=whiten)
+        self.add_projection(name, source, pca=fitted)
+        return fitted
+
     def remove_projection(self, name):
         del self._projections[name]
         self._projected.pop(name, None)

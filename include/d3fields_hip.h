@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define D3F_ABI_VERSION 9
+#define D3F_ABI_VERSION 10
 
 #define D3F_OK 0
 #define D3F_ERR_INVALID_ARG (-1)  /* null pointer, negative count, bad enum               */
@@ -151,6 +151,27 @@ int d3f_map_check_many(const d3f_channel_map *maps, const int32_t *views, int32_
  * `stream`, no host synchronisation. */
 #define D3F_MAX_PROJECTION 64
 int d3f_project_maps(const d3f_channel_map *src, int32_t V, const float *W, int32_t k, float *dst, void *stream);
+
+/* ABI 10.  Weighted moments of M rows of C channels, the device half of a PCA fit: with weights
+ * w_m >= 0 (NULL = all ones; [M] fp32 on the device),
+ *     wsum = sum_m w_m,   mean_c = sum_m w_m x_mc / wsum,   scatter_ij = sum_m w_m (x_mi - mean_i)(x_mj - mean_j),
+ * written as float64 on the device: wsum_out one double, mean_out [C], scatter_out [C,C] row-major with BOTH triangles.
+ * rows is fp32, or fp16 widened exactly; element (m,c) lives at rows[m*row_stride + c], row_stride >= C in ELEMENTS, so a
+ * contiguous channels-last map [V,fh,fw,C] is M = V*fh*fw rows and so are the [N,C] rows a query wrote.  1 <= C <=
+ * D3F_MAX_MOMENT_CHANNELS, M >= 1.  Arithmetic: column sums in fp32 fmaf chains of 32 rows folded in float64; the rows
+ * centred at fp32(mean) in fp32, products and chains of 64 rows on v_mfma_f32_16x16x4_f32 (exact fp32), chain sums folded in
+ * float64 in a fixed order, the shift from fp32(mean) to mean corrected exactly.  Dense: a row with w == 0 still takes part
+ * (0 * NaN = NaN, as in d3f_project_maps), a NaN or Inf in a row makes the affected outputs non-finite, wsum == 0 gives NaN
+ * means.  No atomics: two runs are bit-identical, and scatter is bitwise symmetric.  A base pointer that is not 16-byte
+ * aligned (8 for fp16) or a row_stride that is not a multiple of 4 elements is read by scalar loads: correct, but slow.
+ * workspace: d3f_row_moments_workspace_bytes(M, C) bytes on the device, 16-byte aligned (0 for arguments out of range);
+ * its contents need not be preserved.  Enqueued on `stream`, no host synchronisation. */
+#define D3F_MAX_MOMENT_CHANNELS 2048
+int64_t d3f_row_moments_workspace_bytes(int64_t M, int32_t C);
+int d3f_row_moments(const void *rows, int32_t dtype, int64_t M, int32_t C, int64_t row_stride,
+                    const float *weights /* NULL = all ones; [M], >= 0 */,
+                    double *wsum_out /* 1 */, double *mean_out /* [C] */, double *scatter_out /* [C,C] */,
+                    void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ---- library ---------------------------------------------------------------------- */
 int d3f_abi_version(void);
