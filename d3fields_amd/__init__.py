@@ -7,6 +7,8 @@ The compute lives in libd3fields_hip.so (hand-written HIP, C ABI in include/d3fi
 this package is the host-side mirror of the reference's Python interface.
 """
 from .fusion import Fusion, create_init_grid, fps, instance2onehot, onehot2instance  # noqa: F401
+from . import baked  # noqa: F401
+from .baked import BakedField  # noqa: F401
 from . import corr_utils  # noqa: F401
 from . import mesh  # noqa: F401
 from .mesh import Mesh  # noqa: F401

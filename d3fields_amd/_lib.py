@@ -9,7 +9,7 @@ import os
 
 from . import build as _build
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 # status codes (include/d3fields_hip.h)
 OK = 0
@@ -30,6 +30,7 @@ MAX_VIEWS = 64
 MAX_MAPS = 8
 MAX_PROJECTION = 64
 MAX_MOMENT_CHANNELS = 2048
+VOLUME_MAX_CHANNELS = 4096
 KERNEL_NAME_MAX = 80
 GAUSSIAN_MAX_RADIUS = 64
 DTYPE_F32 = 0
@@ -58,6 +59,17 @@ class ChannelMap(ctypes.Structure):
 class Grid(ctypes.Structure):
     """struct d3f_grid"""
     _fields_ = [("x", _vp), ("y", _vp), ("z", _vp), ("nx", _i32), ("ny", _i32), ("nz", _i32), ("reserved", _i32)]
+
+
+class Volume(ctypes.Structure):
+    """struct d3f_volume"""
+    _fields_ = [("nx", _i32), ("ny", _i32), ("nz", _i32), ("origin", _f32 * 3), ("step", _f32), ("reserved", _i32),
+                ("dist", _vp), ("valid", _vp), ("cell_valid", _vp)]
+
+
+class VolumeSet(ctypes.Structure):
+    """struct d3f_volume_set"""
+    _fields_ = [("data", _vp), ("C", _i32), ("reserved", _i32), ("stride_voxel", _i64), ("fill", _vp)]
 
 
 class TrackState(ctypes.Structure):
@@ -108,6 +120,10 @@ SIGNATURES = {
     "d3f_mesh_extract": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _f32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "d3f_volume_gaussian_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "d3f_volume_gaussian": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _f32, _f32, _vp, _i64, _vp]),
+    "d3f_volume_cell_valid": (ctypes.c_int, [ctypes.POINTER(Volume), _vp, _vp]),
+    "d3f_volume_sample": (ctypes.c_int, [ctypes.POINTER(Volume), _vp, _i64, ctypes.POINTER(VolumeSet), _i32, _vp, _vp, ctypes.POINTER(_vp), _vp]),
+    "d3f_volume_sample_backward": (ctypes.c_int, [ctypes.POINTER(Volume), _vp, _i64, ctypes.POINTER(VolumeSet), _i32, _vp, ctypes.POINTER(_vp),
+                                                  _vp, _vp]),
     "d3f_fps_workspace_bytes": (_i64, [_i64]),
     "d3f_fps_pixels_workspace_bytes": (_i64, [_i64]),
     "d3f_farthest_point_sampling": (ctypes.c_int, [_vp, _i64, _i32, _i64, _vp, _vp, _vp, _vp]),

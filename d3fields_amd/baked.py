@@ -1,0 +1,227 @@
+"""`BakedField` -- bake once, look up many times.
+
+`Fusion.bake(boundaries, step)` runs one grid query (`eval_grid`) and keeps its volume; `BakedField.eval(pts)` then reads that
+volume at arbitrary points by trilinear interpolation (d3f_volume_sample, csrc/volume_kernels.hip): eight corner rows of one
+array per point, no camera arithmetic, and a closed-form gradient w.r.t. the points (d3f_volume_sample_backward).  The lookup
+interpolates the FUSED field -- it does not re-fuse -- so off the lattice it is not `Fusion.eval`.
+
+There is no CPU path: volumes and points live on the ROCm device.
+"""
+import ctypes
+
+import torch
+
+from . import _lib
+
+__all__ = ["BakedField"]
+
+_RESERVED = ("dist", "valid_mask", "grid_shape")
+
+
+class _BakedQueryFn(torch.autograd.Function):
+    """BakedField.eval as an autograd node: forward = d3f_volume_sample, backward = d3f_volume_sample_backward."""
+
+    @staticmethod
+    def forward(ctx, pts, field, names):
+        pts_c = pts.detach().contiguous()
+        out = field._sample(pts_c, names)
+        ctx.field, ctx.names, ctx.pts = field, names, pts_c
+        ctx.mark_non_differentiable(out["valid_mask"])
+        return (out["dist"], out["valid_mask"]) + tuple(out[k] for k in names)
+
+    @staticmethod
+    def backward(ctx, grad_dist, _grad_valid, *grad_sets):
+        return ctx.field.backward(ctx.pts, grad_dist, dict(zip(ctx.names, grad_sets))), None, None
+
+
+class BakedField:
+    """A regular volume of the field and its trilinear lookup.
+
+    origin      (x0, y0, z0): the centre of voxel (0, 0, 0)
+    step        the lattice step h > 0
+    grid_shape  torch.Size([nx, ny, nz]), every extent >= 2, z fastest
+    dist        float32 [nx, ny, nz];  valid: bool [nx, ny, nz]
+    names()     the channel sets, each float32 [nx, ny, nz, C]
+
+    It holds tensors only -- no reference to the Fusion that made it -- and stays valid after Fusion.update()."""
+
+    def __init__(self, origin, step, dist, valid, sets, fills, boundaries=None):
+        self.origin = tuple(float(o) for o in origin)
+        self.step = float(step)
+        self.grid_shape = torch.Size(dist.shape)
+        self.dist, self.valid = dist, valid
+        self._sets, self._fills = dict(sets), dict(fills)
+        nx, ny, nz = self.grid_shape
+        if boundaries is None:
+            lo = [o - self.step / 2 for o in self.origin]
+            boundaries = {"x_lower": lo[0], "x_upper": lo[0] + nx * self.step, "y_lower": lo[1], "y_upper": lo[1] + ny * self.step,
+                          "z_lower": lo[2], "z_upper": lo[2] + nz * self.step}
+        self.boundaries = dict(boundaries)
+        self.device = dist.device
+        self._lib = _lib.load()
+        self.cell_valid = torch.empty((nx - 1, ny - 1, nz - 1), dtype=torch.uint8, device=self.device)
+        vol = self._volume()
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.d3f_volume_cell_valid(ctypes.byref(vol), _lib.ptr(self.cell_valid), _lib.current_stream_handle(self.device)))
+
+    # ---- construction ---------------------------------------------------------------------------------------------------------
+    @classmethod
+    def from_arrays(cls, origin, step, dist, valid=None, fills=None, **named):
+        """A field from volumes made elsewhere (a Gaussian-smoothed `dist`, ...): dist [nx,ny,nz] float32, valid None (every
+        voxel) or bool / uint8 of the same shape, named sets [nx,ny,nz,C] float32, all on one ROCm device; fills: None or
+        {name: [C] row a point outside the valid cells gets} (default zeros).  Tensors are used in place where they are
+        contiguous float32 / bool."""
+        origin = tuple(float(o) for o in origin)
+        if len(origin) != 3:
+            raise ValueError("from_arrays: origin must hold three coordinates")
+        if not float(step) > 0.0:
+            raise ValueError("from_arrays: step must be > 0, got %r" % (step,))
+        if not isinstance(dist, torch.Tensor) or dist.dim() != 3 or min(dist.shape) < 2:
+            raise ValueError("from_arrays: dist must be a [nx,ny,nz] tensor with every extent >= 2")
+        shape = tuple(dist.shape)
+        if valid is not None and (not isinstance(valid, torch.Tensor) or tuple(valid.shape) != shape):
+            raise ValueError("from_arrays: valid must have dist's shape %s" % (shape,))
+        fills = dict(fills or {})
+        for k, t in named.items():
+            if k in _RESERVED:
+                raise ValueError("from_arrays: %r is an output key of eval" % k)
+            if not isinstance(t, torch.Tensor) or t.dim() != 4 or tuple(t.shape[:3]) != shape:
+                raise ValueError("from_arrays: set %r must be [nx,ny,nz,C] with dist's grid %s, got %s" % (k, shape, tuple(getattr(t, "shape", ()))))
+            if not 1 <= t.shape[3] <= _lib.VOLUME_MAX_CHANNELS:
+                raise ValueError("from_arrays: set %r has %d channels, outside 1..%d" % (k, t.shape[3], _lib.VOLUME_MAX_CHANNELS))
+            if fills.get(k) is not None and tuple(fills[k].shape) != (t.shape[3],):
+                raise ValueError("from_arrays: fill of %r must be [%d]" % (k, t.shape[3]))
+        unknown = [k for k in fills if k not in named]
+        if unknown:
+            raise ValueError("from_arrays: fills name unknown sets %s" % unknown)
+        if len(named) > _lib.MAX_MAPS:
+            raise ValueError("from_arrays: at most %d sets" % _lib.MAX_MAPS)
+        if shape[0] * shape[1] * shape[2] > 2 ** 31 - 1:
+            raise ValueError("from_arrays: more than 2^31 - 1 voxels")
+        if not dist.is_cuda:
+            raise RuntimeError("BakedField: the volume must live on the ROCm device; there is no CPU path")
+        dev = dist.device
+        for k, t in list(named.items()) + [("valid", valid)] + [("fill of " + k, f) for k, f in fills.items()]:
+            if t is not None and t.device != dev:
+                raise RuntimeError("BakedField: %s is on %s, dist on %s" % (k, t.device, dev))
+        dist = dist.detach().to(torch.float32).contiguous()
+        valid = torch.ones(shape, dtype=torch.bool, device=dev) if valid is None else (valid.detach() != 0).contiguous()
+        sets = {k: t.detach().to(torch.float32).contiguous() for k, t in named.items()}
+        fills = {k: (None if fills.get(k) is None else fills[k].detach().to(torch.float32).contiguous()) for k in sets}
+        return cls(origin, step, dist, valid, sets, fills)
+
+    @classmethod
+    def from_fusion(cls, fusion, boundaries, step_size, return_names=()):
+        """Fusion.bake: one eval_grid, its tensors viewed (not copied) as the volume; a projected name's fill row is -b, what
+        Fusion.eval returns for an all-invalid point."""
+        from .fusion import _grid_axes
+        names = list(return_names)
+        with torch.no_grad():
+            res = fusion.eval_grid(boundaries, step_size, return_names=names)
+        nx, ny, nz = res["grid_shape"]
+        if min(nx, ny, nz) < 2:
+            raise ValueError("bake: the grid %s needs at least two voxels along every axis" % ((nx, ny, nz),))
+        origin = [float(a[0]) for a in _grid_axes(boundaries, step_size)]
+        step = float(torch.tensor(step_size, dtype=torch.float32))
+        dev = res["dist"].device
+        sets = {k: res[k].view(nx, ny, nz, -1) for k in names}
+        fills = {k: (-fusion._head_on(k, dev)[1]).contiguous() if k in fusion._projections else None for k in names}
+        return cls(origin, step, res["dist"].view(nx, ny, nz), res["valid_mask"].view(nx, ny, nz), sets, fills, boundaries=boundaries)
+
+    # ---- description ----------------------------------------------------------------------------------------------------------
+    def names(self):
+        return list(self._sets)
+
+    def fill_row(self, name):
+        """[C] row of `name` at a point that is not valid"""
+        f = self._fills[name]
+        return torch.zeros(self._sets[name].shape[3], dtype=torch.float32, device=self.device) if f is None else f
+
+    def _volume(self):
+        nx, ny, nz = self.grid_shape
+        return _lib.Volume(nx, ny, nz, (ctypes.c_float * 3)(*self.origin), self.step, 0, _lib.ptr(self.dist), _lib.ptr(self.valid),
+                           _lib.ptr(self.cell_valid))
+
+    def _set_array(self, names):
+        arr = (_lib.VolumeSet * max(len(names), 1))()
+        for s, k in enumerate(names):
+            t = self._sets[k]
+            arr[s] = _lib.VolumeSet(t.data_ptr(), t.shape[3], 0, t.stride(2), _lib.ptr(self._fills[k]))
+        return arr
+
+    def _check_query(self, pts):
+        assert type(pts) == torch.Tensor
+        assert len(pts.shape) == 2
+        assert pts.shape[1] == 3
+        if not pts.is_cuda or pts.device != self.device:
+            raise RuntimeError("BakedField.eval: pts must be on %s (where the volume lives); there is no CPU path" % self.device)
+        if pts.dtype != torch.float32:
+            raise TypeError("BakedField.eval: pts must be float32, got %s" % pts.dtype)
+
+    def _names(self, return_names):
+        names = self.names() if return_names is None else list(return_names)
+        for k in names:
+            if k not in self._sets:
+                raise KeyError("%r was not baked; this field holds %s" % (k, self.names()))
+        if len(names) > _lib.MAX_MAPS:
+            raise ValueError("at most %d names per lookup" % _lib.MAX_MAPS)
+        return names
+
+    # ---- the lookup -----------------------------------------------------------------------------------------------------------
+    def _sample(self, pts_c, names):
+        dev, n = self.device, pts_c.shape[0]
+        out = {"dist": torch.empty(n, dtype=torch.float32, device=dev), "valid_mask": torch.empty(n, dtype=torch.bool, device=dev)}
+        outs = (ctypes.c_void_p * max(len(names), 1))()
+        for s, k in enumerate(names):
+            out[k] = torch.empty((n, self._sets[k].shape[3]), dtype=torch.float32, device=dev)
+            outs[s] = out[k].data_ptr()
+        vol = self._volume()
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.d3f_volume_sample(ctypes.byref(vol), _lib.ptr(pts_c), n, self._set_array(names), len(names), _lib.ptr(out["dist"]),
+                                                   _lib.ptr(out["valid_mask"]), outs, _lib.current_stream_handle(dev)))
+        return out
+
+    def backward(self, pts, grad_dist=None, grad_sets=None):
+        """grad_pts [N,3] = d(sum grad_dist * dist + sum over names of grad * row) / d pts (d3f_volume_sample_backward);
+        grad_sets: {name: [N,C] or None}."""
+        self._check_query(pts)
+        pts_c = pts.detach().contiguous()
+        dev, n = self.device, pts_c.shape[0]
+        grad_sets = {k: g for k, g in (grad_sets or {}).items() if g is not None}
+        names = self._names(list(grad_sets))
+        grads = (ctypes.c_void_p * max(len(names), 1))()
+        hold = []
+        for s, k in enumerate(names):
+            g = grad_sets[k].detach().to(torch.float32).contiguous()
+            if tuple(g.shape) != (n, self._sets[k].shape[3]) or g.device != dev:
+                raise ValueError("backward: the gradient of %r must be [%d,%d] on %s" % (k, n, self._sets[k].shape[3], dev))
+            hold.append(g)
+            grads[s] = g.data_ptr()
+        gd = None
+        if grad_dist is not None:
+            gd = grad_dist.detach().to(torch.float32).contiguous()
+            if tuple(gd.shape) != (n,) or gd.device != dev:
+                raise ValueError("backward: grad_dist must be [%d] on %s" % (n, dev))
+        grad_pts = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        vol = self._volume()
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.d3f_volume_sample_backward(ctypes.byref(vol), _lib.ptr(pts_c), n, self._set_array(names), len(names), _lib.ptr(gd),
+                                                            grads, _lib.ptr(grad_pts), _lib.current_stream_handle(dev)))
+        return grad_pts
+
+    def eval(self, pts, return_names=None):
+        """The dict of Fusion.eval -- 'dist' [N], 'valid_mask' [N] bool, one [N,C] float32 per name (None: every baked name) --
+        interpolated in the volume.  Not valid (outside, a NaN coordinate, a cell with an invalid corner): dist 1e3, the fill row."""
+        self._check_query(pts)
+        names = self._names(return_names)
+        if pts.requires_grad and torch.is_grad_enabled():
+            res = _BakedQueryFn.apply(pts, self, tuple(names))
+            out = {"dist": res[0], "valid_mask": res[1]}
+            out.update(zip(names, res[2:]))
+            return out
+        return self._sample(pts.detach().contiguous(), names)
+
+    batch_eval = eval
+
+    def eval_dist(self, pts):
+        return self.eval(pts, return_names=[])

@@ -621,6 +621,110 @@ int d3f_volume_gaussian(const float *src, float *dst, int32_t nx, int32_t ny, in
     return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_gaussian launch");
 }
 
+// ---- trilinear lookups in a baked volume (volume_kernels.hip) ----
+static int check_volume(const char *who, const d3f_volume *vol)
+{
+    if (!vol) return fail(D3F_ERR_INVALID_ARG, "%s: vol is NULL", who);
+    if (vol->nx < 2 || vol->ny < 2 || vol->nz < 2 || vol->nx > (1 << 24) || vol->ny > (1 << 24) || vol->nz > (1 << 24))
+        return fail(D3F_ERR_BAD_SHAPE, "%s: vol nx=%d ny=%d nz=%d, every extent must be in [2, 2^24]", who, vol->nx, vol->ny, vol->nz);
+    if ((int64_t)vol->nx * vol->ny * vol->nz > 0x7fffffffLL)
+        return fail(D3F_ERR_BAD_SHAPE, "%s: vol holds %lld voxels, more than 2^31 - 1", who, (long long)vol->nx * vol->ny * vol->nz);
+    return D3F_OK;
+}
+
+int d3f_volume_cell_valid(const d3f_volume *vol, uint8_t *cell_valid_out, void *stream)
+{
+    const int rc = check_volume("volume_cell_valid", vol);
+    if (rc != D3F_OK) return rc;
+    if (!vol->valid || !cell_valid_out) return fail(D3F_ERR_INVALID_ARG, "volume_cell_valid: vol->valid / cell_valid_out must be non-NULL");
+    hipError_t e = d3f::launch_volume_cell_valid(vol->valid, cell_valid_out, vol->nx, vol->ny, vol->nz, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_cell_valid launch");
+}
+
+// the checks the forward and the backward lookup share; fills P but for the outputs / gradients.  Returns 1 for "nothing to do".
+static int volume_common(const char *who, const d3f_volume *vol, const float *pts, int64_t n, const d3f_volume_set *sets, int32_t n_sets,
+                         d3f::VolParams &P)
+{
+    int rc = check_volume(who, vol);
+    if (rc != D3F_OK) return rc;
+    if (!(vol->step > 0.0f) || vol->step * 0.0f != 0.0f) return fail(D3F_ERR_INVALID_ARG, "%s: vol->step must be > 0 and finite", who);
+    if (n < 0) return fail(D3F_ERR_INVALID_ARG, "%s: n=%lld is negative", who, (long long)n);
+    if (n_sets < 0 || n_sets > D3F_MAX_MAPS) return fail(D3F_ERR_BAD_SHAPE, "%s: n_sets=%d outside [0,%d]", who, n_sets, D3F_MAX_MAPS);
+    if (n_sets > 0 && !sets) return fail(D3F_ERR_INVALID_ARG, "%s: sets is NULL with n_sets=%d", who, n_sets);
+    for (int s = 0; s < n_sets; ++s)
+        if (sets[s].C < 1 || sets[s].C > D3F_VOLUME_MAX_CHANNELS)
+            return fail(D3F_ERR_BAD_SHAPE, "%s: set %d: C=%d outside [1,%d]", who, s, sets[s].C, D3F_VOLUME_MAX_CHANNELS);
+    if (n == 0) return 1;
+    if (!vol->dist || !vol->cell_valid || !pts) return fail(D3F_ERR_INVALID_ARG, "%s: vol->dist / vol->cell_valid / pts must be non-NULL", who);
+    if (!aligned(vol->dist, 4) || !aligned(pts, 4)) return fail(D3F_ERR_BAD_LAYOUT, "%s: vol->dist / pts must be 4-byte aligned", who);
+    for (int s = 0; s < n_sets; ++s) {
+        if (!sets[s].data) return fail(D3F_ERR_INVALID_ARG, "%s: set %d: data is NULL", who, s);
+        if (sets[s].stride_voxel < sets[s].C) return fail(D3F_ERR_BAD_LAYOUT, "%s: set %d: stride_voxel=%lld < C=%d", who, s, (long long)sets[s].stride_voxel, sets[s].C);
+        if (!aligned(sets[s].data, 4) || !aligned(sets[s].fill, 4)) return fail(D3F_ERR_BAD_LAYOUT, "%s: set %d: data / fill must be 4-byte aligned", who, s);
+        d3f::VolSet &S = P.sets[s];
+        S.data = sets[s].data;
+        S.fill = sets[s].fill;
+        S.out = nullptr;
+        S.grad = nullptr;
+        S.stride = sets[s].stride_voxel;
+        S.C = sets[s].C;
+        S.vec = (S.C % 4 == 0 && S.stride % 4 == 0 && aligned(S.data, 16)) ? 1 : 0;      // and-ed with the alignment of out / grad by the caller
+    }
+    P.dist = vol->dist;
+    P.cell = vol->cell_valid;
+    P.pts = pts;
+    P.out_dist = nullptr;
+    P.out_valid = nullptr;
+    P.grad_dist = nullptr;
+    P.grad_pts = nullptr;
+    P.n = n;
+    P.nx = vol->nx; P.ny = vol->ny; P.nz = vol->nz;
+    P.ox = vol->origin[0]; P.oy = vol->origin[1]; P.oz = vol->origin[2];
+    P.h = vol->step;
+    P.rh = 1.0f / vol->step;
+    P.n_sets = n_sets;
+    return D3F_OK;
+}
+
+int d3f_volume_sample(const d3f_volume *vol, const float *pts, int64_t n, const d3f_volume_set *sets, int32_t n_sets, float *out_dist,
+                      uint8_t *out_valid, void *const *out_sets, void *stream)
+{
+    d3f::VolParams P;
+    const int rc = volume_common("volume_sample", vol, pts, n, sets, n_sets, P);
+    if (rc != D3F_OK) return rc == 1 ? D3F_OK : rc;
+    if (!out_dist || !out_valid || (n_sets > 0 && !out_sets)) return fail(D3F_ERR_INVALID_ARG, "volume_sample: out_dist / out_valid / out_sets must be non-NULL");
+    if (!aligned(out_dist, 4)) return fail(D3F_ERR_BAD_LAYOUT, "volume_sample: out_dist must be 4-byte aligned");
+    for (int s = 0; s < n_sets; ++s) {
+        if (!out_sets[s]) return fail(D3F_ERR_INVALID_ARG, "volume_sample: out_sets[%d] is NULL", s);
+        if (!aligned(out_sets[s], 4)) return fail(D3F_ERR_BAD_LAYOUT, "volume_sample: out_sets[%d] must be 4-byte aligned", s);
+        P.sets[s].out = static_cast<float *>(out_sets[s]);
+        if (!aligned(out_sets[s], 16)) P.sets[s].vec = 0;
+    }
+    P.out_dist = out_dist;
+    P.out_valid = out_valid;
+    hipError_t e = d3f::launch_volume_sample(P, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_sample launch");
+}
+
+int d3f_volume_sample_backward(const d3f_volume *vol, const float *pts, int64_t n, const d3f_volume_set *sets, int32_t n_sets,
+                               const float *grad_dist, const void *const *grad_sets, float *grad_pts, void *stream)
+{
+    d3f::VolParams P;
+    const int rc = volume_common("volume_sample_backward", vol, pts, n, sets, n_sets, P);
+    if (rc != D3F_OK) return rc == 1 ? D3F_OK : rc;
+    if (!grad_pts) return fail(D3F_ERR_INVALID_ARG, "volume_sample_backward: grad_pts is NULL");
+    if (!aligned(grad_pts, 4) || !aligned(grad_dist, 4)) return fail(D3F_ERR_BAD_LAYOUT, "volume_sample_backward: grad_pts / grad_dist must be 4-byte aligned");
+    for (int s = 0; s < n_sets && grad_sets; ++s) {
+        if (!aligned(grad_sets[s], 4)) return fail(D3F_ERR_BAD_LAYOUT, "volume_sample_backward: grad_sets[%d] must be 4-byte aligned", s);
+        P.sets[s].grad = static_cast<const float *>(grad_sets[s]);
+        if (!aligned(grad_sets[s], 16)) P.sets[s].vec = 0;
+    }
+    P.grad_dist = grad_dist;
+    P.grad_pts = grad_pts;
+    hipError_t e = d3f::launch_volume_backward(P, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_sample_backward launch");
+}
+
 int64_t d3f_fps_workspace_bytes(int64_t n) { return n > 0 ? d3f::fps_workspace_bytes(n, 4) : 0; }
 int64_t d3f_fps_pixels_workspace_bytes(int64_t n) { return n > 0 ? d3f::fps_workspace_bytes(n, 8) : 0; }
 

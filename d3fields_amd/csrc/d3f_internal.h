@@ -196,6 +196,35 @@ constexpr int kGaussMaxRadius = D3F_GAUSSIAN_MAX_RADIUS;
 hipError_t launch_volume_gaussian(const float *src, float *dst, int nx, int ny, int nz, const float *weights, int radius, float *tmp,
                                   hipStream_t s);
 
+// volume_kernels.hip: trilinear lookups in a baked volume
+constexpr int kVolNarrowMax = 16;           // channels of a set sampled one lane per point; a wider set takes sixteen lanes per point
+struct VolSet {
+    const float *data;       // row of voxel q: data + q * stride
+    const float *fill;       // C floats or nullptr (zeros): the row of a point that is not valid
+    float *out;              // forward: [n, C]
+    const float *grad;       // backward: [n, C] or nullptr
+    int64_t stride;
+    int32_t C;
+    int32_t vec;             // 1: rows (and out / grad rows) move as 16-byte vectors
+};
+struct VolParams {
+    const float *dist;
+    const uint8_t *cell;     // [nx-1, ny-1, nz-1]
+    const float *pts;
+    float *out_dist;         // forward
+    uint8_t *out_valid;
+    const float *grad_dist;  // backward: [n] or nullptr
+    float *grad_pts;         // backward: [n, 3]
+    int64_t n;
+    int32_t nx, ny, nz;
+    float ox, oy, oz, h, rh; // rh = 1 / h
+    int32_t n_sets;
+    VolSet sets[D3F_MAX_MAPS];
+};
+hipError_t launch_volume_cell_valid(const uint8_t *valid, uint8_t *cell, int nx, int ny, int nz, hipStream_t s);
+hipError_t launch_volume_sample(const VolParams &P, hipStream_t s);
+hipError_t launch_volume_backward(const VolParams &P, hipStream_t s);
+
 // pcd_kernels.hip
 hipError_t launch_backproject(const double *depth, const uint8_t *mask, int H, int W, const double *cam, const double *T,
                               const double *bounds, int64_t capacity, double *out_pts, int32_t *out_pixel, int64_t *count,

@@ -943,6 +943,13 @@ class Fusion:
             self._subtract_offsets(out, names, dev)
         return out
 
+    def bake(self, boundaries, step_size, return_names=[]):
+        """eval_grid(boundaries, step_size, return_names) kept as a baked.BakedField: its eval(pts) interpolates that volume
+        trilinearly (eight corner rows per point, no projection into the views) and has a closed-form gradient w.r.t. pts.
+        The field holds the grid query's tensors and no reference to this object: it keeps answering, unchanged, after update()."""
+        from .baked import BakedField
+        return BakedField.from_fusion(self, boundaries, step_size, return_names)
+
     def grid_shell(self, boundaries, step_size, dist_threshold=0.005):
         """Flat indices (ascending) and coordinates of the grid points with valid_mask & |dist| < dist_threshold:
         the pre-filter of select_features_* (fusion.py:1430,1444) fused into the grid pass, so that no

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define D3F_ABI_VERSION 10
+#define D3F_ABI_VERSION 11
 
 #define D3F_OK 0
 #define D3F_ERR_INVALID_ARG (-1)  /* null pointer, negative count, bad enum               */
@@ -352,6 +352,58 @@ int d3f_mesh_extract(const float *volume, const uint8_t *valid, int32_t nx, int3
 int64_t d3f_volume_gaussian_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
 int d3f_volume_gaussian(const float *src, float *dst, int32_t nx, int32_t ny, int32_t nz, float sigma, float truncate,
                         void *workspace, int64_t workspace_bytes, void *stream);
+
+/* (ABI 11) A BAKED field: the regular volume d3f_eval_grid wrote (dist, valid and any channel set, flat index (ix*ny + iy)*nz + iz,
+ * z fastest), read back at arbitrary points by trilinear interpolation -- eight corner rows of one array per point and no camera
+ * arithmetic -- with the closed-form gradient w.r.t. the point.  It interpolates the FUSED field; it does
+ * not re-fuse, so off the lattice it is not d3f_eval.
+ *   origin  centre of voxel (0,0,0); step h > 0; every extent in [2, 2^24] (lattice coordinates are exact in fp32) and
+ *           nx*ny*nz <= 2^31 - 1, else D3F_ERR_BAD_SHAPE;
+ *   dist    float32 [nx,ny,nz]; valid: one byte per voxel (read by d3f_volume_cell_valid only);
+ *   cell_valid  one byte per CELL, [nx-1,ny-1,nz-1]: the AND of the cell's eight valid bytes, written once per volume by
+ *           d3f_volume_cell_valid (the samplers read this array and never `valid`).
+ * Per point p, everything in fp32:
+ *   g_a = (p_a - origin_a) / h (IEEE division);  inside = 0 <= g_a <= n_a - 1 for x, y, z (a NaN coordinate is not inside);
+ *   i_a = min(floor(g_a), n_a - 2), t_a = g_a - i_a in [0,1] (the far face belongs to the last cell, t = 1);
+ *   valid = inside && cell_valid[i_x,i_y,i_z] -- a cell with ONE invalid corner is rejected as a whole, also at t = 0;
+ *   w(dx,dy,dz) = (dx ? t_x : 1-t_x) * (dy ? t_y : 1-t_y) * (dz ? t_z : 1-t_z), products left to right;
+ *   out = w0*v0, then out = fma(w_c, v_c, out) over the corners (dx,dy,dz) = (0,0,1), (0,1,0), (0,1,1), (1,0,0) ... (1,1,1);
+ * the same chain for dist and for every channel of every set.  Where valid is false NO corner is read (invalid voxels may hold
+ * NaN): dist = 1e3 (d3f_eval's sentinel) and a set's row is its `fill` row (NULL: zeros).  At a lattice point of a valid cell the
+ * weights are exactly 1 and 0 and the result equals the stored value.
+ * A set: rows of C floats (1 <= C <= D3F_VOLUME_MAX_CHANNELS), voxel q at data + q*stride_voxel (stride_voxel >= C, in floats).
+ * Rows move as 16-byte vectors where C % 4 == 0, stride_voxel % 4 == 0 and data / the output are 16-byte aligned, as scalars
+ * otherwise; a set of up to 16 channels is sampled one lane per point, a wider one sixteen lanes per point. */
+#define D3F_VOLUME_MAX_CHANNELS 4096
+typedef struct d3f_volume {
+    int32_t nx, ny, nz;
+    float origin[3];
+    float step;
+    int32_t reserved;          /* 0 */
+    const float *dist;
+    const uint8_t *valid;
+    const uint8_t *cell_valid;
+} d3f_volume;
+typedef struct d3f_volume_set {
+    const float *data;
+    int32_t C;
+    int32_t reserved;          /* 0 */
+    int64_t stride_voxel;
+    const float *fill;         /* C floats on the device, or NULL = zeros */
+} d3f_volume_set;
+/* cell_valid_out[(cx*(ny-1) + cy)*(nz-1) + cz] = AND of vol->valid over the cell's eight corners (vol->dist / cell_valid unused) */
+int d3f_volume_cell_valid(const d3f_volume *vol, uint8_t *cell_valid_out, void *stream);
+/* pts [n,3]; out_dist [n], out_valid [n] bytes, out_sets[s] = float32 [n, sets[s].C] (C-contiguous).  n_sets in [0, D3F_MAX_MAPS].
+ * n == 0: D3F_OK, nothing is read (buffers may be NULL).  One launch (narrow sets only) or one launch that also walks the wide
+ * sets; no allocation, no synchronisation. */
+int d3f_volume_sample(const d3f_volume *vol, const float *pts, int64_t n, const d3f_volume_set *sets, int32_t n_sets, float *out_dist,
+                      uint8_t *out_valid, void *const *out_sets, void *stream);
+/* grad_pts[n,a] = (1/h) * sum over dist and the sets of grad * sum_c (dw_c/dt_a) v_c: the analytic derivative of the chain
+ * above for the cell the point lies in (no term for the choice of the cell); a zero row where valid is false.  grad_dist: [n] or
+ * NULL; grad_sets: NULL, or n_sets pointers to float32 [n, C] (entries may be NULL).  Every row of grad_pts is written by one
+ * lane: no atomics, two runs agree bit for bit. */
+int d3f_volume_sample_backward(const d3f_volume *vol, const float *pts, int64_t n, const d3f_volume_set *sets, int32_t n_sets,
+                               const float *grad_dist, const void *const *grad_sets, float *grad_pts, void *stream);
 
 /* fps_np (utils/my_utils.py:478-497): k samples of pts[n,3] starting from init_idx, float32 Euclidean distances,
  * first maximum wins -> out_idx[k] (int64, device), out_maxdist (device float, may be NULL).  k may exceed n: like
