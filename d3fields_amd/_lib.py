@@ -9,7 +9,7 @@ import os
 
 from . import build as _build
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 # status codes (include/d3fields_hip.h)
 OK = 0
@@ -31,6 +31,7 @@ MAX_MAPS = 8
 MAX_PROJECTION = 64
 MAX_MOMENT_CHANNELS = 2048
 VOLUME_MAX_CHANNELS = 4096
+RAYCAST_MAX_STEPS = 65536
 KERNEL_NAME_MAX = 80
 GAUSSIAN_MAX_RADIUS = 64
 DTYPE_F32 = 0
@@ -70,6 +71,11 @@ class Volume(ctypes.Structure):
 class VolumeSet(ctypes.Structure):
     """struct d3f_volume_set"""
     _fields_ = [("data", _vp), ("C", _i32), ("reserved", _i32), ("stride_voxel", _i64), ("fill", _vp)]
+
+
+class Pinhole(ctypes.Structure):
+    """struct d3f_pinhole (host memory)"""
+    _fields_ = [("K", _f32 * 9), ("pose", _f32 * 12), ("H", _i32), ("W", _i32)]
 
 
 class TrackState(ctypes.Structure):
@@ -124,6 +130,7 @@ SIGNATURES = {
     "d3f_volume_sample": (ctypes.c_int, [ctypes.POINTER(Volume), _vp, _i64, ctypes.POINTER(VolumeSet), _i32, _vp, _vp, ctypes.POINTER(_vp), _vp]),
     "d3f_volume_sample_backward": (ctypes.c_int, [ctypes.POINTER(Volume), _vp, _i64, ctypes.POINTER(VolumeSet), _i32, _vp, ctypes.POINTER(_vp),
                                                   _vp, _vp]),
+    "d3f_volume_raycast": (ctypes.c_int, [ctypes.POINTER(Volume), _vp, _vp, _i64, ctypes.POINTER(Pinhole), _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp]),
     "d3f_fps_workspace_bytes": (_i64, [_i64]),
     "d3f_fps_pixels_workspace_bytes": (_i64, [_i64]),
     "d3f_farthest_point_sampling": (ctypes.c_int, [_vp, _i64, _i32, _i64, _vp, _vp, _vp, _vp]),

@@ -5,9 +5,13 @@ volume at arbitrary points by trilinear interpolation (d3f_volume_sample, csrc/v
 array per point, no camera arithmetic, and a closed-form gradient w.r.t. the points (d3f_volume_sample_backward).  The lookup
 interpolates the FUSED field -- it does not re-fuse -- so off the lattice it is not `Fusion.eval`.
 
+`BakedField.raycast(origins, dirs)` and `BakedField.render(K, pose, H, W)` march rays through `dist` to the first surface they
+meet (d3f_volume_raycast, csrc/raycast_kernels.hip) and read rows and normals at the hit points with the lookup above.
+
 There is no CPU path: volumes and points live on the ROCm device.
 """
 import ctypes
+import math
 
 import torch
 
@@ -16,6 +20,7 @@ from . import _lib
 __all__ = ["BakedField"]
 
 _RESERVED = ("dist", "valid_mask", "grid_shape")
+_RAY_KEYS = ("t", "depth", "hit_mask", "points", "normal")      # output keys of raycast / render: a set of that name cannot be asked for there
 
 
 class _BakedQueryFn(torch.autograd.Function):
@@ -225,3 +230,90 @@ class BakedField:
 
     def eval_dist(self, pts):
         return self.eval(pts, return_names=[])
+
+    # ---- rays -----------------------------------------------------------------------------------------------------------------
+    def _check_rays(self, origins, dirs):
+        for who, t in (("origins", origins), ("dirs", dirs)):
+            assert type(t) == torch.Tensor
+            assert len(t.shape) == 2
+            assert t.shape[1] == 3
+            if not t.is_cuda or t.device != self.device:
+                raise RuntimeError("BakedField.raycast: %s must be on %s (where the volume lives); there is no CPU path" % (who, self.device))
+            if t.dtype != torch.float32:
+                raise TypeError("BakedField.raycast: %s must be float32, got %s" % (who, t.dtype))
+        if origins.shape[0] != dirs.shape[0]:
+            raise ValueError("BakedField.raycast: %d origins but %d dirs" % (origins.shape[0], dirs.shape[0]))
+
+    def _ray_names(self, return_names):
+        names = self._names(list(return_names))
+        clash = [k for k in names if k in _RAY_KEYS]
+        if clash:
+            raise ValueError("raycast / render: the set(s) %s carry the name of an output key %s; read them with eval(out['points'])" % (clash, _RAY_KEYS))
+        return names
+
+    def _march(self, origins, dirs, camera, n, march_step, t_near, t_far, samples=False):
+        """one d3f_volume_raycast launch: (t [n], hit [n] bool, points [n,3], samples [n] int32 or None)"""
+        dev = self.device
+        step = self.step if march_step is None else float(march_step)
+        t = torch.empty(n, dtype=torch.float32, device=dev)
+        hit = torch.empty(n, dtype=torch.bool, device=dev)
+        pts = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        cnt = torch.empty(n, dtype=torch.int32, device=dev) if samples else None
+        vol = self._volume()
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.d3f_volume_raycast(ctypes.byref(vol), _lib.ptr(origins), _lib.ptr(dirs), n, None if camera is None else ctypes.byref(camera),
+                                                    step, float(t_near), float(t_far), _lib.ptr(t), _lib.ptr(hit), _lib.ptr(pts), _lib.ptr(cnt),
+                                                    _lib.current_stream_handle(dev)))
+        return t, hit, pts, cnt
+
+    def _at_hits(self, out, pts, names, normals):
+        """rows and normals at the marched points through the lookup: a miss's NaN row is "not valid" there, so it gets the fill
+        rows and a zero gradient"""
+        if normals:
+            grad = self.backward(pts, torch.ones(pts.shape[0], dtype=torch.float32, device=self.device))
+            length = torch.linalg.vector_norm(grad, dim=1, keepdim=True)
+            out["normal"] = torch.where(length > 0, grad / length, torch.zeros_like(grad))
+        if names:
+            rows = self._sample(pts, names)
+            for k in names:
+                out[k] = rows[k]
+        return out
+
+    def raycast(self, origins, dirs, return_names=(), march_step=None, t_near=0.0, t_far=math.inf, normals=False):
+        """The first surface each ray o + t d meets (d need not be unit): a march through `dist` in steps of `march_step` (a world
+        length, default the lattice step) inside [t_near, t_far] and the volume, stopped at the first + to - crossing between two
+        samples of valid cells and interpolated linearly there; holes are never bridged, back faces are no hits.
+
+        -> {'t' [N] (0 for a miss), 'hit_mask' [N] bool, 'points' [N,3] (NaN rows for a miss), 'normal' [N,3] if `normals`
+        (grad dist / |grad dist|, pointing into free space; zero for a miss or a zero gradient), name: [N,C] for every name}.
+        Rows and normals are BakedField.eval / backward at 'points': a miss gets the fill row, and so does a hit whose own cell
+        holds an invalid corner.  There is no autograd through the march: outputs never require grad."""
+        self._check_rays(origins, dirs)
+        names = self._ray_names(return_names)
+        n = origins.shape[0]
+        t, hit, pts, _ = self._march(origins.detach().contiguous(), dirs.detach().contiguous(), None, n, march_step, t_near, t_far)
+        return self._at_hits({"t": t, "hit_mask": hit, "points": pts}, pts, names, normals)
+
+    def _camera(self, K, pose, H, W):
+        K = torch.as_tensor(K).detach().to("cpu", torch.float32)
+        pose = torch.as_tensor(pose).detach().to("cpu", torch.float32)
+        if tuple(K.shape) != (3, 3):
+            raise ValueError("BakedField.render: K must be [3,3], got %s" % (tuple(K.shape),))
+        if tuple(pose.shape) not in ((3, 4), (4, 4)):
+            raise ValueError("BakedField.render: pose must be [3,4] or [4,4] (world -> camera), got %s" % (tuple(pose.shape),))
+        H, W = int(H), int(W)
+        if H < 1 or W < 1:
+            raise ValueError("BakedField.render: H=%d W=%d must be >= 1" % (H, W))
+        return _lib.Pinhole((ctypes.c_float * 9)(*K.reshape(-1).tolist()), (ctypes.c_float * 12)(*pose[:3].reshape(-1).tolist()), H, W)
+
+    def render(self, K, pose, H, W, return_names=(), march_step=None, t_near=0.0, t_far=math.inf, normals=False):
+        """raycast() through the pixels of a pinhole camera the observation need not have had: K [3,3], pose [3,4] or [4,4]
+        world -> camera as curr_obs_torch['pose'] (tensors on any device, or arrays; read on the host), pixel (u, v) looks along
+        R^T ((u - cx)/fx, (v - cy)/fy, 1) from -R^T tc, so 't' is the camera depth.
+        -> {'depth' [H,W] (0: no surface), 'hit_mask' [H,W] bool, 'points' [H,W,3], 'normal' [H,W,3], name: [H,W,C]}."""
+        names = self._ray_names(return_names)
+        cam = self._camera(K, pose, H, W)
+        H, W = cam.H, cam.W
+        t, hit, pts, _ = self._march(None, None, cam, H * W, march_step, t_near, t_far)
+        out = self._at_hits({"depth": t, "hit_mask": hit, "points": pts}, pts, names, normals)
+        return {k: v.view((H, W) + tuple(v.shape[1:])) for k, v in out.items()}

@@ -725,6 +725,68 @@ int d3f_volume_sample_backward(const d3f_volume *vol, const float *pts, int64_t 
     return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_sample_backward launch");
 }
 
+// ---- the first surface a ray meets in a baked volume (raycast_kernels.hip) ----
+int d3f_volume_raycast(const d3f_volume *vol, const float *origins, const float *dirs, int64_t n, const d3f_pinhole *camera,
+                       float march_step, float t_near, float t_far, float *out_t, uint8_t *out_hit, float *out_points,
+                       int32_t *out_samples, void *stream)
+{
+    const int rc = check_volume("volume_raycast", vol);
+    if (rc != D3F_OK) return rc;
+    if (!(vol->step > 0.0f) || vol->step * 0.0f != 0.0f) return fail(D3F_ERR_INVALID_ARG, "volume_raycast: vol->step must be > 0 and finite");
+    if (!(march_step > 0.0f) || march_step * 0.0f != 0.0f) return fail(D3F_ERR_INVALID_ARG, "volume_raycast: march_step must be > 0 and finite");
+    const double ex = vol->nx - 1, ey = vol->ny - 1, ez = vol->nz - 1;
+    const double steps = ceil((double)vol->step * sqrt(ex * ex + ey * ey + ez * ez) / (double)march_step);
+    if (!(steps <= (double)D3F_RAYCAST_MAX_STEPS))
+        return fail(D3F_ERR_INVALID_ARG, "volume_raycast: march_step=%g takes %.0f steps across the box diagonal, more than %d", (double)march_step, steps,
+                    D3F_RAYCAST_MAX_STEPS);
+    if (!(t_near >= 0.0f) || t_near * 0.0f != 0.0f) return fail(D3F_ERR_INVALID_ARG, "volume_raycast: t_near must be >= 0 and finite");
+    if (t_far != t_far) return fail(D3F_ERR_INVALID_ARG, "volume_raycast: t_far is NaN");
+    if (n < 0) return fail(D3F_ERR_INVALID_ARG, "volume_raycast: n=%lld is negative", (long long)n);
+    if (n > 0x7fffffffLL) return fail(D3F_ERR_BAD_SHAPE, "volume_raycast: n=%lld rays, more than 2^31 - 1", (long long)n);
+    d3f::RayParams P = {};
+    if (camera) {
+        if (camera->H < 0 || camera->W < 0) return fail(D3F_ERR_BAD_SHAPE, "volume_raycast: camera H=%d W=%d", camera->H, camera->W);
+        if ((int64_t)camera->H * camera->W > 0x7fffffffLL)
+            return fail(D3F_ERR_BAD_SHAPE, "volume_raycast: camera H*W=%lld pixels, more than 2^31 - 1", (long long)camera->H * camera->W);
+        if (n != (int64_t)camera->H * camera->W) return fail(D3F_ERR_BAD_SHAPE, "volume_raycast: n=%lld but camera H*W=%lld", (long long)n, (long long)camera->H * camera->W);
+        if (origins || dirs) return fail(D3F_ERR_INVALID_ARG, "volume_raycast: origins / dirs must be NULL with a camera");
+        const float fx = camera->K[0], fy = camera->K[4];
+        if (fx == 0.0f || fy == 0.0f || fx * 0.0f != 0.0f || fy * 0.0f != 0.0f) return fail(D3F_ERR_INVALID_ARG, "volume_raycast: camera fx / fy must be non-zero and finite");
+        P.H = camera->H; P.W = camera->W;
+        P.fx = fx; P.fy = fy; P.cx = camera->K[2]; P.cy = camera->K[5];
+        for (int r = 0; r < 3; ++r)
+            for (int a = 0; a < 3; ++a) P.R[3 * r + a] = camera->pose[4 * r + a];
+        for (int a = 0; a < 3; ++a) {                      // o = -R^T tc in double, rounded once
+            double acc = 0.0;
+            for (int r = 0; r < 3; ++r) acc += (double)camera->pose[4 * r + a] * (double)camera->pose[4 * r + 3];
+            P.co[a] = (float)(-acc);
+        }
+    }
+    if (n == 0) return D3F_OK;
+    if (!vol->dist || !vol->cell_valid) return fail(D3F_ERR_INVALID_ARG, "volume_raycast: vol->dist / vol->cell_valid must be non-NULL");
+    if (!camera && (!origins || !dirs)) return fail(D3F_ERR_INVALID_ARG, "volume_raycast: origins / dirs must be non-NULL without a camera");
+    if (!out_t || !out_hit || !out_points) return fail(D3F_ERR_INVALID_ARG, "volume_raycast: out_t / out_hit / out_points must be non-NULL");
+    if (!aligned(vol->dist, 4) || !aligned(origins, 4) || !aligned(dirs, 4) || !aligned(out_t, 4) || !aligned(out_points, 4) || !aligned(out_samples, 4))
+        return fail(D3F_ERR_BAD_LAYOUT, "volume_raycast: vol->dist / origins / dirs / out_t / out_points / out_samples must be 4-byte aligned");
+    P.dist = vol->dist;
+    P.cell = vol->cell_valid;
+    P.origins = origins;
+    P.dirs = dirs;
+    P.out_t = out_t;
+    P.out_hit = out_hit;
+    P.out_pts = out_points;
+    P.out_samples = out_samples;
+    P.n = n;
+    P.nx = vol->nx; P.ny = vol->ny; P.nz = vol->nz;
+    P.ox = vol->origin[0]; P.oy = vol->origin[1]; P.oz = vol->origin[2];
+    P.h = vol->step;
+    P.march = march_step;
+    P.t_near = t_near;
+    P.t_far = t_far;
+    hipError_t e = d3f::launch_volume_raycast(P, camera != nullptr, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_raycast launch");
+}
+
 int64_t d3f_fps_workspace_bytes(int64_t n) { return n > 0 ? d3f::fps_workspace_bytes(n, 4) : 0; }
 int64_t d3f_fps_pixels_workspace_bytes(int64_t n) { return n > 0 ? d3f::fps_workspace_bytes(n, 8) : 0; }
 

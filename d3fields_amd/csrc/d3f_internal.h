@@ -225,6 +225,28 @@ hipError_t launch_volume_cell_valid(const uint8_t *valid, uint8_t *cell, int nx,
 hipError_t launch_volume_sample(const VolParams &P, hipStream_t s);
 hipError_t launch_volume_backward(const VolParams &P, hipStream_t s);
 
+// raycast_kernels.hip: the first surface a ray meets in a baked volume
+constexpr float kRayMaxSamples = 131072.0f;  // a ray whose K exceeds this misses: unreachable under the entry point's 65536-step guard but for overflow
+struct RayParams {
+    const float *dist;
+    const uint8_t *cell;     // [nx-1, ny-1, nz-1]
+    const float *origins;    // explicit rays: [n, 3] each
+    const float *dirs;
+    float *out_t;            // [n]
+    uint8_t *out_hit;        // [n]
+    float *out_pts;          // [n, 3]
+    int32_t *out_samples;    // [n] or nullptr
+    int64_t n;
+    int32_t nx, ny, nz;
+    float ox, oy, oz, h;
+    float march, t_near, t_far;
+    int32_t H, W;            // camera rays: pixel (u, v) is ray v * W + u
+    float fx, fy, cx, cy;
+    float R[9];              // world -> camera rotation, row-major
+    float co[3];             // the camera centre -R^T tc
+};
+hipError_t launch_volume_raycast(const RayParams &P, bool camera, hipStream_t s);
+
 // pcd_kernels.hip
 hipError_t launch_backproject(const double *depth, const uint8_t *mask, int H, int W, const double *cam, const double *T,
                               const double *bounds, int64_t capacity, double *out_pts, int32_t *out_pixel, int64_t *count,

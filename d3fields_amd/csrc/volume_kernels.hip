@@ -19,6 +19,7 @@
 // a lane sums grad * that over its channels, a group folds its sixteen partial sums (__shfl_xor), the lane that located the point
 // adds them to its own (phase A) sums and writes the row: three plain stores per point, no atomics.
 #include "d3f_internal.h"
+#include "volume_cell.h"      // corner_weights, corner_offset, blend
 
 namespace d3f {
 
@@ -50,24 +51,6 @@ __device__ __forceinline__ Cell locate(const VolParams &P, int64_t i)
         if (P.cell[cell] != 0) c.base = (ix * P.ny + iy) * P.nz + iz;
     }
     return c;
-}
-
-__device__ __forceinline__ void corner_weights(float tx, float ty, float tz, float (&w)[8])
-{
-    const float ax[2] = {1.0f - tx, tx}, ay[2] = {1.0f - ty, ty}, az[2] = {1.0f - tz, tz};
-#pragma unroll
-    for (int c = 0; c < 8; ++c) w[c] = ax[c >> 2] * ay[(c >> 1) & 1] * az[c & 1];
-}
-
-// voxel offset of corner c = dx*4 + dy*2 + dz from the cell's base
-__device__ __forceinline__ int64_t corner_offset(int c, int64_t sx, int64_t sy) { return (c >> 2) * sx + ((c >> 1) & 1) * sy + (c & 1); }
-
-__device__ __forceinline__ float blend(const float (&w)[8], const float (&v)[8])
-{
-    float acc = w[0] * v[0];
-#pragma unroll
-    for (int c = 1; c < 8; ++c) acc = fmaf(w[c], v[c], acc);
-    return acc;
 }
 
 __device__ __forceinline__ float4 blend4(const float (&w)[8], const float4 (&v)[8])

@@ -946,7 +946,8 @@ class Fusion:
     def bake(self, boundaries, step_size, return_names=[]):
         """eval_grid(boundaries, step_size, return_names) kept as a baked.BakedField: its eval(pts) interpolates that volume
         trilinearly (eight corner rows per point, no projection into the views) and has a closed-form gradient w.r.t. pts.
-        The field holds the grid query's tensors and no reference to this object: it keeps answering, unchanged, after update()."""
+        The field holds the grid query's tensors and no reference to this object: it keeps answering, unchanged, after update().
+        BakedField.raycast / render march rays through it to the first surface."""
         from .baked import BakedField
         return BakedField.from_fusion(self, boundaries, step_size, return_names)
 

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define D3F_ABI_VERSION 11
+#define D3F_ABI_VERSION 12
 
 #define D3F_OK 0
 #define D3F_ERR_INVALID_ARG (-1)  /* null pointer, negative count, bad enum               */
@@ -404,6 +404,42 @@ int d3f_volume_sample(const d3f_volume *vol, const float *pts, int64_t n, const 
  * lane: no atomics, two runs agree bit for bit. */
 int d3f_volume_sample_backward(const d3f_volume *vol, const float *pts, int64_t n, const d3f_volume_set *sets, int32_t n_sets,
                                const float *grad_dist, const void *const *grad_sets, float *grad_pts, void *stream);
+
+/* (ABI 12) The first surface a ray meets in a baked volume: a fixed-step march through `dist` with one linear interpolation at the
+ * sign change.  Everything in fp32.  Ray i is p(t) = o + t*d; d need not be unit.
+ *   once per ray: go_a = (o_a - origin_a) / h, gd_a = d_a / h (IEEE divisions), len = sqrtf(fma(d_z, d_z, fma(d_y, d_y, d_x*d_x)));
+ *   the ray MISSES if a go_a or gd_a is not finite (NaN or infinite input) or len is not in (0, inf) (d = 0);
+ *   clip: per axis with gd_a != 0, ta = (0 - go_a) / gd_a, tb = ((n_a - 1) - go_a) / gd_a, lo = max(lo, min(ta, tb)), hi = min(hi, max(ta, tb))
+ *         from lo = -inf, hi = +inf; an axis with gd_a == 0 constrains nothing if 0 <= go_a <= n_a - 1, else the ray misses;
+ *         t0 = max(lo, t_near), t1 = min(hi, t_far); the ray misses if !(t0 <= t1);
+ *   samples: dt = march_step / len (march_step is a world length), K = floor((t1 - t0) / dt) (a ray with K > 2^17 misses: overflow only, see
+ *         the guard below), t_k = fma(k, dt, t0) for k = 0..K -- never accumulated --, g_k,a = min(max(fma(t_k, gd_a, go_a), 0), n_a - 1):
+ *         the clip already put the sample into the box, the clamp takes the box faces away as a knife edge;
+ *   cell i_a = min(floor(g_a), n_a - 2), t_a = g_a - i_a, validity cell_valid[i] and s_k = the eight-corner chain on `dist` exactly as
+ *         d3f_volume_sample forms them; no corner of an invalid cell is read;
+ *   decision, `prev` empty at first: an invalid sample empties prev (a hole is never bridged); a valid sample with prev > 0 and s_k <= 0
+ *         is the HIT, t* = fma(dt, prev / (prev - s_k), t_{k-1}), and the march stops; any other valid sample becomes prev.  A crossing
+ *         from - to + (a back face) is no hit, nor is a first valid sample <= 0.  No refinement beyond this interpolation.
+ * Outputs per ray: out_t = t* (0 for a miss, the reference's "no depth"), out_hit one byte, out_points = fma(t*, d_a, o_a) (a NaN row
+ * for a miss, which d3f_volume_sample answers with "not valid" and the fill rows), out_samples (may be NULL) the samples taken.
+ * Rays: `camera` NULL: origins / dirs [n,3] on the device, one lane per ray in caller order.  `camera` non-NULL (HOST memory;
+ * origins / dirs must be NULL and n == H*W): pixel (u, v), u the column, is ray v*W + u with dc = ((u - cx)/fx, (v - cy)/fy, 1),
+ * d_a = fma(R[1][a], dc_y, R[0][a]*dc_x) + R[2][a] (= R^T dc) and o = -R^T tc, formed once per launch on the host in double and rounded;
+ * pose = [R | tc] world -> camera, 3 x 4 row-major; of K only fx = K[0], cx = K[2], fy = K[4], cy = K[5] are read.  d_cam,z = 1, so t is
+ * the camera depth.  A wave takes an 8 x 8 pixel tile.
+ * Status errors, never device-side checks: march_step not finite or <= 0; ceil(box diagonal / march_step) > 65536 (a bad argument must
+ * not become a long kernel); t_near not finite or < 0; t_far NaN; n or H*W > 2^31 - 1; fx or fy zero or not finite; the volume checks
+ * of d3f_volume_sample.  n == 0: D3F_OK, nothing is read.  One launch on `stream`; no atomics, no allocation, no synchronisation;
+ * two runs agree bit for bit. */
+#define D3F_RAYCAST_MAX_STEPS 65536
+typedef struct d3f_pinhole {
+    float K[9];                /* row-major 3 x 3 */
+    float pose[12];            /* row-major 3 x 4, world -> camera */
+    int32_t H, W;
+} d3f_pinhole;
+int d3f_volume_raycast(const d3f_volume *vol, const float *origins, const float *dirs, int64_t n, const d3f_pinhole *camera,
+                       float march_step, float t_near, float t_far, float *out_t, uint8_t *out_hit, float *out_points,
+                       int32_t *out_samples, void *stream);
 
 /* fps_np (utils/my_utils.py:478-497): k samples of pts[n,3] starting from init_idx, float32 Euclidean distances,
  * first maximum wins -> out_idx[k] (int64, device), out_maxdist (device float, may be NULL).  k may exceed n: like
