@@ -9,7 +9,7 @@ import os
 
 from . import build as _build
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 # status codes (include/d3fields_hip.h)
 OK = 0
@@ -73,6 +73,11 @@ class VolumeSet(ctypes.Structure):
     _fields_ = [("data", _vp), ("C", _i32), ("reserved", _i32), ("stride_voxel", _i64), ("fill", _vp)]
 
 
+class Band(ctypes.Structure):
+    """struct d3f_band"""
+    _fields_ = [("slot", _vp), ("cell_band", _vp), ("n_rows", _i64)]
+
+
 class Pinhole(ctypes.Structure):
     """struct d3f_pinhole (host memory)"""
     _fields_ = [("K", _f32 * 9), ("pose", _f32 * 12), ("H", _i32), ("W", _i32)]
@@ -130,6 +135,12 @@ SIGNATURES = {
     "d3f_volume_sample": (ctypes.c_int, [ctypes.POINTER(Volume), _vp, _i64, ctypes.POINTER(VolumeSet), _i32, _vp, _vp, ctypes.POINTER(_vp), _vp]),
     "d3f_volume_sample_backward": (ctypes.c_int, [ctypes.POINTER(Volume), _vp, _i64, ctypes.POINTER(VolumeSet), _i32, _vp, ctypes.POINTER(_vp),
                                                   _vp, _vp]),
+    "d3f_band_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "d3f_band_mark": (ctypes.c_int, [ctypes.POINTER(Volume), _f32, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "d3f_band_sample": (ctypes.c_int, [ctypes.POINTER(Volume), ctypes.POINTER(Band), _vp, _i64, ctypes.POINTER(VolumeSet), _i32, _vp, _vp, _vp,
+                                       ctypes.POINTER(_vp), _vp]),
+    "d3f_band_sample_backward": (ctypes.c_int, [ctypes.POINTER(Volume), ctypes.POINTER(Band), _vp, _i64, ctypes.POINTER(VolumeSet), _i32, _vp,
+                                                ctypes.POINTER(_vp), _vp, _vp]),
     "d3f_volume_raycast": (ctypes.c_int, [ctypes.POINTER(Volume), _vp, _vp, _i64, ctypes.POINTER(Pinhole), _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp]),
     "d3f_fps_workspace_bytes": (_i64, [_i64]),
     "d3f_fps_pixels_workspace_bytes": (_i64, [_i64]),

@@ -8,6 +8,11 @@ interpolates the FUSED field -- it does not re-fuse -- so off the lattice it is 
 `BakedField.raycast(origins, dirs)` and `BakedField.render(K, pose, H, W)` march rays through `dist` to the first surface they
 meet (d3f_volume_raycast, csrc/raycast_kernels.hip) and read rows and normals at the hit points with the lookup above.
 
+`BakedField.to_band(band)` / `Fusion.bake(..., band=)` keep channel rows only for the voxels a cell near the surface needs
+(d3f_band_mark): `dist` / `valid` stay dense, one int32 slot per voxel names its row in a compacted `[M, C]`
+array, and every lookup above goes through d3f_band_sample / d3f_band_sample_backward -- the same bits wherever the band covers the
+point, the fill row and `in_band = False` elsewhere.
+
 There is no CPU path: volumes and points live on the ROCm device.
 """
 import ctypes
@@ -23,19 +28,37 @@ _RESERVED = ("dist", "valid_mask", "grid_shape")
 _RAY_KEYS = ("t", "depth", "hit_mask", "points", "normal")      # output keys of raycast / render: a set of that name cannot be asked for there
 
 
+def _check_band(band, who):
+    try:
+        value = float(band)
+    except (TypeError, ValueError):
+        raise TypeError("%s: band must be a number (a world length), got %r" % (who, band))
+    if not (value > 0.0 and math.isfinite(value)):
+        raise ValueError("%s: band must be a finite length > 0, got %r" % (who, band))
+    return value
+
+
+def _check_band_names(names):
+    if "in_band" in names:
+        raise ValueError("a set named 'in_band' cannot live in a banded field: 'in_band' is an output key of its lookups")
+
+
 class _BakedQueryFn(torch.autograd.Function):
-    """BakedField.eval as an autograd node: forward = d3f_volume_sample, backward = d3f_volume_sample_backward."""
+    """BakedField.eval as an autograd node: forward = d3f_volume_sample, backward = d3f_volume_sample_backward (d3f_band_sample and
+    d3f_band_sample_backward on a banded field, whose 'in_band' follows 'valid_mask')."""
 
     @staticmethod
     def forward(ctx, pts, field, names):
         pts_c = pts.detach().contiguous()
         out = field._sample(pts_c, names)
         ctx.field, ctx.names, ctx.pts = field, names, pts_c
-        ctx.mark_non_differentiable(out["valid_mask"])
-        return (out["dist"], out["valid_mask"]) + tuple(out[k] for k in names)
+        masks = tuple(out[k] for k in field._mask_keys())
+        ctx.mark_non_differentiable(*masks)
+        return (out["dist"],) + masks + tuple(out[k] for k in names)
 
     @staticmethod
-    def backward(ctx, grad_dist, _grad_valid, *grad_sets):
+    def backward(ctx, grad_dist, *rest):
+        grad_sets = rest[len(ctx.field._mask_keys()):]
         return ctx.field.backward(ctx.pts, grad_dist, dict(zip(ctx.names, grad_sets))), None, None
 
 
@@ -48,9 +71,13 @@ class BakedField:
     dist        float32 [nx, ny, nz];  valid: bool [nx, ny, nz]
     names()     the channel sets, each float32 [nx, ny, nz, C]
 
+    A BANDED field (to_band / Fusion.bake(band=)) holds each set as [M, C] rows of the stored voxels instead, and has
+    band (the world length), slot int32 [nx, ny, nz] (-1: no row), cell_band uint8 [nx-1, ny-1, nz-1], band_voxels int32 [M]
+    (ascending flat indices), band_points() and stored_fraction; its lookups add 'in_band'.  A dense field has band = None.
+
     It holds tensors only -- no reference to the Fusion that made it -- and stays valid after Fusion.update()."""
 
-    def __init__(self, origin, step, dist, valid, sets, fills, boundaries=None):
+    def __init__(self, origin, step, dist, valid, sets, fills, boundaries=None, axes=None):
         self.origin = tuple(float(o) for o in origin)
         self.step = float(step)
         self.grid_shape = torch.Size(dist.shape)
@@ -64,6 +91,8 @@ class BakedField:
         self.boundaries = dict(boundaries)
         self.device = dist.device
         self._lib = _lib.load()
+        self._axes = axes                 # the three axis tensors of the grid that was baked (Fusion.bake), or None: origin + i * step
+        self.band = self.slot = self.cell_band = self.band_voxels = None
         self.cell_valid = torch.empty((nx - 1, ny - 1, nz - 1), dtype=torch.uint8, device=self.device)
         vol = self._volume()
         with torch.cuda.device(self.device):
@@ -116,22 +145,124 @@ class BakedField:
         return cls(origin, step, dist, valid, sets, fills)
 
     @classmethod
-    def from_fusion(cls, fusion, boundaries, step_size, return_names=()):
+    def from_fusion(cls, fusion, boundaries, step_size, return_names=(), band=None):
         """Fusion.bake: one eval_grid, its tensors viewed (not copied) as the volume; a projected name's fill row is -b, what
-        Fusion.eval returns for an all-invalid point."""
+        Fusion.eval returns for an all-invalid point.  With a band: the distance-only grid pass, d3f_band_mark, and ONE
+        batch_eval of the M stored voxel centres (the grid's own axis values) whose [M, C] outputs are the row arrays -- no
+        [nx, ny, nz, C] array exists at any time."""
         from .fusion import _grid_axes
         names = list(return_names)
+        if band is not None:
+            band = _check_band(band, "bake")
+            _check_band_names(names)
         with torch.no_grad():
-            res = fusion.eval_grid(boundaries, step_size, return_names=names)
+            res = fusion.eval_grid(boundaries, step_size, return_names=names if band is None else [])
         nx, ny, nz = res["grid_shape"]
         if min(nx, ny, nz) < 2:
             raise ValueError("bake: the grid %s needs at least two voxels along every axis" % ((nx, ny, nz),))
-        origin = [float(a[0]) for a in _grid_axes(boundaries, step_size)]
-        step = float(torch.tensor(step_size, dtype=torch.float32))
         dev = res["dist"].device
-        sets = {k: res[k].view(nx, ny, nz, -1) for k in names}
+        axes = [a.to(dev) for a in _grid_axes(boundaries, step_size)]
+        origin = [float(a[0]) for a in axes]
+        step = float(torch.tensor(step_size, dtype=torch.float32))
         fills = {k: (-fusion._head_on(k, dev)[1]).contiguous() if k in fusion._projections else None for k in names}
-        return cls(origin, step, res["dist"].view(nx, ny, nz), res["valid_mask"].view(nx, ny, nz), sets, fills, boundaries=boundaries)
+        dist, valid = res["dist"].view(nx, ny, nz), res["valid_mask"].view(nx, ny, nz)
+        if band is None:
+            sets = {k: res[k].view(nx, ny, nz, -1) for k in names}
+            return cls(origin, step, dist, valid, sets, fills, boundaries=boundaries, axes=axes)
+        field = cls(origin, step, dist, valid, {}, {}, boundaries=boundaries, axes=axes)
+        mark = field._mark(band)
+        pts = field._voxel_centres(mark[2])
+        with torch.no_grad():
+            if pts.shape[0] > 0:
+                rows = fusion.batch_eval(pts, return_names=names)
+                rows = {k: rows[k] for k in names}
+            else:                     # nothing within the band: empty row arrays of the widths the query would write
+                rows = {k: torch.empty((0, fusion._query_map(k, dev).shape[3]), dtype=torch.float32, device=dev) for k in names}
+        return field._banded(band, mark, rows, fills)
+
+    # ---- the band -------------------------------------------------------------------------------------------------------------
+    def _mark(self, band):
+        """d3f_band_mark -> (cell_band, slot, voxels [M]); a capacity that turns out too small costs one re-run with the count"""
+        dev = self.device
+        nx, ny, nz = self.grid_shape
+        n = nx * ny * nz
+        cell_band = torch.empty((nx - 1, ny - 1, nz - 1), dtype=torch.uint8, device=dev)
+        slot = torch.empty((nx, ny, nz), dtype=torch.int32, device=dev)
+        count = torch.zeros(1, dtype=torch.int64, device=dev)
+        ws_bytes = int(self._lib.d3f_band_workspace_bytes(nx, ny, nz))
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+        vol = self._volume()
+        capacity = min(n, max(1 << 12, n // 8))
+        while True:
+            voxels = torch.empty(capacity, dtype=torch.int32, device=dev)
+            with torch.cuda.device(dev):
+                _lib.check(self._lib.d3f_band_mark(ctypes.byref(vol), float(band), _lib.ptr(cell_band), _lib.ptr(slot), _lib.ptr(voxels), capacity,
+                                                   _lib.ptr(count), _lib.ptr(ws), ws_bytes, _lib.current_stream_handle(dev)))
+            found = int(count.item())
+            if found <= capacity:
+                break
+            capacity = found
+        return cell_band, slot, voxels[:found].clone() if found < capacity else voxels
+
+    def _voxel_centres(self, voxels):
+        """[len, 3] centres of the voxels with these flat indices: the baked grid's own axis values where the field came from
+        Fusion.bake (exactly the points eval_grid evaluated), origin + i * step in float32 otherwise"""
+        nx, ny, nz = self.grid_shape
+        q = voxels.long()
+        iz, ixy = q % nz, q // nz
+        ix, iy = ixy // ny, ixy % ny
+        if self._axes is not None:
+            return torch.stack((self._axes[0][ix], self._axes[1][iy], self._axes[2][iz]), dim=1)
+        o = torch.tensor(self.origin, dtype=torch.float32, device=self.device)
+        return o + torch.stack((ix, iy, iz), dim=1).to(torch.float32) * torch.tensor(self.step, dtype=torch.float32, device=self.device)
+
+    def _banded(self, band, mark, rows, fills):
+        """a field that shares this one's dist / valid / cell_valid and holds `rows` {name: [M, C]} behind the slot volume"""
+        f = object.__new__(type(self))
+        f.__dict__.update(self.__dict__)
+        f.band = float(band)
+        f.cell_band, f.slot, f.band_voxels = mark
+        f._sets, f._fills = dict(rows), dict(fills)
+        return f
+
+    def to_band(self, band):
+        """A new field with the same dist / valid / cell_valid (shared, not copied) whose sets keep only the rows of the voxels a
+        cell within `band` (a world length > 0) of the surface needs: seed = valid & |dist| < band, a cell is kept if it is valid
+        and has a seed corner, a voxel is stored if it is a corner of a kept cell.  Lookups give the same bits as this field where
+        'in_band', the fill row elsewhere."""
+        if self.band is not None:
+            raise ValueError("to_band: this field is already banded (band = %g)" % self.band)
+        band = _check_band(band, "to_band")
+        _check_band_names(self.names())
+        mark = self._mark(band)
+        idx = mark[2].long()
+        rows = {k: t.view(-1, t.shape[3]).index_select(0, idx) for k, t in self._sets.items()}
+        return self._banded(band, mark, rows, self._fills)
+
+    def _need_band(self, what):
+        if self.band is None:
+            raise AttributeError("%s: this field is dense; to_band(band) or Fusion.bake(..., band=) make a banded one" % what)
+
+    def band_points(self):
+        """[M, 3] float32: the centres of the stored voxels, in slot order"""
+        self._need_band("band_points")
+        return self._voxel_centres(self.band_voxels)
+
+    @property
+    def stored_fraction(self):
+        """M / (nx * ny * nz)"""
+        self._need_band("stored_fraction")
+        nx, ny, nz = self.grid_shape
+        return self.band_voxels.shape[0] / float(nx * ny * nz)
+
+    def _band_struct(self):
+        return _lib.Band(_lib.ptr(self.slot), _lib.ptr(self.cell_band), self.band_voxels.shape[0])
+
+    def _mask_keys(self):
+        return ("valid_mask",) if self.band is None else ("valid_mask", "in_band")
+
+    def _channels(self, name):
+        return self._sets[name].shape[-1]
 
     # ---- description ----------------------------------------------------------------------------------------------------------
     def names(self):
@@ -140,7 +271,7 @@ class BakedField:
     def fill_row(self, name):
         """[C] row of `name` at a point that is not valid"""
         f = self._fills[name]
-        return torch.zeros(self._sets[name].shape[3], dtype=torch.float32, device=self.device) if f is None else f
+        return torch.zeros(self._channels(name), dtype=torch.float32, device=self.device) if f is None else f
 
     def _volume(self):
         nx, ny, nz = self.grid_shape
@@ -151,7 +282,7 @@ class BakedField:
         arr = (_lib.VolumeSet * max(len(names), 1))()
         for s, k in enumerate(names):
             t = self._sets[k]
-            arr[s] = _lib.VolumeSet(t.data_ptr(), t.shape[3], 0, t.stride(2), _lib.ptr(self._fills[k]))
+            arr[s] = _lib.VolumeSet(t.data_ptr(), t.shape[-1], 0, t.stride(-2), _lib.ptr(self._fills[k]))      # dense: the voxel stride; banded: the row stride
         return arr
 
     def _check_query(self, pts):
@@ -177,18 +308,27 @@ class BakedField:
         dev, n = self.device, pts_c.shape[0]
         out = {"dist": torch.empty(n, dtype=torch.float32, device=dev), "valid_mask": torch.empty(n, dtype=torch.bool, device=dev)}
         outs = (ctypes.c_void_p * max(len(names), 1))()
+        if self.band is not None:
+            out["in_band"] = torch.empty(n, dtype=torch.bool, device=dev)
         for s, k in enumerate(names):
-            out[k] = torch.empty((n, self._sets[k].shape[3]), dtype=torch.float32, device=dev)
+            out[k] = torch.empty((n, self._channels(k)), dtype=torch.float32, device=dev)
             outs[s] = out[k].data_ptr()
         vol = self._volume()
         with torch.cuda.device(dev):
-            _lib.check(self._lib.d3f_volume_sample(ctypes.byref(vol), _lib.ptr(pts_c), n, self._set_array(names), len(names), _lib.ptr(out["dist"]),
-                                                   _lib.ptr(out["valid_mask"]), outs, _lib.current_stream_handle(dev)))
+            if self.band is None:
+                _lib.check(self._lib.d3f_volume_sample(ctypes.byref(vol), _lib.ptr(pts_c), n, self._set_array(names), len(names), _lib.ptr(out["dist"]),
+                                                       _lib.ptr(out["valid_mask"]), outs, _lib.current_stream_handle(dev)))
+            else:
+                band = self._band_struct()
+                _lib.check(self._lib.d3f_band_sample(ctypes.byref(vol), ctypes.byref(band), _lib.ptr(pts_c), n, self._set_array(names), len(names),
+                                                     _lib.ptr(out["dist"]), _lib.ptr(out["valid_mask"]), _lib.ptr(out["in_band"]), outs,
+                                                     _lib.current_stream_handle(dev)))
         return out
 
     def backward(self, pts, grad_dist=None, grad_sets=None):
         """grad_pts [N,3] = d(sum grad_dist * dist + sum over names of grad * row) / d pts (d3f_volume_sample_backward);
-        grad_sets: {name: [N,C] or None}."""
+        grad_sets: {name: [N,C] or None}.  Banded (d3f_band_sample_backward): the dist term at every valid point, a set's term
+        only where 'in_band'."""
         self._check_query(pts)
         pts_c = pts.detach().contiguous()
         dev, n = self.device, pts_c.shape[0]
@@ -198,8 +338,8 @@ class BakedField:
         hold = []
         for s, k in enumerate(names):
             g = grad_sets[k].detach().to(torch.float32).contiguous()
-            if tuple(g.shape) != (n, self._sets[k].shape[3]) or g.device != dev:
-                raise ValueError("backward: the gradient of %r must be [%d,%d] on %s" % (k, n, self._sets[k].shape[3], dev))
+            if tuple(g.shape) != (n, self._channels(k)) or g.device != dev:
+                raise ValueError("backward: the gradient of %r must be [%d,%d] on %s" % (k, n, self._channels(k), dev))
             hold.append(g)
             grads[s] = g.data_ptr()
         gd = None
@@ -210,19 +350,25 @@ class BakedField:
         grad_pts = torch.empty((n, 3), dtype=torch.float32, device=dev)
         vol = self._volume()
         with torch.cuda.device(dev):
-            _lib.check(self._lib.d3f_volume_sample_backward(ctypes.byref(vol), _lib.ptr(pts_c), n, self._set_array(names), len(names), _lib.ptr(gd),
-                                                            grads, _lib.ptr(grad_pts), _lib.current_stream_handle(dev)))
+            if self.band is None:
+                _lib.check(self._lib.d3f_volume_sample_backward(ctypes.byref(vol), _lib.ptr(pts_c), n, self._set_array(names), len(names), _lib.ptr(gd),
+                                                                grads, _lib.ptr(grad_pts), _lib.current_stream_handle(dev)))
+            else:
+                band = self._band_struct()
+                _lib.check(self._lib.d3f_band_sample_backward(ctypes.byref(vol), ctypes.byref(band), _lib.ptr(pts_c), n, self._set_array(names), len(names),
+                                                              _lib.ptr(gd), grads, _lib.ptr(grad_pts), _lib.current_stream_handle(dev)))
         return grad_pts
 
     def eval(self, pts, return_names=None):
         """The dict of Fusion.eval -- 'dist' [N], 'valid_mask' [N] bool, one [N,C] float32 per name (None: every baked name) --
-        interpolated in the volume.  Not valid (outside, a NaN coordinate, a cell with an invalid corner): dist 1e3, the fill row."""
+        interpolated in the volume.  Not valid (outside, a NaN coordinate, a cell with an invalid corner): dist 1e3, the fill row.
+        A banded field adds 'in_band' [N] bool after 'valid_mask' (valid and the point's cell is kept): rows are the dense field's
+        where it is set and the fill row elsewhere; dist and valid_mask never depend on the band."""
         self._check_query(pts)
         names = self._names(return_names)
         if pts.requires_grad and torch.is_grad_enabled():
             res = _BakedQueryFn.apply(pts, self, tuple(names))
-            out = {"dist": res[0], "valid_mask": res[1]}
-            out.update(zip(names, res[2:]))
+            out = dict(zip(("dist",) + self._mask_keys() + tuple(names), res))
             return out
         return self._sample(pts.detach().contiguous(), names)
 
@@ -246,9 +392,10 @@ class BakedField:
 
     def _ray_names(self, return_names):
         names = self._names(list(return_names))
-        clash = [k for k in names if k in _RAY_KEYS]
+        keys = _RAY_KEYS + (("in_band",) if self.band is not None else ())
+        clash = [k for k in names if k in keys]
         if clash:
-            raise ValueError("raycast / render: the set(s) %s carry the name of an output key %s; read them with eval(out['points'])" % (clash, _RAY_KEYS))
+            raise ValueError("raycast / render: the set(s) %s carry the name of an output key %s; read them with eval(out['points'])" % (clash, keys))
         return names
 
     def _march(self, origins, dirs, camera, n, march_step, t_near, t_far, samples=False):
@@ -273,8 +420,10 @@ class BakedField:
             grad = self.backward(pts, torch.ones(pts.shape[0], dtype=torch.float32, device=self.device))
             length = torch.linalg.vector_norm(grad, dim=1, keepdim=True)
             out["normal"] = torch.where(length > 0, grad / length, torch.zeros_like(grad))
-        if names:
+        if names or self.band is not None:
             rows = self._sample(pts, names)
+            if self.band is not None:
+                out["in_band"] = rows["in_band"]      # of the hit point's cell: False for a miss, and for a hit outside the band (fill rows)
             for k in names:
                 out[k] = rows[k]
         return out

@@ -643,7 +643,7 @@ int d3f_volume_cell_valid(const d3f_volume *vol, uint8_t *cell_valid_out, void *
 
 // the checks the forward and the backward lookup share; fills P but for the outputs / gradients.  Returns 1 for "nothing to do".
 static int volume_common(const char *who, const d3f_volume *vol, const float *pts, int64_t n, const d3f_volume_set *sets, int32_t n_sets,
-                         d3f::VolParams &P)
+                         d3f::VolParams &P, bool null_data_ok = false)
 {
     int rc = check_volume(who, vol);
     if (rc != D3F_OK) return rc;
@@ -658,7 +658,7 @@ static int volume_common(const char *who, const d3f_volume *vol, const float *pt
     if (!vol->dist || !vol->cell_valid || !pts) return fail(D3F_ERR_INVALID_ARG, "%s: vol->dist / vol->cell_valid / pts must be non-NULL", who);
     if (!aligned(vol->dist, 4) || !aligned(pts, 4)) return fail(D3F_ERR_BAD_LAYOUT, "%s: vol->dist / pts must be 4-byte aligned", who);
     for (int s = 0; s < n_sets; ++s) {
-        if (!sets[s].data) return fail(D3F_ERR_INVALID_ARG, "%s: set %d: data is NULL", who, s);
+        if (!sets[s].data && !null_data_ok) return fail(D3F_ERR_INVALID_ARG, "%s: set %d: data is NULL", who, s);
         if (sets[s].stride_voxel < sets[s].C) return fail(D3F_ERR_BAD_LAYOUT, "%s: set %d: stride_voxel=%lld < C=%d", who, s, (long long)sets[s].stride_voxel, sets[s].C);
         if (!aligned(sets[s].data, 4) || !aligned(sets[s].fill, 4)) return fail(D3F_ERR_BAD_LAYOUT, "%s: set %d: data / fill must be 4-byte aligned", who, s);
         d3f::VolSet &S = P.sets[s];
@@ -723,6 +723,91 @@ int d3f_volume_sample_backward(const d3f_volume *vol, const float *pts, int64_t 
     P.grad_pts = grad_pts;
     hipError_t e = d3f::launch_volume_backward(P, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_sample_backward launch");
+}
+
+// ---- a baked volume with rows only near the surface (band_kernels.hip) ----
+int64_t d3f_band_workspace_bytes(int32_t nx, int32_t ny, int32_t nz)
+{
+    if (nx < 2 || ny < 2 || nz < 2 || (int64_t)nx * ny * nz > 0x7fffffffLL) return 0;
+    return d3f::band_workspace_bytes((int64_t)nx * ny * nz);
+}
+
+int d3f_band_mark(const d3f_volume *vol, float band, uint8_t *cell_band_out, int32_t *slot_out, int32_t *voxels_out, int64_t capacity,
+                  int64_t *count_out, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    const int rc = check_volume("band_mark", vol);
+    if (rc != D3F_OK) return rc;
+    if (!(band > 0.0f) || band * 0.0f != 0.0f) return fail(D3F_ERR_INVALID_ARG, "band_mark: band must be > 0 and finite");
+    if (capacity < 0) return fail(D3F_ERR_INVALID_ARG, "band_mark: capacity=%lld is negative", (long long)capacity);
+    if (!vol->dist || !vol->cell_valid) return fail(D3F_ERR_INVALID_ARG, "band_mark: vol->dist / vol->cell_valid must be non-NULL");
+    if (!cell_band_out || !slot_out || !count_out || (capacity > 0 && !voxels_out))
+        return fail(D3F_ERR_INVALID_ARG, "band_mark: cell_band_out / slot_out / count_out (and voxels_out for a positive capacity) must be non-NULL");
+    if (!aligned(vol->dist, 4) || !aligned(slot_out, 4) || !aligned(voxels_out, 4) || !aligned(count_out, 8))
+        return fail(D3F_ERR_BAD_LAYOUT, "band_mark: vol->dist / slot_out / voxels_out / count_out must be aligned to their element size");
+    if (!workspace || workspace_bytes < d3f_band_workspace_bytes(vol->nx, vol->ny, vol->nz))
+        return fail(D3F_ERR_WORKSPACE, "band_mark: needs %lld workspace bytes", (long long)d3f_band_workspace_bytes(vol->nx, vol->ny, vol->nz));
+    if (!aligned(workspace, 4)) return fail(D3F_ERR_BAD_LAYOUT, "band_mark: workspace must be 4-byte aligned");
+    hipError_t e = d3f::launch_band_mark(vol->dist, vol->cell_valid, vol->nx, vol->ny, vol->nz, band, cell_band_out, slot_out, voxels_out, capacity,
+                                         count_out, workspace, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "band_mark launch");
+}
+
+// the checks of the band on top of volume_common's; fills B but for the outputs / gradients.  Returns 1 for "nothing to do".
+static int band_common(const char *who, const d3f_volume *vol, const d3f_band *band, const float *pts, int64_t n, const d3f_volume_set *sets,
+                       int32_t n_sets, d3f::BandParams &B)
+{
+    if (!band) return fail(D3F_ERR_INVALID_ARG, "%s: band is NULL", who);
+    if (band->n_rows < 0 || band->n_rows > 0x7fffffffLL) return fail(D3F_ERR_BAD_SHAPE, "%s: band->n_rows=%lld outside [0, 2^31 - 1]", who, (long long)band->n_rows);
+    const bool empty = band->n_rows == 0;
+    const int rc = volume_common(who, vol, pts, n, sets, n_sets, B.V, empty);
+    if (rc != D3F_OK) return rc;
+    if (!empty && (!band->slot || !band->cell_band)) return fail(D3F_ERR_INVALID_ARG, "%s: band->slot / band->cell_band must be non-NULL with n_rows > 0", who);
+    if (!empty && !aligned(band->slot, 4)) return fail(D3F_ERR_BAD_LAYOUT, "%s: band->slot must be 4-byte aligned", who);
+    B.slot = empty ? nullptr : band->slot;
+    B.cell_band = empty ? nullptr : band->cell_band;      // nullptr: the kernels read nothing of the band and no row
+    B.out_in_band = nullptr;
+    return D3F_OK;
+}
+
+int d3f_band_sample(const d3f_volume *vol, const d3f_band *band, const float *pts, int64_t n, const d3f_volume_set *sets, int32_t n_sets,
+                    float *out_dist, uint8_t *out_valid, uint8_t *out_in_band, void *const *out_sets, void *stream)
+{
+    d3f::BandParams B;
+    const int rc = band_common("band_sample", vol, band, pts, n, sets, n_sets, B);
+    if (rc != D3F_OK) return rc == 1 ? D3F_OK : rc;
+    if (!out_dist || !out_valid || !out_in_band || (n_sets > 0 && !out_sets))
+        return fail(D3F_ERR_INVALID_ARG, "band_sample: out_dist / out_valid / out_in_band / out_sets must be non-NULL");
+    if (!aligned(out_dist, 4)) return fail(D3F_ERR_BAD_LAYOUT, "band_sample: out_dist must be 4-byte aligned");
+    for (int s = 0; s < n_sets; ++s) {
+        if (!out_sets[s]) return fail(D3F_ERR_INVALID_ARG, "band_sample: out_sets[%d] is NULL", s);
+        if (!aligned(out_sets[s], 4)) return fail(D3F_ERR_BAD_LAYOUT, "band_sample: out_sets[%d] must be 4-byte aligned", s);
+        B.V.sets[s].out = static_cast<float *>(out_sets[s]);
+        if (!aligned(out_sets[s], 16)) B.V.sets[s].vec = 0;
+    }
+    B.V.out_dist = out_dist;
+    B.V.out_valid = out_valid;
+    B.out_in_band = out_in_band;
+    hipError_t e = d3f::launch_band_sample(B, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "band_sample launch");
+}
+
+int d3f_band_sample_backward(const d3f_volume *vol, const d3f_band *band, const float *pts, int64_t n, const d3f_volume_set *sets, int32_t n_sets,
+                             const float *grad_dist, const void *const *grad_sets, float *grad_pts, void *stream)
+{
+    d3f::BandParams B;
+    const int rc = band_common("band_sample_backward", vol, band, pts, n, sets, n_sets, B);
+    if (rc != D3F_OK) return rc == 1 ? D3F_OK : rc;
+    if (!grad_pts) return fail(D3F_ERR_INVALID_ARG, "band_sample_backward: grad_pts is NULL");
+    if (!aligned(grad_pts, 4) || !aligned(grad_dist, 4)) return fail(D3F_ERR_BAD_LAYOUT, "band_sample_backward: grad_pts / grad_dist must be 4-byte aligned");
+    for (int s = 0; s < n_sets && grad_sets; ++s) {
+        if (!aligned(grad_sets[s], 4)) return fail(D3F_ERR_BAD_LAYOUT, "band_sample_backward: grad_sets[%d] must be 4-byte aligned", s);
+        B.V.sets[s].grad = static_cast<const float *>(grad_sets[s]);
+        if (!aligned(grad_sets[s], 16)) B.V.sets[s].vec = 0;
+    }
+    B.V.grad_dist = grad_dist;
+    B.V.grad_pts = grad_pts;
+    hipError_t e = d3f::launch_band_backward(B, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "band_sample_backward launch");
 }
 
 // ---- the first surface a ray meets in a baked volume (raycast_kernels.hip) ----

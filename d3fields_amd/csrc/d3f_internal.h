@@ -225,6 +225,19 @@ hipError_t launch_volume_cell_valid(const uint8_t *valid, uint8_t *cell, int nx,
 hipError_t launch_volume_sample(const VolParams &P, hipStream_t s);
 hipError_t launch_volume_backward(const VolParams &P, hipStream_t s);
 
+// band_kernels.hip: a baked volume whose channel rows exist only near the surface
+struct BandParams {
+    VolParams V;               // sets[s].data / stride: the COMPACTED rows [n_rows, C] and their row stride
+    const int32_t *slot;       // [nx, ny, nz]: the row of a stored voxel, -1 elsewhere
+    const uint8_t *cell_band;  // [nx-1, ny-1, nz-1], or nullptr (n_rows == 0): no point is in the band, nothing of the band is read
+    uint8_t *out_in_band;      // forward: [n]
+};
+int64_t band_workspace_bytes(int64_t n);
+hipError_t launch_band_mark(const float *dist, const uint8_t *cell_valid, int nx, int ny, int nz, float band, uint8_t *cell_band, int32_t *slot,
+                            int32_t *voxels, int64_t capacity, int64_t *count, void *workspace, hipStream_t s);
+hipError_t launch_band_sample(const BandParams &B, hipStream_t s);
+hipError_t launch_band_backward(const BandParams &B, hipStream_t s);
+
 // raycast_kernels.hip: the first surface a ray meets in a baked volume
 constexpr float kRayMaxSamples = 131072.0f;  // a ray whose K exceeds this misses: unreachable under the entry point's 65536-step guard but for overflow
 struct RayParams {

@@ -1,0 +1,168 @@
+// volume_rows.h -- the per-point pieces of the baked-volume lookups (DESIGN.md sections 13 and 15), shared by the dense samplers
+// (volume_kernels.hip: corner rows at voxel * stride) and the band samplers (band_kernels.hip: corner rows at slot[voxel] * stride):
+// locating a point, the fill row, the eight-corner chain over a set's channels and its derivative.  ONE definition, so a banded
+// lookup and a dense one round alike.  The callers differ only in how they form the eight row pointers.
+#pragma once
+#include "d3f_internal.h"
+#include "volume_cell.h"      // corner_weights, corner_offset, blend
+
+namespace d3f {
+
+constexpr int kNotValid = -1;      // Cell::base of a point outside the volume or in a cell with an invalid corner
+constexpr int kNoPoint = -2;       // ... of a lane past the last point
+
+struct Cell {
+    int32_t base;                  // flat index of the cell's corner (0,0,0), < nx*ny*nz <= 2^31 - 1
+    float tx, ty, tz;
+};
+
+// cell: the flat CELL index of a valid point (untouched otherwise)
+__device__ __forceinline__ Cell locate(const VolParams &P, int64_t i, int64_t &cell)
+{
+    const float *p = P.pts + 3 * i;
+    const float gx = (p[0] - P.ox) / P.h, gy = (p[1] - P.oy) / P.h, gz = (p[2] - P.oz) / P.h;
+    Cell c;
+    c.base = kNotValid;
+    c.tx = c.ty = c.tz = 0.0f;
+    // (NaN fails every comparison)
+    const bool inside = gx >= 0.0f && gx <= (float)(P.nx - 1) && gy >= 0.0f && gy <= (float)(P.ny - 1) && gz >= 0.0f && gz <= (float)(P.nz - 1);
+    if (inside) {
+        const int ix = min((int)floorf(gx), P.nx - 2), iy = min((int)floorf(gy), P.ny - 2), iz = min((int)floorf(gz), P.nz - 2);
+        c.tx = gx - (float)ix;
+        c.ty = gy - (float)iy;
+        c.tz = gz - (float)iz;
+        const int64_t at = ((int64_t)ix * (P.ny - 1) + iy) * (P.nz - 1) + iz;
+        if (P.cell[at] != 0) {
+            c.base = (ix * P.ny + iy) * P.nz + iz;
+            cell = at;
+        }
+    }
+    return c;
+}
+
+__device__ __forceinline__ Cell locate(const VolParams &P, int64_t i)
+{
+    int64_t cell;
+    return locate(P, i, cell);
+}
+
+__device__ __forceinline__ float4 blend4(const float (&w)[8], const float4 (&v)[8])
+{
+    float4 acc = make_float4(w[0] * v[0].x, w[0] * v[0].y, w[0] * v[0].z, w[0] * v[0].w);
+#pragma unroll
+    for (int c = 1; c < 8; ++c) {
+        acc.x = fmaf(w[c], v[c].x, acc.x);
+        acc.y = fmaf(w[c], v[c].y, acc.y);
+        acc.z = fmaf(w[c], v[c].z, acc.z);
+        acc.w = fmaf(w[c], v[c].w, acc.w);
+    }
+    return acc;
+}
+
+__device__ __forceinline__ float fill_of(const VolSet &S, int ch) { return S.fill ? S.fill[ch] : 0.0f; }
+
+// channels [first, C) in steps of `lanes` vectors / floats of the row of point i: lanes = 1 is phase A, 16 is phase B.
+// rows(row): called for a point that has rows (`has`), fills the eight corner row pointers; otherwise the fill row is written
+template <class Rows>
+__device__ __forceinline__ void sample_row(const VolSet &S, int64_t i, bool has, const float (&w)[8], int first, int lanes, Rows rows)
+{
+    float *o = S.out + i * S.C;
+    if (!has) {
+        if (S.vec) {
+            for (int k = 4 * first; k < S.C; k += 4 * lanes)
+                *reinterpret_cast<float4 *>(o + k) = make_float4(fill_of(S, k), fill_of(S, k + 1), fill_of(S, k + 2), fill_of(S, k + 3));
+        } else {
+            for (int k = first; k < S.C; k += lanes) o[k] = fill_of(S, k);
+        }
+        return;
+    }
+    const float *row[8];
+    rows(row);
+    if (S.vec) {
+        for (int k = 4 * first; k < S.C; k += 4 * lanes) {
+            float4 v[8];
+#pragma unroll
+            for (int c = 0; c < 8; ++c) v[c] = *reinterpret_cast<const float4 *>(row[c] + k);
+            *reinterpret_cast<float4 *>(o + k) = blend4(w, v);
+        }
+    } else {
+        for (int k = first; k < S.C; k += lanes) {
+            float v[8];
+#pragma unroll
+            for (int c = 0; c < 8; ++c) v[c] = row[c][k];
+            o[k] = blend(w, v);
+        }
+    }
+}
+
+// ---- backward -----------------------------------------------------------------------------------------------------------------
+struct FaceWeights {
+    float yz[4], xz[4], xy[4];      // products of the two OTHER axes' weights, index = first * 2 + second
+};
+
+__device__ __forceinline__ FaceWeights face_weights(float tx, float ty, float tz)
+{
+    const float ax[2] = {1.0f - tx, tx}, ay[2] = {1.0f - ty, ty}, az[2] = {1.0f - tz, tz};
+    FaceWeights f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        f.yz[j] = ay[j >> 1] * az[j & 1];
+        f.xz[j] = ax[j >> 1] * az[j & 1];
+        f.xy[j] = ax[j >> 1] * ay[j & 1];
+    }
+    return f;
+}
+
+// acc += g * d blend / d (tx, ty, tz) for one channel with corner values v
+__device__ __forceinline__ void add_derivative(const FaceWeights &f, const float (&v)[8], float g, float (&acc)[3])
+{
+    float dx = f.yz[0] * (v[4] - v[0]);
+    dx = fmaf(f.yz[1], v[5] - v[1], dx);
+    dx = fmaf(f.yz[2], v[6] - v[2], dx);
+    dx = fmaf(f.yz[3], v[7] - v[3], dx);
+    float dy = f.xz[0] * (v[2] - v[0]);
+    dy = fmaf(f.xz[1], v[3] - v[1], dy);
+    dy = fmaf(f.xz[2], v[6] - v[4], dy);
+    dy = fmaf(f.xz[3], v[7] - v[5], dy);
+    float dz = f.xy[0] * (v[1] - v[0]);
+    dz = fmaf(f.xy[1], v[3] - v[2], dz);
+    dz = fmaf(f.xy[2], v[5] - v[4], dz);
+    dz = fmaf(f.xy[3], v[7] - v[6], dz);
+    acc[0] = fmaf(g, dx, acc[0]);
+    acc[1] = fmaf(g, dy, acc[1]);
+    acc[2] = fmaf(g, dz, acc[2]);
+}
+
+// S.grad is not null; rows(row) fills the eight corner row pointers of the point's cell
+template <class Rows>
+__device__ __forceinline__ void backward_row(const VolSet &S, int64_t i, const FaceWeights &f, int first, int lanes, float (&acc)[3], Rows rows)
+{
+    const float *g = S.grad + i * S.C;
+    const float *row[8];
+    rows(row);
+    if (S.vec) {
+        for (int k = 4 * first; k < S.C; k += 4 * lanes) {
+            float4 v[8];
+#pragma unroll
+            for (int c = 0; c < 8; ++c) v[c] = *reinterpret_cast<const float4 *>(row[c] + k);
+            const float4 gk = *reinterpret_cast<const float4 *>(g + k);
+            const float a[8] = {v[0].x, v[1].x, v[2].x, v[3].x, v[4].x, v[5].x, v[6].x, v[7].x};
+            const float b[8] = {v[0].y, v[1].y, v[2].y, v[3].y, v[4].y, v[5].y, v[6].y, v[7].y};
+            const float c2[8] = {v[0].z, v[1].z, v[2].z, v[3].z, v[4].z, v[5].z, v[6].z, v[7].z};
+            const float d[8] = {v[0].w, v[1].w, v[2].w, v[3].w, v[4].w, v[5].w, v[6].w, v[7].w};
+            add_derivative(f, a, gk.x, acc);
+            add_derivative(f, b, gk.y, acc);
+            add_derivative(f, c2, gk.z, acc);
+            add_derivative(f, d, gk.w, acc);
+        }
+    } else {
+        for (int k = first; k < S.C; k += lanes) {
+            float v[8];
+#pragma unroll
+            for (int c = 0; c < 8; ++c) v[c] = row[c][k];
+            add_derivative(f, v, g[k], acc);
+        }
+    }
+}
+
+}  // namespace d3f

@@ -943,13 +943,17 @@ class Fusion:
             self._subtract_offsets(out, names, dev)
         return out
 
-    def bake(self, boundaries, step_size, return_names=[]):
+    def bake(self, boundaries, step_size, return_names=[], band=None):
         """eval_grid(boundaries, step_size, return_names) kept as a baked.BakedField: its eval(pts) interpolates that volume
         trilinearly (eight corner rows per point, no projection into the views) and has a closed-form gradient w.r.t. pts.
         The field holds the grid query's tensors and no reference to this object: it keeps answering, unchanged, after update().
-        BakedField.raycast / render march rays through it to the first surface."""
+        BakedField.raycast / render march rays through it to the first surface.
+
+        band (a world length > 0, e.g. 0.005): bake channel rows only for the voxels a cell within `band` of the surface needs
+        (DESIGN.md 15).  dist / valid stay dense; the rows come from one batch_eval of the stored voxel centres, so no
+        [nx, ny, nz, C] array is ever allocated.  Lookups add 'in_band'; outside the band a set reads as its fill row."""
         from .baked import BakedField
-        return BakedField.from_fusion(self, boundaries, step_size, return_names)
+        return BakedField.from_fusion(self, boundaries, step_size, return_names, band=band)
 
     def grid_shell(self, boundaries, step_size, dist_threshold=0.005):
         """Flat indices (ascending) and coordinates of the grid points with valid_mask & |dist| < dist_threshold:

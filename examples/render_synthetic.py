@@ -23,6 +23,7 @@ from d3fields_amd import Fusion, synth     # noqa: E402
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--step", type=float, default=0.004)
+    ap.add_argument("--band", type=float, default=None, help="bake channel rows only within this distance (m) of the surface, e.g. 0.005")
     ap.add_argument("--out", default=".")
     args = ap.parse_args()
     dev = "cuda:0"
@@ -33,7 +34,7 @@ def main():
     f.curr_obs_torch["dino_feats"] = synth.random_map(V, H // 10, W // 10, C, seed=2, device=dev)
     f.H, f.W = H, W
     f.add_projection("pca3", components=torch.randn(3, C, generator=torch.Generator().manual_seed(5)))
-    baked = f.bake(synth.WORK_BOX, args.step, return_names=["pca3"])
+    baked = f.bake(synth.WORK_BOX, args.step, return_names=["pca3"], band=args.band)
     K = sc["K"][0]
     pose = torch.from_numpy(synth.ring_cameras(2 * V, H, W)[1][1])           # on the ring, halfway between cameras 0 and 1
     baked.render(K, pose, H, W, return_names=["pca3"], normals=True)        # warm-up
@@ -45,6 +46,9 @@ def main():
     print("volume %s at %.3f m; %d x %d view: %d of %d pixels hit a surface, depth %.3f .. %.3f m, %.2f ms"
           % (tuple(baked.grid_shape), args.step, W, H, int(hit.sum()), H * W, float(out["depth"][hit].min()), float(out["depth"][hit].max()),
              1e3 * (time.perf_counter() - t0)))
+    if args.band is not None:
+        print("band %.4f m: %.1f %% of the voxels hold rows; %d of the %d hits lie in the band"
+              % (args.band, 100 * baked.stored_fraction, int(out["in_band"].sum()), int(hit.sum())))
     depth, pca = out["depth"].cpu().numpy(), out["pca3"].cpu().numpy()
     os.makedirs(args.out, exist_ok=True)
     np.save(os.path.join(args.out, "render_depth.npy"), depth)

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define D3F_ABI_VERSION 12
+#define D3F_ABI_VERSION 13
 
 #define D3F_OK 0
 #define D3F_ERR_INVALID_ARG (-1)  /* null pointer, negative count, bad enum               */
@@ -404,6 +404,42 @@ int d3f_volume_sample(const d3f_volume *vol, const float *pts, int64_t n, const 
  * lane: no atomics, two runs agree bit for bit. */
 int d3f_volume_sample_backward(const d3f_volume *vol, const float *pts, int64_t n, const d3f_volume_set *sets, int32_t n_sets,
                                const float *grad_dist, const void *const *grad_sets, float *grad_pts, void *stream);
+
+/* (ABI 13) A baked field whose channel rows exist only in a BAND around the surface.  dist, valid and
+ * cell_valid of the d3f_volume stay dense; a set's rows are compacted.  For a world length band > 0 (finite), in fp32:
+ *   seed     a voxel with valid && fabsf(dist) < band (strict; a NaN dist is no seed);
+ *   kept     a cell with cell_valid set and at least one seed among its eight corners: cell_band, one byte per cell [nx-1,ny-1,nz-1];
+ *   stored   a voxel that is a corner of at least one kept cell (so every stored voxel is valid and a kept cell has eight rows);
+ *   slot[q]  the rank of voxel q among the stored voxels in ascending flat index (ix*ny + iy)*nz + iz, -1 if q is not stored: an int32
+ *            volume; M = the number of stored voxels, voxels[M] the inverse list; rows are [M, C] in slot order.
+ * d3f_band_mark writes cell_band_out, slot_out (both complete), voxels_out[0 .. min(M, capacity)) and *count_out = M (ONE device
+ * int64, the true count also when M > capacity: then nothing is written beyond the capacity and the caller re-runs with a
+ * voxels_out of M entries; capacity 0 with voxels_out NULL only counts).  vol->dist and vol->cell_valid are read (vol->valid is not:
+ * a valid cell has eight valid corners; dist of an invalid cell is never read).  Four kernels and the recursive exclusive scan on
+ * `stream`: order-preserving, no atomics, no spinning, two runs give byte-identical output.  workspace: d3f_band_workspace_bytes (the scan's
+ * scratch, about 2 bytes per 1024 voxels; the flags are scanned inside slot_out), 4-byte aligned.  Status errors: the volume checks of
+ * d3f_volume_sample, band not finite or <= 0, capacity < 0, NULL outputs, a short workspace. */
+typedef struct d3f_band {
+    const int32_t *slot;       /* [nx,ny,nz] */
+    const uint8_t *cell_band;  /* [nx-1,ny-1,nz-1] */
+    int64_t n_rows;            /* M, in [0, 2^31 - 1] */
+} d3f_band;
+int64_t d3f_band_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
+int d3f_band_mark(const d3f_volume *vol, float band, uint8_t *cell_band_out, int32_t *slot_out, int32_t *voxels_out, int64_t capacity,
+                  int64_t *count_out, void *workspace, int64_t workspace_bytes, void *stream);
+/* d3f_volume_sample on a banded field: g, the cell, t, the weights, out_dist and out_valid exactly as there, read from the dense
+ * dist; out_in_band[i] = valid && cell_band[cell] (one byte).  sets[s].data holds the COMPACTED rows [n_rows, C], stride_voxel the
+ * row stride: for an in_band point the eight corner rows are data + slot[corner]*stride_voxel (64-bit offsets), run through the same
+ * chain in the same corner order -- the same bits as the dense field gives.  Any other point gets the set's fill row, and no slot or
+ * row is read for it.  n_rows == 0 is legal: slot, cell_band and every data may be NULL, every point gets fill rows and nothing of the
+ * band is dereferenced.  n == 0: D3F_OK, nothing is read.  Same vector / scalar row rule and the same 16-channel boundary between one
+ * lane and sixteen lanes per point as d3f_volume_sample.  slot values are trusted to be < n_rows (d3f_band_mark wrote them). */
+int d3f_band_sample(const d3f_volume *vol, const d3f_band *band, const float *pts, int64_t n, const d3f_volume_set *sets, int32_t n_sets,
+                    float *out_dist, uint8_t *out_valid, uint8_t *out_in_band, void *const *out_sets, void *stream);
+/* d3f_volume_sample_backward on a banded field: the dist term applies to every valid point, a set's term only to in_band points;
+ * no term for the choice of the cell or for the band edge.  No atomics; two runs agree bit for bit. */
+int d3f_band_sample_backward(const d3f_volume *vol, const d3f_band *band, const float *pts, int64_t n, const d3f_volume_set *sets, int32_t n_sets,
+                             const float *grad_dist, const void *const *grad_sets, float *grad_pts, void *stream);
 
 /* (ABI 12) The first surface a ray meets in a baked volume: a fixed-step march through `dist` with one linear interpolation at the
  * sign change.  Everything in fp32.  Ray i is p(t) = o + t*d; d need not be unit.
