@@ -7,7 +7,8 @@
 //                   workgroup) + in-workgroup rank.
 //   nearest_kernel  the two directed nearest-neighbour searches of Fusion.pcd_iou (fusion.py:724-741), which
 //                   the reference does through an [N,M] distance matrix: one lane per query point, the other
-//                   cloud staged through LDS in 256-point tiles, first minimum wins (np.argmin).
+//                   cloud staged through LDS in 256-point tiles; the first minimum of the ROOTED distances wins and the
+//                   first NaN beats every number (np.min / np.argmin; the rule is stated at the kernel).
 #include "d3f_internal.h"
 
 namespace d3f {
@@ -105,6 +106,34 @@ hipError_t launch_backproject(const double *depth, const uint8_t *mask, int H, i
 }
 
 // ---- directed nearest neighbour (fusion.py:731-735): min / first argmin of sqrt((dx*dx + dy*dy) + dz*dz) ----
+// The order is that of the ROOTS, as np.argmin over np.linalg.norm sees them: sqrt is monotone but not injective in floating
+// point (two squares one ulp apart often share a root), so among rows with equal roots the FIRST wins, also when a later
+// one has the smaller square.  The root stays off the per-pair path: only a square below the smallest one seen so far can
+// have a smaller root, so only such a pair takes a root, and it replaces the winner only if that root is strictly smaller.
+// Invariant while no NaN was met: best2 = the smallest square seen, best = sqrt(best2), arg = the first row whose root is best.
+// NaN as in numpy's min / argmin: the first row with a NaN distance wins and nothing replaces it (best2 = -inf closes the
+// gate for every later square, best != best for every later NaN).
+constexpr int kNearestGroup = 8;       // rows of b whose squares are formed together before one test whether any of them matters
+
+__device__ __forceinline__ double nearest_square(double ax, double ay, double az, const double *__restrict__ p)
+{
+    const double dx = ax - p[0], dy = ay - p[1], dz = az - p[2];
+    return (dx * dx + dy * dy) + dz * dz;
+}
+
+__device__ __forceinline__ void nearest_visit(double d2, int64_t row, double &best2, double &best, int64_t &arg)
+{
+    if (d2 >= best2) return;                                 // what passes is a smaller square, or a NaN
+    const double r = sqrt(d2);
+    if (r != r) {
+        if (best == best) { best = r; arg = row; }
+        best2 = -INFINITY;
+    } else {
+        if (r < best) { best = r; arg = row; }
+        best2 = d2;
+    }
+}
+
 __global__ __launch_bounds__(kBlock) void nearest_kernel(const double *__restrict__ a, int64_t na, const double *__restrict__ b,
                                                         int64_t nb, double *__restrict__ min_dist, int64_t *__restrict__ argmin)
 {
@@ -112,20 +141,32 @@ __global__ __launch_bounds__(kBlock) void nearest_kernel(const double *__restric
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     const bool live = i < na;
     const double ax = live ? a[i * 3 + 0] : 0.0, ay = live ? a[i * 3 + 1] : 0.0, az = live ? a[i * 3 + 2] : 0.0;
-    double best = INFINITY;
+    double best2 = INFINITY, best = INFINITY;
     int64_t arg = 0;
     for (int64_t j0 = 0; j0 < nb; j0 += kBlock) {
-        const int64_t cnt = min((int64_t)kBlock, nb - j0);
+        const int cnt = (int)min((int64_t)kBlock, nb - j0);
         __syncthreads();
         for (int t = threadIdx.x; t < cnt * 3; t += kBlock) tile[t] = b[j0 * 3 + t];
         __syncthreads();
-        for (int t = 0; t < cnt; ++t) {
-            const double dx = ax - tile[t * 3 + 0], dy = ay - tile[t * 3 + 1], dz = az - tile[t * 3 + 2];
-            const double d2 = (dx * dx + dy * dy) + dz * dz;
-            if (d2 < best) { best = d2; arg = j0 + t; }      // sqrt is monotone: compare squares, root once
+        // rows are visited in order, one by one; a group whose squares all fail the gate as it stands before the group is
+        // skipped whole (the gate only tightens, so none of them would pass it later either)
+        int t = 0;
+        for (; t + kNearestGroup <= cnt; t += kNearestGroup) {
+            double d2[kNearestGroup];
+            bool any = false;
+#pragma unroll
+            for (int u = 0; u < kNearestGroup; ++u) {
+                d2[u] = nearest_square(ax, ay, az, tile + (t + u) * 3);
+                any |= !(d2[u] >= best2);
+            }
+            if (any) {
+#pragma unroll
+                for (int u = 0; u < kNearestGroup; ++u) nearest_visit(d2[u], j0 + t + u, best2, best, arg);
+            }
         }
+        for (; t < cnt; ++t) nearest_visit(nearest_square(ax, ay, az, tile + t * 3), j0 + t, best2, best, arg);
     }
-    if (live) { min_dist[i] = sqrt(best); argmin[i] = arg; }
+    if (live) { min_dist[i] = best; argmin[i] = arg; }
 }
 
 hipError_t launch_nearest(const double *a, int64_t na, const double *b, int64_t nb, double *min_dist, int64_t *argmin, hipStream_t s)

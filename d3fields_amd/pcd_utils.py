@@ -96,6 +96,9 @@ def voxel_downsample(pcd, voxel_size, pcd_color=None):
     """Reference utils/draw_utils.py:318-323 (open3d's voxel_down_sample): one point (and colour) per occupied voxel of
     side voxel_size anchored at min_bound - voxel_size/2 = the mean of the voxel's points.  Runs as d3f_voxel_downsample
     on the device: the same SET as open3d's to ~1e-14 m, in ascending voxel order (open3d: the order of its hash map).
+    Limit: the device packs a voxel index into 21 bits per axis, so the cloud may span at most 2 097 150 voxel sides on any
+    axis (max - min <= 2097150 * voxel_size).  Beyond that the index is clamped to 2^21 - 1 and the voxels past it are merged
+    into one; nothing is raised.
     Returns (points, colors) or points, like the reference."""
     pts_np = np.ascontiguousarray(pcd, dtype=np.float64).reshape(-1, 3)
     n = pts_np.shape[0]

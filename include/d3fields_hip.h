@@ -500,7 +500,9 @@ int d3f_backproject_view(const double *depth, const uint8_t *mask, int32_t H, in
                          int32_t *out_pixel, int64_t *count_out, void *workspace, void *stream);
 
 /* One direction of Fusion.pcd_iou's nearest-neighbour search (fusion.py:731-735): for every point of a[na,3]
- * the Euclidean distance to, and index of, its nearest point in b[nb,3] (first minimum wins), fp64. */
+ * the Euclidean distance to, and index of, its nearest point in b[nb,3], fp64, with np.min / np.argmin's rules: the first
+ * minimum of the ROOTED distances wins (rows whose squares differ but whose roots are equal tie), and a NaN distance beats
+ * every number (min_dist NaN, argmin the first such row). */
 int d3f_pcd_nearest(const double *a, int64_t na, const double *b, int64_t nb, double *min_dist, int64_t *argmin,
                     void *stream);
 
