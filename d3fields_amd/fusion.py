@@ -259,6 +259,7 @@ class Fusion:
         self._pending = []                      #      query of that size said; _pending: probes still in flight
         self._pinned = []                       # reusable pinned host buffers for the probe results
         self._last_plan = None
+        self._last_lanes = None
         self.record_plans = False               # last_plan(): query the launch plan of every eval (bench.py, tests)
         self.detect_lattice = True              # probe new query tensors for create_init_grid's layout (brick walk, no sort)
         self._projections = {}                  # add_projection: name -> linear head (source key, W [k,C] fp32, b = mean W^T [k] fp32)
@@ -676,6 +677,11 @@ class Fusion:
         points were ordered -- from d3f_eval_plan_query on the same shapes and flags."""
         return self._last_plan
 
+    def last_lane_mapping(self):
+        """The phase-B lane mapping of the same launch, per queried map in the caller's order: vector_floats (channels per
+        load), lanes_per_point, vectors_per_lane (negative: load-use per vector) -- d3f_eval_plan's fields of these names."""
+        return self._last_lanes
+
     def _record_plan(self, views, n, maps, n_maps, flags, have_ws, want_inter, lattice):
         plan = _lib.EvalPlan()
         if lattice is not None:
@@ -699,6 +705,7 @@ class Fusion:
         # (kernel: the instance's entry point and template arguments, named by the library -- csrc/fuse_<family>.hip)
         self._last_plan = {"kernel": plan.kernel.decode(), "tile_points": int(plan.tile_points), "point_order": order,
                            "workgroups": int(plan.workgroups), "lattice": lattice, "gated_window": bool(plan.gated_window), "family": family}
+        self._last_lanes = {k: [int(getattr(plan, k)[s]) for s in range(n_maps)] for k in ("vector_floats", "lanes_per_point", "vectors_per_lane")}
         if plan.gated_window:
             # a cloud on the gated pair of launches (ABI 5): the fields above describe the cell-run side; the window side is the
             # sparse-pool window kernel on 64-point tiles of the same order.  last_gate() says which one ran.

@@ -25,6 +25,25 @@ def scaled_map(V, fh, fw, C, seed, cancel=True):
     return m.contiguous()
 
 
+def onehot_map(V, fh, fw, NI, seed, block=16):
+    """[V,fh,fw,NI] float32 one-hot instance mask, constant over block x block texels: an instance covers a region, so away
+    from the region borders the four corners of a sample agree (the fused value is then the normalised weight sum or 0);
+    half the regions belong to instance 0, so that the views of a point often agree as well."""
+    g = torch.Generator().manual_seed(seed)
+    shape = (V, (fh + block - 1) // block, (fw + block - 1) // block)
+    idx = torch.randint(0, NI, shape, generator=g)
+    idx = torch.where(torch.rand(shape, generator=g) < 0.5, torch.zeros_like(idx), idx)      # instance 0 is large: views often agree
+    idx = idx.repeat_interleave(block, 1).repeat_interleave(block, 2)[:, :fh, :fw]
+    return torch.nn.functional.one_hot(idx, NI).float().contiguous()
+
+
+def companions(V, H, W, thin, seed):
+    """The thin maps that ride along with a wide one, at full resolution (what the product queries: features + mask):
+    'mask' = 8-channel one-hot, 'color' = 3 channels of scaled_map."""
+    made = {"mask": lambda: onehot_map(V, H, W, 8, seed + 50), "color": lambda: scaled_map(V, H, W, 3, seed + 51)}
+    return {k: made[k]() for k in thin}
+
+
 def surface_points(obs, H, W, n, mu, seed):
     """[n,3] float32 points placed on pixel rays of random views at distances s in front of the ray-cast surface, so that the
     weight exp(min(mu - s, 0) / mu) runs from 1 through 1e-6 and 1e-30 into float32's subnormal range and to zero."""
@@ -63,14 +82,17 @@ def _mix(obs, H, W, n_cloud, n_surf, mu, seed, scale=1.0):
 
 def _grid():
     from d3fields_amd import create_init_grid, synth
-    return create_init_grid(synth.WORK_BOX, 0.0107)[0]                            # 74 x 65 x 20 points, a lattice
+    return create_init_grid(synth.WORK_BOX, 0.0107)[0]                            # 75 x 66 x 21 points, a lattice
 
 
 # Every case: name -> builder.  A builder returns dict(obs, H, W, mu, maps {name: [V,fh,fw,C] cpu tensor}, names (queried
 # maps, wide first), pts [N,3] cpu, edge (rows always compared), and how the GPU test calls it: call ("eval" /
 # "batch_eval"), flags (tuning-flag names of d3fields_amd._lib), reorder (Fusion.reorder_points), reference_rounding,
 # expect (prefix of last_plan()["kernel"]; for a gated cloud the side that ran), rows (sample size on big batches)).
-def _direct(V=4, C=384, cs=(), f16=False, mu=0.005, n=3000, seed=1, **kw):
+# The thin cases (THIN_CASES) add: thin_form ("parallel": every thin map of the case meets thin_map()'s condition of
+# csrc/fuse_common.h and is gathered with the views across lanes; "outside": none does), base (the earlier case it was derived
+# from: its share of rows left out / non-finite bounds the new case's).
+def _direct(V=4, C=384, cs=(), f16=False, mu=0.005, n=3000, seed=1, thin=(), **kw):
     H, W = 96, 128
     obs = scene(V, H, W)
     maps = {"wide": scaled_map(V, 12, 16, C, seed)}
@@ -78,6 +100,7 @@ def _direct(V=4, C=384, cs=(), f16=False, mu=0.005, n=3000, seed=1, **kw):
         maps["m%d" % j] = scaled_map(V, 12, 16, c, seed + 1 + j)
     if f16:
         maps = {k: (m / m.abs().amax((0, 1, 2)).clamp_min(1e-30) * 100.0).half() for k, m in maps.items()}
+    maps.update(companions(V, H, W, thin, seed))
     pts, edge = _mix(obs, H, W, n // 2, n - n // 2, mu, seed + 10)
     d = dict(obs=obs, H=H, W=W, mu=mu, maps=maps, names=list(maps), pts=pts, edge=edge, call="eval", flags=(), reorder=True,
              reference_rounding=False, expect="fused_eval_f16_kernel<0>" if f16 else "fused_eval_kernel<0>", rows=None)
@@ -85,13 +108,14 @@ def _direct(V=4, C=384, cs=(), f16=False, mu=0.005, n=3000, seed=1, **kw):
     return d
 
 
-def _edges(mu=G.MU_EDGE):
+def _edges(mu=G.MU_EDGE, thin=False):
     """grad_cases' edge scene: dyadic cameras, points on texel lines / centres and on the border, a 9 x 17 patch map, a
-    full-resolution one, 1 x W and H x 1 maps."""
+    full-resolution one, 1 x W and H x 1 maps (thin: the same four shapes with 3, 8, 2 and 1 channels)."""
     obs = G.edge_scene()
     pts = G.edge_points(3000)
-    maps = {"patch": scaled_map(4, 9, 17, 96, 61), "full": scaled_map(4, G.EH, G.EW, 72, 62),
-            "row": scaled_map(4, 1, 16, 80, 63, cancel=False), "col": scaled_map(4, 12, 1, 80, 64, cancel=False)}
+    C = (3, 8, 2, 1) if thin else (96, 72, 80, 80)
+    maps = {"patch": scaled_map(4, 9, 17, C[0], 61), "full": scaled_map(4, G.EH, G.EW, C[1], 62),
+            "row": scaled_map(4, 1, 16, C[2], 63, cancel=False), "col": scaled_map(4, 12, 1, C[3], 64, cancel=False)}
     return dict(obs=obs, H=G.EH, W=G.EW, mu=mu, maps=maps, names=list(maps), pts=pts, edge=torch.arange(270), call="eval",
                 flags=(), reorder=True, reference_rounding=False, expect="fused_eval_kernel<0>", rows=None)
 
@@ -112,11 +136,32 @@ def _wide():
                 reference_rounding=False, expect="fused_eval_wide_kernel<0>", rows=None)
 
 
-def _big(V, H, W, fhw, C, points, mu, expect, seed, n=0, flags=(), call="batch_eval", rows=20000, f16=False, kind="smooth"):
+def _thin(V, C, n, seed, call="eval", f16=False, onehot=False, view=None, mu=0.005, **kw):
+    """A thin map (<= 256 bytes per texel) queried alone: full resolution, points on the surface and far off it.  view =
+    (first channel, channels of the tensor): the map is that channel range of a wider tensor (texel stride > C; a first
+    channel that is no multiple of 4 leaves the pointer off the 16-byte boundary: scalar lanes)."""
+    H, W = 96, 128
+    obs = scene(V, H, W)
+    lo, total = view if view else (0, C)
+    m = onehot_map(V, H, W, total, seed, block=8) if onehot else scaled_map(V, H, W, total, seed)
+    if f16:
+        m = (m / m.abs().amax((0, 1, 2)).clamp_min(1e-30) * 100.0).half()
+    m = m[..., lo:lo + C]
+    pts, edge = _mix(obs, H, W, n // 2, n - n // 2, mu, seed + 10)
+    d = dict(obs=obs, H=H, W=W, mu=mu, maps={"thin": m}, names=["thin"], pts=pts, edge=edge, call=call, flags=(), reorder=True,
+             reference_rounding=False, expect="fused_eval_f16_kernel<0>" if f16 else "fused_eval_kernel<0>", rows=None,
+             base="direct V4 C384")
+    d.update(kw)
+    return d
+
+
+def _big(V, H, W, fhw, C, points, mu, expect, seed, n=0, flags=(), call="batch_eval", rows=20000, f16=False, kind="smooth", thin=()):
     obs = scene(V, H, W, kind)
     m = scaled_map(V, fhw[0], fhw[1], C, seed)
     if f16:
         m = (m / m.abs().amax((0, 1, 2)).clamp_min(1e-30) * 100.0).half()
+    maps = {"feats": m}
+    maps.update(companions(V, H, W, thin, seed))
     if points == "grid":
         pts, edge = _grid(), torch.zeros(0, dtype=torch.long)
     else:
@@ -127,7 +172,7 @@ def _big(V, H, W, fhw, C, points, mu, expect, seed, n=0, flags=(), call="batch_e
         surf = surface_points(obs, H, W, 3000, mu, seed + 2)
         pts = torch.cat((pts[:n - 3000], surf))                 # the controlled-distance rows at the end
         edge = torch.arange(n - 3000, n)
-    return dict(obs=obs, H=H, W=W, mu=mu, maps={"feats": m}, names=["feats"], pts=pts.contiguous(), edge=edge, call=call,
+    return dict(obs=obs, H=H, W=W, mu=mu, maps=maps, names=list(maps), pts=pts.contiguous(), edge=edge, call=call,
                 flags=tuple(flags), reorder=True, reference_rounding=False, expect=expect, rows=rows)
 
 
@@ -144,25 +189,109 @@ CASES = {
     "strict: reference rounding": lambda: _direct(V=5, seed=8, reference_rounding=True),
     "batch_eval, reorder off": lambda: _direct(V=3, C=256, seed=9, n=4000, call="batch_eval", reorder=False),
     # the big-batch families (a seeded sample of rows plus the controlled-distance rows)
-    "window lattice": lambda: _big(4, 480, 640, (48, 64), 384, "grid", 0.005, "fused_eval_window_kernel", 21),
-    "window cloud, window side": lambda: _big(4, 480, 640, (48, 64), 384, "dense cloud", 0.005, "fused_eval_window_kernel", 22,
-                                              n=300001, flags=("TUNE_WINDOW_SIDE",)),
-    "window cloud, cell-run side": lambda: _big(4, 480, 640, (48, 64), 384, "dense cloud", 0.005, "fused_eval_runs_kernel", 23,
-                                                n=300001, flags=("TUNE_NO_WINDOW_GATE",)),
-    "cell runs V8 C512": lambda: _big(8, 480, 640, (24, 32), 512, "cloud", 0.02, "fused_eval_runs_kernel", 24, n=150001),
-    "sliced lattice": lambda: _big(4, 192, 256, (192, 256), 384, "grid", 0.005, "fused_eval_sliced_kernel", 25),
+    "window lattice": lambda thin=(): _big(4, 480, 640, (48, 64), 384, "grid", 0.005, "fused_eval_window_kernel", 21, thin=thin),
+    "window cloud, window side": lambda thin=(): _big(4, 480, 640, (48, 64), 384, "dense cloud", 0.005, "fused_eval_window_kernel", 22,
+                                              n=300001, flags=("TUNE_WINDOW_SIDE",), thin=thin),
+    "window cloud, cell-run side": lambda thin=(): _big(4, 480, 640, (48, 64), 384, "dense cloud", 0.005, "fused_eval_runs_kernel", 23,
+                                                n=300001, flags=("TUNE_NO_WINDOW_GATE",), thin=thin),
+    "cell runs V8 C512": lambda thin=(): _big(8, 480, 640, (24, 32), 512, "cloud", 0.02, "fused_eval_runs_kernel", 24, n=150001, thin=thin),
+    "sliced lattice": lambda thin=(): _big(4, 192, 256, (192, 256), 384, "grid", 0.005, "fused_eval_sliced_kernel", 25, thin=thin),
     "sliced cloud, eval, reorder off": lambda: dict(_big(4, 96, 128, (96, 128), 384, "cloud", 0.005, "fused_eval_kernel<0>", 26,
                                                          n=70001, call="eval"), reorder=False),
-    "sliced cloud": lambda: _big(4, 96, 128, (96, 128), 384, "cloud", 0.005, "fused_eval_sliced_kernel", 26, n=70001),
+    "sliced cloud": lambda thin=(): _big(4, 96, 128, (96, 128), 384, "cloud", 0.005, "fused_eval_sliced_kernel", 26, n=70001, thin=thin),
     "sliced lattice f16": lambda: _big(4, 192, 256, (192, 256), 384, "grid", 0.005, "fused_eval_sliced_kernel", 27, f16=True),
     "window lattice f16": lambda: _big(3, 480, 640, (24, 32), 256, "grid", 0.005, "fused_eval_window_kernel", 28, f16=True),
-    "rows V8 lattice": lambda: _big(8, 480, 640, (36, 64), 1024, "grid", 0.005, "fused_eval_rows_kernel", 31, rows=5000),
-    "rows V8 cloud": lambda: _big(8, 480, 640, (36, 64), 1024, "cloud", 0.02, "fused_eval_rows_kernel", 32, n=150001, rows=5000),
+    "rows V8 lattice": lambda thin=(): _big(8, 480, 640, (36, 64), 1024, "grid", 0.005, "fused_eval_rows_kernel", 31, rows=5000, thin=thin),
+    "rows V8 cloud": lambda thin=(): _big(8, 480, 640, (36, 64), 1024, "cloud", 0.02, "fused_eval_rows_kernel", 32, n=150001, rows=5000, thin=thin),
     "rows V4 sorted cloud": lambda: _big(4, 480, 640, (24, 32), 1024, "sorted cloud", 0.005, "fused_eval_rows_kernel", 33, n=100000),
     "rows V5 lattice": lambda: _big(5, 480, 640, (24, 32), 1024, "grid", 0.005, "fused_eval_rows_kernel", 34, rows=10000),
     "rows V1 sorted cloud eval": lambda: _big(1, 480, 640, (48, 64), 1024, "sorted cloud", 0.005, "fused_eval_rows_kernel", 35,
                                              n=66000, call="eval"),
 }
+
+
+def _beside(base, thin):
+    """The earlier case `base` with thin companions beside its wide map (same points, same sample of rows, same kernel)."""
+    return lambda: dict(CASES[base](thin=thin), thin_form="parallel", base=base)
+
+
+# The thin family (<= 256 bytes per texel: the instance mask, colours, fp16 maps of up to 128 channels), which keeps the
+# reference's operation order in every kernel.  Also part of CASES.
+THIN_CASES = {
+    # thin alone, the views in parallel across lanes (gather_map_thin): vector widths 4 / 2 / 1, 1 / 2 / 4 lanes per point, 2..8
+    # views (3 and 5 leave view lanes idle), N no multiple of the points per workgroup, N = 1 and 17
+    "thin V2 C3": lambda: _thin(2, 3, 3001, 101, thin_form="parallel"),
+    # (five scalar vectors get 8 lanes per point from the planner -- one pass --, so this one is view-sequential; V3 C6 is the
+    #  nearest shape that keeps three views in the parallel form)
+    "thin V3 C5": lambda: _thin(3, 5, 3003, 102, call="batch_eval", thin_form="outside"),
+    "thin V3 C6": lambda: _thin(3, 6, 3003, 112, call="batch_eval", thin_form="parallel"),
+    "thin V4 C8": lambda: _thin(4, 8, 3999, 103, thin_form="parallel"),
+    "thin V4 C8 one-hot, batch_eval": lambda: _thin(4, 8, 3001, 113, call="batch_eval", onehot=True, thin_form="parallel"),
+    "thin V5 C1": lambda: _thin(5, 1, 3005, 104, call="batch_eval", thin_form="parallel"),
+    "thin V8 C16": lambda: _thin(8, 16, 3007, 105, mu=0.02, thin_form="parallel"),
+    "thin V4 C12": lambda: _thin(4, 12, 17, 106, call="batch_eval", thin_form="parallel"),
+    "thin V8 C2": lambda: _thin(8, 2, 1, 107, mu=0.02, thin_form="parallel"),
+    "thin V8 C2, batch_eval": lambda: _thin(8, 2, 3011, 117, call="batch_eval", mu=0.02, thin_form="parallel"),
+    "thin V4 C8 in a 16-channel tensor": lambda: _thin(4, 8, 3001, 108, view=(4, 16), thin_form="parallel"),
+    "thin edges": lambda: dict(_edges(thin=True), thin_form="parallel", base="direct edges"),
+    # thin alone, outside that form: the view-sequential gather_map
+    "thin V1 C8": lambda: _thin(1, 8, 3001, 121, thin_form="outside"),
+    "thin V9 C8": lambda: _thin(9, 8, 3001, 122, mu=0.02, call="batch_eval", thin_form="outside"),
+    "thin V4 C17": lambda: _thin(4, 17, 3001, 123, thin_form="outside"),
+    "thin V4 C33": lambda: _thin(4, 33, 3001, 124, call="batch_eval", thin_form="outside"),
+    "thin V4 C64": lambda: _thin(4, 64, 3001, 125, thin_form="outside"),
+    "thin f16 V4 C8": lambda: _thin(4, 8, 3001, 126, f16=True, thin_form="outside", base="direct f16 C129 + C128"),
+    "thin f16 V4 C24": lambda: _thin(4, 24, 3001, 127, f16=True, call="batch_eval", thin_form="outside", base="direct f16 C129 + C128"),
+    "thin f16 V4 C127": lambda: _thin(4, 127, 3001, 128, f16=True, thin_form="outside", base="direct f16 C129 + C128"),
+    "thin f16 V4 C128": lambda: _thin(4, 128, 3001, 129, f16=True, thin_form="outside", base="direct f16 C129 + C128"),
+    "thin channel-range view C20 of 32": lambda: _thin(4, 20, 3001, 130, view=(4, 32), thin_form="outside", base="direct channel-range view"),
+    "thin C8 off by 4 bytes": lambda: _thin(4, 8, 3001, 131, view=(1, 12), thin_form="outside", base="direct channel-range view"),
+    # reference_rounding: thin_max_views is 0, every point strict
+    "strict: reference rounding, thin alone": lambda: _thin(4, 8, 3001, 132, reference_rounding=True, thin_form="outside",
+                                                            base="strict: reference rounding"),
+    "strict: reference rounding + mask + color": lambda: dict(_direct(V=5, seed=8, reference_rounding=True, thin=("mask", "color")),
+                                                              thin_form="outside", base="strict: reference rounding"),
+    # thin beside wide: once per big-batch family, an 8-channel one-hot mask (and once a 3-channel colour map)
+    "window lattice + mask + color": _beside("window lattice", ("mask", "color")),
+    "window cloud, window side + mask": _beside("window cloud, window side", ("mask",)),
+    "window cloud, cell-run side + mask": _beside("window cloud, cell-run side", ("mask",)),
+    "cell runs V8 C512 + mask": _beside("cell runs V8 C512", ("mask",)),
+    "sliced lattice + mask": _beside("sliced lattice", ("mask",)),
+    "sliced cloud + mask": _beside("sliced cloud", ("mask",)),
+    "rows V8 lattice + mask": _beside("rows V8 lattice", ("mask",)),
+    "rows V8 cloud + mask": _beside("rows V8 cloud", ("mask",)),
+}
+CASES.update(THIN_CASES)
+# the big-batch cases a thin map rides along in (each must be seen with a companion): lattice and cloud of every family
+BESIDE_BASES = ("window lattice", "window cloud, window side", "window cloud, cell-run side", "cell runs V8 C512", "sliced lattice",
+                "sliced cloud", "rows V8 lattice", "rows V8 cloud")
+
+
+def ordered_names():
+    """The cases, each one with thin companions right behind the case it was derived from (the two share the wide map's
+    float64 reference: field_ref.field64_shared)."""
+    beside = {}
+    for k in CASES:
+        if k in THIN_CASES and " + " in k:
+            beside.setdefault(k.split(" + ")[0], []).append(k)
+    rest = [k for k in CASES if not any(k in v for v in beside.values())]
+    return [n for k in rest for n in [k] + beside.get(k, [])]
+
+
+def thin_names(case):
+    """The queried maps of the thin family (<= 256 bytes per texel)."""
+    return [k for k in case["names"] if case["maps"][k].shape[3] * case["maps"][k].element_size() <= 256]
+
+
+def views_in_parallel(case, k, plan):
+    """thin_map() of csrc/fuse_common.h for the queried map k, recomputed from the lane mapping the plan recorded
+    (Fusion.last_lane_mapping()): one vector per lane, at most 4 lanes per point that hold every vector of a texel, 2..8 views (none
+    under reference_rounding: thin_max_views is 0 there); fp16 maps never take that form (fuse_body.h: gather_map_half_u)."""
+    i, m = case["names"].index(k), case["maps"][k]
+    vw, lanes, per_lane = plan["vector_floats"][i], plan["lanes_per_point"][i], plan["vectors_per_lane"][i]
+    max_views = 0 if case["reference_rounding"] or "TUNE_DIRECT_GATHER" in case["flags"] else 8
+    return bool(m.dtype == torch.float32 and per_lane == 1 and lanes <= 4 and m.shape[3] // vw <= lanes and 2 <= m.shape[0] <= max_views)
+
 
 # what every query with a wide map can be routed to (fusion.py: Fusion._record_plan)
 FAMILIES = ("fused_eval_kernel<0>", "fused_eval_wide_kernel<0>", "fused_eval_f16_kernel<0>", "fused_eval_window_kernel",
@@ -179,12 +308,19 @@ def sample_rows(case, n=None):
     return torch.unique(torch.cat((pick, case["edge"])))
 
 
-def poison(case, points=True):
-    """Non-finite inputs for the strict path: a NaN and an Inf texel in the first map and (points) NaN / Inf query points."""
-    m = case["maps"][case["names"][0]].clone()
+def poison(case, points=True, name=None):
+    """Non-finite inputs for the strict path: a NaN and an Inf texel in the first map -- or NaN and Inf texels spread over
+    the (thin, full-resolution) map `name` -- and (points) NaN / Inf query points."""
+    thin = name is not None
+    name = case["names"][0] if name is None else name
+    m = case["maps"][name].clone()
     m[0, 1, 1, 0] = float("nan")
     m[-1, m.shape[1] // 2, m.shape[2] // 2, m.shape[3] - 1] = float("inf")
-    case["maps"][case["names"][0]] = m
+    if thin:
+        # a full-resolution map: one texel is a pixel, which few points see -- one in every 8 x 8 texels
+        m[0, 1::8, 1::8, 0] = float("nan")
+        m[-1, 5::8, 5::8, m.shape[3] - 1] = float("inf")
+    case["maps"][name] = m
     if not points:
         return case
     p = case["pts"].clone()

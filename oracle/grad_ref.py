@@ -119,9 +119,11 @@ def _field64(obs, p64, dec, H, W, mu, maps, mode, sl):
     out = {"dist": torch.where(empty, torch.full_like(dist, 1e3), dist)}
     V = M.shape[0]
     vv = torch.arange(V)[:, None].expand(V, n)
+    samples = []                                                                  # per map [V,n,C]: the '<k>_inter' rows
     for k, m in enumerate(maps):
         if m is None:
             out["map%d" % k] = None
+            samples.append(None)
             continue
         c = dec["cells"][k]
         fh, fw = int(m.shape[1]), int(m.shape[2])
@@ -140,7 +142,8 @@ def _field64(obs, p64, dec, H, W, mu, maps, mode, sl):
             per_view = per_view + torch.where(inb[..., None], val * wts[q][..., None], torch.zeros_like(val))
         fused = (per_view * livef[..., None] * weight[..., None]).sum(0) / (count[:, None] + 1e-6)
         out["map%d" % k] = torch.where(empty[:, None], torch.zeros_like(fused), fused)
-    return out, dict(M=M, z=z, uvx=uvx, uvy=uvy, weight=weight, livef=livef, count=count, empty=empty)
+        samples.append(per_view)
+    return out, dict(M=M, z=z, uvx=uvx, uvy=uvy, weight=weight, livef=livef, count=count, empty=empty, samples=samples)
 
 
 def corner_terms(m, c, sl, aux, H, W, vv):

@@ -2,7 +2,8 @@
 golden scenes and the batch_eval sub-sample), the calibration of field_ref.TOL on the float32 torch port and the C oracle
 over the cases of tests/test_gpu_field_ref.py (oracle/field_cases.py), and mutants of the port -- a dropped low-weight
 view, a small channel off by 1e-4, a reweighted small corner, a reciprocal 64 ulp off -- that the norm-wise rel_err
-accepts and field_ref.check rejects."""
+accepts and field_ref.check rejects.  The thin family (masks, colours: oracle/field_cases.py THIN_CASES) has mutants of
+its own: the ways a views-across-lanes gather goes wrong (test_thin_mutants_fail_the_pin lists them)."""
 import numpy as np
 import torch
 
@@ -52,14 +53,22 @@ def test_float32_port_and_oracle_within_bound_and_tol_calibrated():
     """The float32 torch port and the C oracle meet |got - f64| <= TOL * scale on 2000 rows of every case (plus its
     controlled-distance rows) and on the non-finite variants; TOL is a few times their worst ratio (PORT_WORST)."""
     worst = 0.0
-    for name, build in FC.CASES.items():
+    shares = {}                     # case -> (share of rows the GPU test's sample leaves out, share of non-finite reference rows)
+    worst_thin = 0.0                # ... over the thin maps of the thin cases (noted beside field_ref.PORT_WORST)
+    print("\nworst |float32 port or C oracle - f64| / scale per case (TOL %.3g): all maps, thin maps; rows left out / non-finite:" % R.TOL)
+    for name in FC.ordered_names():
         for bad in (False, True) if name == "direct V4 C384" else (False,):
-            case = build()
+            case = FC.CASES[name]()
             if bad:
                 FC.poison(case)
             rows = FC.sample_rows(case, 2000)
             maps = [case["maps"][k] for k in case["names"]]
-            vals, scales = R.field64(case["obs"], case["pts"], case["H"], case["W"], case["mu"], maps, rows=rows)
+            vals, scales = R.field64_shared(case["obs"], case["pts"], case["H"], case["W"], case["mu"], maps, rows=rows)
+            case_worst, thin_worst = 0.0, 0.0
+            if not bad:
+                N = case["pts"].shape[0]
+                shares[name] = (1.0 - FC.sample_rows(case).numel() / N,
+                                float(torch.stack([~torch.isfinite(v).all(1) for v in vals]).any(0).double().mean()))
             port = _port(case, rows)
             ref = O.eval_field(case["obs"]["depth"], case["obs"]["K"], case["obs"]["pose"], case["pts"][rows].numpy(),
                                [m.float().numpy() for m in maps], mu=case["mu"])
@@ -67,10 +76,22 @@ def test_float32_port_and_oracle_within_bound_and_tol_calibrated():
                 for tag, got in (("port", port[k]), ("oracle", torch.from_numpy(ref["sets"][i]))):
                     ok, w, msg = R.check(got, vals[i], scales[i])
                     assert ok, "%s%s / %s / %s: %s" % (name, " (non-finite)" if bad else "", k, tag, msg)
-                    worst = max(worst, w)
+                    case_worst = max(case_worst, w)
+                    if k in FC.thin_names(case):
+                        thin_worst = max(thin_worst, w)
+            worst = max(worst, case_worst)
             if bad:
                 assert bool(torch.isnan(vals[0]).any())
+                continue
+            print("  %-46s %-9.3g %-9s %.4f / %.4f" % (name, case_worst, "%.3g" % thin_worst if FC.thin_names(case) else "-", shares[name][0], shares[name][1]))
+            if name in FC.THIN_CASES:
+                worst_thin = max(worst_thin, thin_worst)
+                # a thin case compares no smaller a share of its rows than the case it was derived from
+                assert shares[name][0] <= shares[case["base"]][0] and shares[name][1] <= shares[case["base"]][1], (name, shares[name], shares[case["base"]])
     assert worst <= 1.5 * R.PORT_WORST, "port / oracle worst ratio %.3g: re-measure PORT_WORST" % worst
+    # the bound is attainable for the thin family before any GPU run (the figures beside field_ref.PORT_WORST)
+    print("  thin maps of the thin cases: worst %.3g" % worst_thin)
+    assert 0.0 < worst_thin <= worst
     assert 2.0 * worst <= R.TOL <= 10.0 * max(worst, R.PORT_WORST), "TOL %.3g vs worst %.3g" % (R.TOL, worst)
 
 
@@ -150,3 +171,93 @@ def test_mutants_pass_rel_err_and_fail_the_pin():
         assert rel_err(got.numpy(), base.numpy()) <= 1e-5, "%s: rel_err should accept it" % tag
         ok, w, msg = R.check(got, f64, sc)
         assert not ok, "%s: field_ref.check accepts it (worst ratio %.3g)" % (tag, w)
+
+
+# ---- the thin family: the ways a views-across-lanes gather goes wrong -----------------------------------------------------------
+def _thin_mutants(case):
+    """name -> the float32 port with one defect of gather_map_thin (csrc/fuse_common.h) built in."""
+    m = case["maps"][case["names"][0]].float()
+    per_view, livef, weight = _parts(case)
+    V, N, C = per_view.shape
+    count = livef.sum(0)
+
+    def fuse(term):
+        fused = term.sum(0) / (count.unsqueeze(-1) + 1e-6)
+        fused[count == 0] = 0.0
+        return fused
+
+    term = per_view * livef.unsqueeze(-1) * weight.unsqueeze(-1)
+    out = {"port": fuse(term)}
+    # 1. one view's term read from the next point's lane group: on the last, ragged group of 8 points (the last two rows where
+    #    that group is a single point) view 1's terms move up by one point
+    last = N - (N - 1) // 8 * 8
+    lo = N - max(last, 2)
+    if lo >= 0:
+        t = term.clone()
+        t[1, lo:] = term[1, lo:].roll(-1, 0)
+        out["1 a view read from the next point's lanes"] = fuse(t)
+    # 2. view V - 1 left out of the ordered sum
+    t = term.clone()
+    t[V - 1] = 0.0
+    out["2 view V-1 dropped"] = fuse(t)
+    # 3. min(g, cvec - 1) replaced by g: the last vector read past C, i.e. channel C - 1 taken from what follows the texel
+    #    in memory, channel 0 of the next texel
+    m2 = m.clone()
+    flat = torch.cat((m.reshape(V, -1)[:, C::C], torch.zeros(V, 1)), 1)
+    m2[..., C - 1] = flat.reshape(V, m.shape[1], m.shape[2])
+    pv2, _, _ = _parts(dict(case, maps={case["names"][0]: m2}))
+    out["3 last vector read past C"] = fuse(pv2 * livef.unsqueeze(-1) * weight.unsqueeze(-1))
+    # 4. the weight of an invalid view not zeroed
+    out["4 invalid view keeps its weight"] = fuse(per_view * weight.unsqueeze(-1))
+    return out
+
+
+def test_thin_mutants_fail_the_pin():
+    """Each defect a views-in-parallel gather can have fails field_ref.check on a thin-alone case, which the unmutated
+    float32 port passes (mutant -> the assert of tests/test_gpu_field_ref.py::test_family_against_float64 that catches it:
+    compare()'s R.check on the case printed here):
+      1 a view's term read from the next point's lane group (a shuffle past a ragged last group)
+      2 view V - 1 dropped from the ordered sum (a wrong lane count per point)
+      3 the last vector read past C (min(g, cvec - 1) -> g)
+      4 the weight of an invalid view not zeroed (the skipped view must add +0)"""
+    caught = {}
+    for name in ("thin V2 C3", "thin V3 C6", "thin V4 C8", "thin V8 C16", "thin V4 C12", "thin V5 C1"):
+        case = FC.CASES[name]()
+        assert case["thin_form"] == "parallel"
+        vals, scales = R.field64(case["obs"], case["pts"], case["H"], case["W"], case["mu"], [case["maps"]["thin"]])
+        for tag, got in _thin_mutants(case).items():
+            ok, w, msg = R.check(got, vals[0], scales[0])
+            if tag == "port":
+                assert ok, "%s: %s" % (name, msg)
+            elif not ok:
+                caught.setdefault(tag, []).append("%s (%.3g)" % (name, w))
+    print("\nthin mutants -> the cases that catch them (worst ratio):")
+    for tag in ("1 a view read from the next point's lanes", "2 view V-1 dropped", "3 last vector read past C", "4 invalid view keeps its weight"):
+        print("  %-44s %s" % (tag, ", ".join(caught.get(tag, [])) or "NOT CAUGHT"))
+        assert caught.get(tag), "%s: no thin-alone case fails field_ref.check" % tag
+
+
+def test_onehot_weight_sum_is_attainable():
+    """Where a one-hot mask is flat over the corners of every valid view, the float32 port is within the bound of
+    sum_v w_v / (cnt + 1e-6) and exactly 0 elsewhere (what tests/test_gpu_field_ref.py::test_onehot_mask_is_the_weight_sum
+    asks of the kernels); the float64 per-view samples of a map with non-finite texels and points match the port's."""
+    case = FC.CASES["thin V4 C8 one-hot, batch_eval"]()
+    m = case["maps"]["thin"]
+    got = _port(case, torch.arange(case["pts"].shape[0]))["thin"]
+    expect, scale, ones, zeros, unseen = R.weight_sum_entries(case["obs"], case["pts"], case["H"], case["W"], case["mu"], m)
+    assert int(ones.sum()) >= 100 and int(zeros.sum()) >= 1000 and int(unseen.sum()) >= 10, (int(ones.sum()), int(zeros.sum()), int(unseen.sum()))
+    ok, w, msg = R.check(got[ones], expect[ones], scale[ones])
+    print("\none-hot: %d entries are the weight sum (worst ratio %.3g), %d exactly 0, %d unseen rows" % (int(ones.sum()), w, int(zeros.sum()), int(unseen.sum())))
+    assert ok, msg
+    assert bool((got[zeros] == 0.0).all()) and bool((got[unseen] == 0.0).all())
+    # '<k>_inter': the per-view samples
+    case = FC.poison(FC.CASES["thin V4 C8"](), name="thin")
+    m = case["maps"]["thin"]
+    o = dict(case["obs"], thin=m)
+    with torch.no_grad():
+        port = torch_port.field_query(o, case["pts"], ["thin"], case["H"], case["W"], case["mu"], keep_inter=True)
+    vals, scales, parts = R.field64(case["obs"], case["pts"], case["H"], case["W"], case["mu"], [m], parts=True)
+    ok, w, msg = R.check(port["thin_inter"], parts["inter"][0], parts["inter_scale"][0])
+    print("per-view samples of the poisoned thin map: worst ratio %.3g" % w)
+    assert ok, msg
+    assert bool(torch.isnan(parts["inter"][0]).any())
