@@ -9,7 +9,7 @@ import os
 
 from . import build as _build
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 # status codes (include/d3fields_hip.h)
 OK = 0
@@ -32,6 +32,7 @@ MAX_PROJECTION = 64
 MAX_MOMENT_CHANNELS = 2048
 VOLUME_MAX_CHANNELS = 4096
 RAYCAST_MAX_STEPS = 65536
+EDT_MAX_EXTENT = 16384
 KERNEL_NAME_MAX = 80
 GAUSSIAN_MAX_RADIUS = 64
 DTYPE_F32 = 0
@@ -141,6 +142,8 @@ SIGNATURES = {
                                        ctypes.POINTER(_vp), _vp]),
     "d3f_band_sample_backward": (ctypes.c_int, [ctypes.POINTER(Volume), ctypes.POINTER(Band), _vp, _i64, ctypes.POINTER(VolumeSet), _i32, _vp,
                                                 ctypes.POINTER(_vp), _vp, _vp]),
+    "d3f_volume_edt_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "d3f_volume_edt": (ctypes.c_int, [_vp, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
     "d3f_volume_raycast": (ctypes.c_int, [ctypes.POINTER(Volume), _vp, _vp, _i64, ctypes.POINTER(Pinhole), _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp]),
     "d3f_fps_workspace_bytes": (_i64, [_i64]),
     "d3f_fps_pixels_workspace_bytes": (_i64, [_i64]),

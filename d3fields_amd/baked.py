@@ -13,6 +13,10 @@ meet (d3f_volume_raycast, csrc/raycast_kernels.hip) and read rows and normals at
 array, and every lookup above goes through d3f_band_sample / d3f_band_sample_backward -- the same bits wherever the band covers the
 point, the fill row and `in_band = False` elsewhere.
 
+`BakedField.clearance()` answers "how far is this point from the nearest observed surface, and which surface is that": the exact
+Euclidean distance transform of the occupied voxels (d3f_volume_edt, csrc/edt_kernels.hip) as a new field whose
+`dist` is the distance to the nearest site and whose `nearest_voxel` names that site; `nearest_site(pts)` looks it up.
+
 There is no CPU path: volumes and points live on the ROCm device.
 """
 import ctypes
@@ -71,6 +75,9 @@ class BakedField:
     dist        float32 [nx, ny, nz];  valid: bool [nx, ny, nz]
     names()     the channel sets, each float32 [nx, ny, nz, C]
 
+    A CLEARANCE field (clearance()) has no sets; its dist is the distance to the nearest site, and it has d2 int32 [nx, ny, nz] (squared
+    voxel distance), nearest_voxel int32 (flat index of that site, -1: none), sites bool, and nearest_site(pts).  They are None elsewhere.
+
     A BANDED field (to_band / Fusion.bake(band=)) holds each set as [M, C] rows of the stored voxels instead, and has
     band (the world length), slot int32 [nx, ny, nz] (-1: no row), cell_band uint8 [nx-1, ny-1, nz-1], band_voxels int32 [M]
     (ascending flat indices), band_points() and stored_fraction; its lookups add 'in_band'.  A dense field has band = None.
@@ -93,6 +100,7 @@ class BakedField:
         self._lib = _lib.load()
         self._axes = axes                 # the three axis tensors of the grid that was baked (Fusion.bake), or None: origin + i * step
         self.band = self.slot = self.cell_band = self.band_voxels = None
+        self.d2 = self.nearest_voxel = self.sites = None      # a clearance field's (clearance()); None on every other field
         self.cell_valid = torch.empty((nx - 1, ny - 1, nz - 1), dtype=torch.uint8, device=self.device)
         vol = self._volume()
         with torch.cuda.device(self.device):
@@ -376,6 +384,82 @@ class BakedField:
 
     def eval_dist(self, pts):
         return self.eval(pts, return_names=[])
+
+    # ---- clearance ------------------------------------------------------------------------------------------------------------
+    def _edt(self, sites, max_d2):
+        """one d3f_volume_edt on a bool volume -> (d2 int32, nearest int32, dist float32), each [nx, ny, nz]"""
+        dev = self.device
+        nx, ny, nz = self.grid_shape
+        site = sites.contiguous().view(torch.uint8)
+        d2 = torch.empty((nx, ny, nz), dtype=torch.int32, device=dev)
+        nearest = torch.empty((nx, ny, nz), dtype=torch.int32, device=dev)
+        dist = torch.empty((nx, ny, nz), dtype=torch.float32, device=dev)
+        ws_bytes = int(self._lib.d3f_volume_edt_workspace_bytes(nx, ny, nz))
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.d3f_volume_edt(_lib.ptr(site), nx, ny, nz, self.step, int(max_d2), _lib.ptr(d2), _lib.ptr(nearest), _lib.ptr(dist),
+                                                _lib.ptr(ws), ws_bytes, _lib.current_stream_handle(dev)))
+        return d2, nearest, dist
+
+    def clearance(self, iso=0.0, unknown="free", signed=False, max_distance=None):
+        """The exact Euclidean distance from every voxel centre to the centre of the nearest SITE, as a new field (d3f_volume_edt).
+
+        sites         valid & (dist <= iso) (iso rounded to float32, as dist is stored); unknown="occupied" makes every invalid voxel a
+                      site too -- the conservative reading of "never observed"; unknown="free" (default) ignores them.
+        max_distance  a world length or None: max_d2 = floor((max_distance / step)^2) caps the squared voxel distance (and bounds the
+                      search); the clamp value of dist is therefore step * sqrt(max_d2) <= max_distance.  Rejected if max_d2 would be 0.
+        signed        a second transform on the complement: a site voxel gets MINUS the distance to the nearest non-site voxel, and
+                      its nearest_voxel / d2 are that voxel's.  Distances are centre to centre, so dist steps from +step to -step
+                      across the boundary and is never in between; the source's own dist is the sub-voxel truth inside its shell.
+
+        -> a BakedField (origin, step, boundaries of this one, no sets) with dist float32, d2 int32 (squared voxel distance, capped),
+        nearest_voxel int32 (flat index of the nearest site, -1: none within the cap), sites bool; valid = d2 != INT32_MAX: a volume
+        without sites is invalid everywhere, with max_distance every voxel is valid, so eval never blends an inf.  eval(pts)['dist']
+        is the trilinear clearance and its gradient points away from the obstacle.  Works on a dense or a banded field."""
+        if unknown not in ("free", "occupied"):
+            raise ValueError("clearance: unknown must be 'free' or 'occupied', got %r" % (unknown,))
+        iso = float(iso)
+        if not math.isfinite(iso):
+            raise ValueError("clearance: iso must be finite, got %r" % iso)
+        max_d2 = 0
+        if max_distance is not None:
+            max_distance = float(max_distance)
+            if not (math.isfinite(max_distance) and max_distance > 0.0):
+                raise ValueError("clearance: max_distance must be a finite length > 0, got %r" % max_distance)
+            max_d2 = min(math.floor((max_distance / self.step) ** 2), 2 ** 31 - 2)
+            if max_d2 < 1:
+                raise ValueError("clearance: max_distance = %g is less than one step (%g)" % (max_distance, self.step))
+        sites = self.valid & (self.dist <= iso)
+        if unknown == "occupied":
+            sites = sites | ~self.valid
+        d2, nearest, dist = self._edt(sites, max_d2)
+        if signed:
+            d2_in, nearest_in, dist_in = self._edt(~sites, max_d2)
+            d2, nearest, dist = torch.where(sites, d2_in, d2), torch.where(sites, nearest_in, nearest), torch.where(sites, -dist_in, dist)
+        c = type(self)(self.origin, self.step, dist, d2 != 2 ** 31 - 1, {}, {}, boundaries=self.boundaries, axes=self._axes)
+        c.d2, c.nearest_voxel, c.sites = d2, nearest, sites
+        return c
+
+    def nearest_site(self, pts):
+        """The site nearest to the voxel each point falls into (a clearance field only).  A point is rounded to its nearest voxel
+        (g = (p - origin) / step in float64, half away from zero) and clipped to the lattice; it counts as inside while every
+        -0.5 <= g_a <= n_a - 0.5 (the box of the voxels' own cubes).
+        -> {'voxel': int64 [N] flat index of the site (-1: the point is outside or holds a NaN, or no site within the cap),
+            'points': float32 [N,3] the centre of that site (a NaN row where voxel is -1), 'valid_mask': bool [N]}.
+        Plain torch indexing: not a hot path."""
+        if self.nearest_voxel is None:
+            raise ValueError("nearest_site: this is not a clearance field; BakedField.clearance() makes one")
+        self._check_query(pts)
+        n = torch.tensor(self.grid_shape, dtype=torch.float64, device=self.device)
+        g = (pts.detach().double() - torch.tensor(self.origin, dtype=torch.float64, device=self.device)) / self.step
+        inside = ((g >= -0.5) & (g <= n - 0.5)).all(dim=1)                   # (NaN compares false)
+        r = torch.sign(g) * torch.floor(torch.abs(g) + 0.5)
+        i = torch.minimum(torch.clamp(torch.nan_to_num(r, nan=0.0), min=0.0), n - 1).long()
+        flat = (i[:, 0] * self.grid_shape[1] + i[:, 1]) * self.grid_shape[2] + i[:, 2]
+        voxel = torch.where(inside, self.nearest_voxel.view(-1)[flat].long(), torch.full_like(flat, -1))
+        ok = voxel >= 0
+        centres = self._voxel_centres(torch.clamp(voxel, min=0))
+        return {"voxel": voxel, "points": torch.where(ok[:, None], centres, torch.full_like(centres, float("nan"))), "valid_mask": ok}
 
     # ---- rays -----------------------------------------------------------------------------------------------------------------
     def _check_rays(self, origins, dirs):

@@ -810,6 +810,38 @@ int d3f_band_sample_backward(const d3f_volume *vol, const d3f_band *band, const 
     return e == hipSuccess ? D3F_OK : hip_fail(e, "band_sample_backward launch");
 }
 
+// ---- the exact Euclidean distance transform of a site volume (edt_kernels.hip) ----
+static bool edt_shape_ok(int32_t nx, int32_t ny, int32_t nz)
+{
+    return nx >= 1 && ny >= 1 && nz >= 1 && nx <= D3F_EDT_MAX_EXTENT && ny <= D3F_EDT_MAX_EXTENT && nz <= D3F_EDT_MAX_EXTENT &&
+           (int64_t)nx * ny * nz <= 0x7fffffffLL;
+}
+
+int64_t d3f_volume_edt_workspace_bytes(int32_t nx, int32_t ny, int32_t nz)
+{
+    return edt_shape_ok(nx, ny, nz) ? d3f::edt_workspace_bytes((int64_t)nx * ny * nz) : 0;
+}
+
+int d3f_volume_edt(const uint8_t *site, int32_t nx, int32_t ny, int32_t nz, float step, int32_t max_d2, int32_t *out_d2, int32_t *out_nearest,
+                   float *out_dist, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (!site) return fail(D3F_ERR_INVALID_ARG, "volume_edt: site is NULL");
+    if (!out_d2 && !out_nearest && !out_dist) return fail(D3F_ERR_INVALID_ARG, "volume_edt: out_d2, out_nearest and out_dist are all NULL");
+    if (!edt_shape_ok(nx, ny, nz))
+        return fail(D3F_ERR_BAD_SHAPE, "volume_edt: nx=%d ny=%d nz=%d, every extent must be in [1, %d] and the volume at most 2^31 - 1 voxels", nx, ny, nz,
+                    D3F_EDT_MAX_EXTENT);
+    if (max_d2 < 0) return fail(D3F_ERR_INVALID_ARG, "volume_edt: max_d2=%d is negative (0: no cap)", max_d2);
+    if (out_dist && (!(step > 0.0f) || step * 0.0f != 0.0f)) return fail(D3F_ERR_INVALID_ARG, "volume_edt: step must be > 0 and finite with out_dist");
+    if (!aligned(out_d2, 4) || !aligned(out_nearest, 4) || !aligned(out_dist, 4))
+        return fail(D3F_ERR_BAD_LAYOUT, "volume_edt: out_d2 / out_nearest / out_dist must be 4-byte aligned");
+    const int64_t need = d3f_volume_edt_workspace_bytes(nx, ny, nz);
+    if (!workspace || workspace_bytes < need) return fail(D3F_ERR_WORKSPACE, "volume_edt: needs %lld workspace bytes", (long long)need);
+    if (!aligned(workspace, 4)) return fail(D3F_ERR_BAD_LAYOUT, "volume_edt: workspace must be 4-byte aligned");
+    hipError_t e = d3f::launch_volume_edt(site, nx, ny, nz, step, max_d2 > 0 ? max_d2 : 0x7fffffff, out_d2, out_nearest, out_dist, workspace,
+                                          static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_edt launch");
+}
+
 // ---- the first surface a ray meets in a baked volume (raycast_kernels.hip) ----
 int d3f_volume_raycast(const d3f_volume *vol, const float *origins, const float *dirs, int64_t n, const d3f_pinhole *camera,
                        float march_step, float t_near, float t_far, float *out_t, uint8_t *out_hit, float *out_points,

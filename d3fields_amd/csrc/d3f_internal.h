@@ -238,6 +238,11 @@ hipError_t launch_band_mark(const float *dist, const uint8_t *cell_valid, int nx
 hipError_t launch_band_sample(const BandParams &B, hipStream_t s);
 hipError_t launch_band_backward(const BandParams &B, hipStream_t s);
 
+// edt_kernels.hip: the exact Euclidean distance transform of a site volume; cap: max_d2, or INT32_MAX for none
+int64_t edt_workspace_bytes(int64_t n);
+hipError_t launch_volume_edt(const uint8_t *site, int nx, int ny, int nz, float step, int32_t cap, int32_t *out_d2, int32_t *out_nearest, float *out_dist,
+                             void *workspace, hipStream_t s);
+
 // raycast_kernels.hip: the first surface a ray meets in a baked volume
 constexpr float kRayMaxSamples = 131072.0f;  // a ray whose K exceeds this misses: unreachable under the entry point's 65536-step guard but for overflow
 struct RayParams {

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define D3F_ABI_VERSION 13
+#define D3F_ABI_VERSION 14
 
 #define D3F_OK 0
 #define D3F_ERR_INVALID_ARG (-1)  /* null pointer, negative count, bad enum               */
@@ -440,6 +440,30 @@ int d3f_band_sample(const d3f_volume *vol, const d3f_band *band, const float *pt
  * no term for the choice of the cell or for the band edge.  No atomics; two runs agree bit for bit. */
 int d3f_band_sample_backward(const d3f_volume *vol, const d3f_band *band, const float *pts, int64_t n, const d3f_volume_set *sets, int32_t n_sets,
                              const float *grad_dist, const void *const *grad_sets, float *grad_pts, void *stream);
+
+/* (ABI 14) The exact Euclidean distance transform of a volume of SITES.  site: one byte per voxel, [nx,ny,nz]
+ * with z fastest, non-zero = site.  With v, s integer voxel coordinates:
+ *   true_d2(v)   = min over the sites s of |v - s|^2; INT32_MAX when the volume has no site;
+ *   cap          = max_d2 if max_d2 > 0, else INT32_MAX (no cap);
+ *   out_d2[v]    = min(true_d2(v), cap);
+ *   out_nearest[v] = the flat index (x*ny + y)*nz + z of A site with |v - s|^2 == true_d2(v); -1 where true_d2(v) > cap or no site
+ *                  exists.  Among equidistant sites the choice is fixed by the kernels' candidate order (the z line's lower site, then
+ *                  the lower y, then the lower x, each at equal distance) -- never by the order in which anything lands: there are
+ *                  no atomics and two runs give identical bytes;
+ *   out_dist[v]  = sqrtf((float)out_d2[v]) * step, each operation correctly rounded; +inf where out_d2[v] == INT32_MAX.
+ * A positive max_d2 also bounds the search: no site farther than floor(sqrt(max_d2)) voxels along an axis is looked at.
+ * Each output may be NULL (not all three).  Extents are in [1, D3F_EDT_MAX_EXTENT] (|v - s|^2 <= 3 * 16383^2 stays inside int32; an
+ * extent of 1 is legal: a 2-D image is a volume with nz = 1) and the volume holds at most 2^31 - 1 voxels.
+ * Three launches on `stream` (z, y, x; separable, the winning site carried through the passes); no allocation, no synchronisation.
+ * workspace: d3f_volume_edt_workspace_bytes (6 bytes per voxel: one int32 and one int16 volume), 4-byte aligned; the function
+ * returns 0 exactly for a shape d3f_volume_edt rejects.
+ * Status errors, nothing launched: site NULL or all outputs NULL, max_d2 < 0, out_dist with a step that is not finite and > 0
+ * (D3F_ERR_INVALID_ARG); a bad shape (D3F_ERR_BAD_SHAPE); an int32 / float pointer or the workspace not 4-byte aligned
+ * (D3F_ERR_BAD_LAYOUT); workspace NULL or too short (D3F_ERR_WORKSPACE). */
+#define D3F_EDT_MAX_EXTENT 16384
+int64_t d3f_volume_edt_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
+int d3f_volume_edt(const uint8_t *site, int32_t nx, int32_t ny, int32_t nz, float step, int32_t max_d2, int32_t *out_d2, int32_t *out_nearest,
+                   float *out_dist, void *workspace, int64_t workspace_bytes, void *stream);
 
 /* (ABI 12) The first surface a ray meets in a baked volume: a fixed-step march through `dist` with one linear interpolation at the
  * sign change.  Everything in fp32.  Ray i is p(t) = o + t*d; d need not be unit.
