@@ -8,7 +8,7 @@ this package is the host-side mirror of the reference's Python interface.
 """
 from .fusion import Fusion, create_init_grid, fps, instance2onehot, onehot2instance  # noqa: F401
 from . import baked  # noqa: F401
-from .baked import BakedField  # noqa: F401
+from .baked import BakedField, Components  # noqa: F401
 from . import corr_utils  # noqa: F401
 from . import mesh  # noqa: F401
 from .mesh import Mesh  # noqa: F401

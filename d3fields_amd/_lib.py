@@ -9,7 +9,7 @@ import os
 
 from . import build as _build
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 # status codes (include/d3fields_hip.h)
 OK = 0
@@ -144,6 +144,8 @@ SIGNATURES = {
                                                 ctypes.POINTER(_vp), _vp, _vp]),
     "d3f_volume_edt_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "d3f_volume_edt": (ctypes.c_int, [_vp, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "d3f_volume_components_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "d3f_volume_components": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _i64, _vp]),
     "d3f_volume_raycast": (ctypes.c_int, [ctypes.POINTER(Volume), _vp, _vp, _i64, ctypes.POINTER(Pinhole), _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp]),
     "d3f_fps_workspace_bytes": (_i64, [_i64]),
     "d3f_fps_pixels_workspace_bytes": (_i64, [_i64]),

@@ -17,6 +17,10 @@ point, the fill row and `in_band = False` elsewhere.
 Euclidean distance transform of the occupied voxels (d3f_volume_edt, csrc/edt_kernels.hip) as a new field whose
 `dist` is the distance to the nearest site and whose `nearest_voxel` names that site; `nearest_site(pts)` looks it up.
 
+`BakedField.components()` labels the connected components of the occupied voxels, or of any site volume (d3f_volume_components,
+csrc/ccl_kernels.hip): a `Components` with the label volume, each component's root, size and box; small
+components are dropped by `min_voxels`, which `clearance(min_voxels=)` uses to keep floaters out of the transform.
+
 There is no CPU path: volumes and points live on the ROCm device.
 """
 import ctypes
@@ -26,7 +30,7 @@ import torch
 
 from . import _lib
 
-__all__ = ["BakedField"]
+__all__ = ["BakedField", "Components"]
 
 _RESERVED = ("dist", "valid_mask", "grid_shape")
 _RAY_KEYS = ("t", "depth", "hit_mask", "points", "normal")      # output keys of raycast / render: a set of that name cannot be asked for there
@@ -64,6 +68,80 @@ class _BakedQueryFn(torch.autograd.Function):
     def backward(ctx, grad_dist, *rest):
         grad_sets = rest[len(ctx.field._mask_keys()):]
         return ctx.field.backward(ctx.pts, grad_dist, dict(zip(ctx.names, grad_sets))), None, None
+
+
+def _check_points(pts, device, who):
+    assert type(pts) == torch.Tensor
+    assert len(pts.shape) == 2
+    assert pts.shape[1] == 3
+    if not pts.is_cuda or pts.device != device:
+        raise RuntimeError("%s: pts must be on %s (where the volume lives); there is no CPU path" % (who, device))
+    if pts.dtype != torch.float32:
+        raise TypeError("%s: pts must be float32, got %s" % (who, pts.dtype))
+
+
+def _voxel_of(pts, origin, step, grid_shape):
+    """(inside bool [N], flat int64 [N]): the voxel each point falls into -- g = (p - origin) / step in float64, rounded half away from
+    zero and clipped to the lattice; inside while every -0.5 <= g_a <= n_a - 0.5 (NaN compares false).  The one voxel rule of
+    BakedField.nearest_site and Components.label_at."""
+    n = torch.tensor(tuple(grid_shape), dtype=torch.float64, device=pts.device)
+    g = (pts.detach().double() - torch.tensor(origin, dtype=torch.float64, device=pts.device)) / step
+    inside = ((g >= -0.5) & (g <= n - 0.5)).all(dim=1)
+    r = torch.sign(g) * torch.floor(torch.abs(g) + 0.5)
+    i = torch.minimum(torch.clamp(torch.nan_to_num(r, nan=0.0), min=0.0), n - 1).long()
+    return inside, (i[:, 0] * grid_shape[1] + i[:, 1]) * grid_shape[2] + i[:, 2]
+
+
+class Components:
+    """The connected components of a site volume (BakedField.components).  Tensors only, on the field's device.
+
+    labels      int32 [nx, ny, nz]: 1..count for the voxels of a kept component, 0 for a non-site or a dropped component
+    count       K, the number of kept components (size >= min_voxels), numbered in ascending order of root; found: all components
+    roots       int32 [K]: the smallest flat index (x*ny + y)*nz + z of each;  sizes int32 [K]: its voxel count
+    box_lo, box_hi   int32 [K, 3]: the inclusive min and max of x, y, z
+    sites       bool [nx, ny, nz]: the volume that was labelled;  connectivity (6, 18 or 26) and min_voxels as used
+    origin, step, grid_shape   of the field it came from (label_at, boxes_world); no reference to the field itself"""
+
+    def __init__(self, origin, step, labels, count, found, stats, sites, connectivity, min_voxels):
+        self.origin, self.step, self.grid_shape = tuple(origin), float(step), torch.Size(labels.shape)
+        self.labels, self.count, self.found = labels, int(count), int(found)
+        self.roots, self.sizes = stats[:, 0].contiguous(), stats[:, 1].contiguous()
+        self.box_lo, self.box_hi = stats[:, 2:5].contiguous(), stats[:, 5:8].contiguous()
+        self.sites, self.connectivity, self.min_voxels = sites, int(connectivity), int(min_voxels)
+
+    def mask(self, ids=None):
+        """bool [nx, ny, nz]: the voxels of the components with these label ids (an int, a sequence or a tensor); None: every kept one"""
+        if ids is None:
+            return self.labels > 0
+        ids = torch.as_tensor(ids, device=self.labels.device).reshape(-1).long()
+        if ids.numel() and (int(ids.min()) < 1 or int(ids.max()) > self.count):
+            raise ValueError("Components.mask: label ids must lie in 1..%d" % self.count)
+        lut = torch.zeros(self.count + 1, dtype=torch.bool, device=self.labels.device)
+        lut[ids] = True
+        return lut[self.labels.long()]
+
+    def largest(self, k=1):
+        """int64 [min(k, count)]: label ids by descending size, the smaller id first among equal sizes"""
+        k = int(k)
+        if k < 0:
+            raise ValueError("Components.largest: k must be >= 0, got %d" % k)
+        order = torch.sort(self.sizes.long(), descending=True, stable=True).indices      # ids ascend already: stable keeps them so at ties
+        return order[:k] + 1
+
+    def boxes_world(self):
+        """float32 [K, 2, 3]: lower and upper corner of each box in world coordinates, the outer faces of the voxels' cubes"""
+        o = torch.tensor(self.origin, dtype=torch.float32, device=self.labels.device)
+        h = torch.tensor(self.step, dtype=torch.float32, device=self.labels.device)
+        lo = o + (self.box_lo.to(torch.float32) - 0.5) * h
+        hi = o + (self.box_hi.to(torch.float32) + 0.5) * h
+        return torch.stack((lo, hi), dim=1)
+
+    def label_at(self, pts):
+        """int32 [N]: the label of the voxel each point falls into, by the rounding and inside rule of BakedField.nearest_site; 0 for a
+        point outside, a NaN coordinate, a non-site or a dropped component.  Plain torch indexing: not a hot path."""
+        _check_points(pts, self.labels.device, "Components.label_at")
+        inside, flat = _voxel_of(pts, self.origin, self.step, self.grid_shape)
+        return torch.where(inside, self.labels.view(-1)[flat], torch.zeros_like(flat, dtype=torch.int32))
 
 
 class BakedField:
@@ -401,7 +479,77 @@ class BakedField:
                                                 _lib.ptr(ws), ws_bytes, _lib.current_stream_handle(dev)))
         return d2, nearest, dist
 
-    def clearance(self, iso=0.0, unknown="free", signed=False, max_distance=None):
+    def _site_mask(self, who, iso, unknown, sites):
+        """the bool site volume of clearance / components: valid & (dist <= iso), plus the invalid voxels for unknown="occupied"; or the
+        caller's own `sites` volume, which iso and unknown then must not accompany"""
+        if unknown not in ("free", "occupied"):
+            raise ValueError("%s: unknown must be 'free' or 'occupied', got %r" % (who, unknown))
+        iso = float(iso)
+        if not math.isfinite(iso):
+            raise ValueError("%s: iso must be finite, got %r" % (who, iso))
+        if sites is None:
+            mask = self.valid & (self.dist <= iso)
+            return mask | ~self.valid if unknown == "occupied" else mask
+        if iso != 0.0 or unknown != "free":
+            raise ValueError("%s: iso and unknown describe the field's own site mask; leave them at their defaults with sites=" % who)
+        if not isinstance(sites, torch.Tensor) or tuple(sites.shape) != tuple(self.grid_shape) or sites.dtype not in (torch.bool, torch.uint8):
+            raise ValueError("%s: sites must be a bool or uint8 tensor of shape %s" % (who, tuple(self.grid_shape)))
+        if sites.device != self.device:
+            raise RuntimeError("%s: sites is on %s, the field on %s" % (who, sites.device, self.device))
+        return sites.detach() if sites.dtype == torch.bool else sites.detach() != 0
+
+    @staticmethod
+    def _check_ccl(who, connectivity, min_voxels):
+        if connectivity not in (6, 18, 26):
+            raise ValueError("%s: connectivity must be 6, 18 or 26, got %r" % (who, connectivity))
+        if isinstance(min_voxels, bool) or not isinstance(min_voxels, int) or not 1 <= min_voxels <= 2 ** 31 - 1:
+            raise ValueError("%s: min_voxels must be an integer >= 1, got %r" % (who, min_voxels))
+
+    _STATS_ROWS = 4096      # the stats rows the first launch of _label has room for
+
+    def _label(self, mask, connectivity, min_voxels, want_stats=True):
+        """d3f_volume_components on a bool volume -> (labels int32 [nx,ny,nz], K, found, stats int32 [K, 8] or None); one host read of
+        the count; more kept components than the first launch had rows for cost one re-run with the count (as _mark)"""
+        dev = self.device
+        nx, ny, nz = self.grid_shape
+        site = mask.contiguous().view(torch.uint8)
+        labels = torch.empty((nx, ny, nz), dtype=torch.int32, device=dev)
+        count = torch.empty(2, dtype=torch.int32, device=dev)
+        ws_bytes = int(self._lib.d3f_volume_components_workspace_bytes(nx, ny, nz))
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+
+        def launch(stats, capacity):
+            with torch.cuda.device(dev):
+                _lib.check(self._lib.d3f_volume_components(_lib.ptr(site), nx, ny, nz, connectivity, min_voxels, _lib.ptr(labels), _lib.ptr(count),
+                                                           _lib.ptr(stats), capacity, _lib.ptr(ws), ws_bytes, _lib.current_stream_handle(dev)))
+            return count.tolist()
+
+        if not want_stats:
+            kept, found = launch(None, 0)
+            return labels, kept, found, None
+        capacity = min(nx * ny * nz, self._STATS_ROWS)
+        stats = torch.empty((capacity, 8), dtype=torch.int32, device=dev)
+        kept, found = launch(stats, capacity)
+        if kept > capacity:
+            stats = torch.empty((kept, 8), dtype=torch.int32, device=dev)
+            launch(stats, kept)
+        return labels, kept, found, stats[:kept].clone() if kept < stats.shape[0] else stats
+
+    def components(self, iso=0.0, unknown="free", connectivity=26, min_voxels=1, sites=None):
+        """The connected components of the occupied voxels (d3f_volume_components) -> Components.
+
+        sites         the mask of clearance(): valid & (dist <= iso), plus the invalid voxels for unknown="occupied"; or an explicit
+                      bool / uint8 [nx, ny, nz] volume on this device (non-zero = site; iso and unknown must then keep their defaults)
+        connectivity  6, 18 or 26: two sites are neighbours if they differ by at most 1 on every axis and by at most 1 / 2 / 3 in L1
+        min_voxels    components with fewer voxels are dropped: their voxels get label 0 and the kept ones are numbered 1..count in
+                      ascending order of their root, the smallest flat index
+        Exact and reproducible: integer data, the same bytes on every run.  Works on a dense, a banded and a clearance field."""
+        self._check_ccl("components", connectivity, min_voxels)
+        mask = self._site_mask("components", iso, unknown, sites)
+        labels, kept, found, stats = self._label(mask, connectivity, min_voxels)
+        return Components(self.origin, self.step, labels, kept, found, stats, mask, connectivity, min_voxels)
+
+    def clearance(self, iso=0.0, unknown="free", signed=False, max_distance=None, sites=None, min_voxels=1, connectivity=26):
         """The exact Euclidean distance from every voxel centre to the centre of the nearest SITE, as a new field (d3f_volume_edt).
 
         sites         valid & (dist <= iso) (iso rounded to float32, as dist is stored); unknown="occupied" makes every invalid voxel a
@@ -415,12 +563,14 @@ class BakedField:
         -> a BakedField (origin, step, boundaries of this one, no sets) with dist float32, d2 int32 (squared voxel distance, capped),
         nearest_voxel int32 (flat index of the nearest site, -1: none within the cap), sites bool; valid = d2 != INT32_MAX: a volume
         without sites is invalid everywhere, with max_distance every voxel is valid, so eval never blends an inf.  eval(pts)['dist']
-        is the trilinear clearance and its gradient points away from the obstacle.  Works on a dense or a banded field."""
-        if unknown not in ("free", "occupied"):
-            raise ValueError("clearance: unknown must be 'free' or 'occupied', got %r" % (unknown,))
-        iso = float(iso)
-        if not math.isfinite(iso):
-            raise ValueError("clearance: iso must be finite, got %r" % iso)
+        is the trilinear clearance and its gradient points away from the obstacle.  Works on a dense or a banded field.
+
+        sites         an explicit bool / uint8 [nx, ny, nz] volume instead of that mask (iso and unknown must keep their defaults).
+        min_voxels    > 1: the site mask first goes through components(connectivity=, min_voxels=) and only the voxels of kept
+                      components stay sites -- floaters of a few voxels no longer cast a phantom obstacle; with signed=True this
+                      happens before both transforms.  With the default 1 no labelling runs."""
+        self._check_ccl("clearance", connectivity, min_voxels)
+        sites = self._site_mask("clearance", iso, unknown, sites)
         max_d2 = 0
         if max_distance is not None:
             max_distance = float(max_distance)
@@ -429,9 +579,8 @@ class BakedField:
             max_d2 = min(math.floor((max_distance / self.step) ** 2), 2 ** 31 - 2)
             if max_d2 < 1:
                 raise ValueError("clearance: max_distance = %g is less than one step (%g)" % (max_distance, self.step))
-        sites = self.valid & (self.dist <= iso)
-        if unknown == "occupied":
-            sites = sites | ~self.valid
+        if min_voxels > 1:
+            sites = self._label(sites, connectivity, min_voxels, want_stats=False)[0] > 0
         d2, nearest, dist = self._edt(sites, max_d2)
         if signed:
             d2_in, nearest_in, dist_in = self._edt(~sites, max_d2)
@@ -450,12 +599,7 @@ class BakedField:
         if self.nearest_voxel is None:
             raise ValueError("nearest_site: this is not a clearance field; BakedField.clearance() makes one")
         self._check_query(pts)
-        n = torch.tensor(self.grid_shape, dtype=torch.float64, device=self.device)
-        g = (pts.detach().double() - torch.tensor(self.origin, dtype=torch.float64, device=self.device)) / self.step
-        inside = ((g >= -0.5) & (g <= n - 0.5)).all(dim=1)                   # (NaN compares false)
-        r = torch.sign(g) * torch.floor(torch.abs(g) + 0.5)
-        i = torch.minimum(torch.clamp(torch.nan_to_num(r, nan=0.0), min=0.0), n - 1).long()
-        flat = (i[:, 0] * self.grid_shape[1] + i[:, 1]) * self.grid_shape[2] + i[:, 2]
+        inside, flat = _voxel_of(pts, self.origin, self.step, self.grid_shape)
         voxel = torch.where(inside, self.nearest_voxel.view(-1)[flat].long(), torch.full_like(flat, -1))
         ok = voxel >= 0
         centres = self._voxel_centres(torch.clamp(voxel, min=0))

@@ -842,6 +842,35 @@ int d3f_volume_edt(const uint8_t *site, int32_t nx, int32_t ny, int32_t nz, floa
     return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_edt launch");
 }
 
+// ---- connected components of a site volume (ccl_kernels.hip) ----
+int64_t d3f_volume_components_workspace_bytes(int32_t nx, int32_t ny, int32_t nz)
+{
+    return edt_shape_ok(nx, ny, nz) ? d3f::ccl_workspace_bytes((int64_t)nx * ny * nz) : 0;
+}
+
+int d3f_volume_components(const uint8_t *site, int32_t nx, int32_t ny, int32_t nz, int32_t connectivity, int32_t min_voxels, int32_t *out_label,
+                          int32_t *out_count, int32_t *out_stats, int32_t stats_capacity, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (!site) return fail(D3F_ERR_INVALID_ARG, "volume_components: site is NULL");
+    if (!out_label || !out_count) return fail(D3F_ERR_INVALID_ARG, "volume_components: out_label or out_count is NULL");
+    if (connectivity != 6 && connectivity != 18 && connectivity != 26)
+        return fail(D3F_ERR_INVALID_ARG, "volume_components: connectivity=%d, must be 6, 18 or 26", connectivity);
+    if (min_voxels < 1) return fail(D3F_ERR_INVALID_ARG, "volume_components: min_voxels=%d, must be >= 1", min_voxels);
+    if (stats_capacity < 0) return fail(D3F_ERR_INVALID_ARG, "volume_components: stats_capacity=%d is negative", stats_capacity);
+    if (stats_capacity > 0 && !out_stats) return fail(D3F_ERR_INVALID_ARG, "volume_components: out_stats is NULL with stats_capacity=%d", stats_capacity);
+    if (!edt_shape_ok(nx, ny, nz))
+        return fail(D3F_ERR_BAD_SHAPE, "volume_components: nx=%d ny=%d nz=%d, every extent must be in [1, %d] and the volume at most 2^31 - 1 voxels", nx,
+                    ny, nz, D3F_EDT_MAX_EXTENT);
+    if (!aligned(out_label, 4) || !aligned(out_count, 4) || !aligned(out_stats, 4))
+        return fail(D3F_ERR_BAD_LAYOUT, "volume_components: out_label / out_count / out_stats must be 4-byte aligned");
+    const int64_t need = d3f_volume_components_workspace_bytes(nx, ny, nz);
+    if (!workspace || workspace_bytes < need) return fail(D3F_ERR_WORKSPACE, "volume_components: needs %lld workspace bytes", (long long)need);
+    if (!aligned(workspace, 4)) return fail(D3F_ERR_BAD_LAYOUT, "volume_components: workspace must be 4-byte aligned");
+    hipError_t e = d3f::launch_volume_components(site, nx, ny, nz, connectivity, min_voxels, out_label, out_count, stats_capacity > 0 ? out_stats : nullptr,
+                                                 stats_capacity, workspace, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_components launch");
+}
+
 // ---- the first surface a ray meets in a baked volume (raycast_kernels.hip) ----
 int d3f_volume_raycast(const d3f_volume *vol, const float *origins, const float *dirs, int64_t n, const d3f_pinhole *camera,
                        float march_step, float t_near, float t_far, float *out_t, uint8_t *out_hit, float *out_points,

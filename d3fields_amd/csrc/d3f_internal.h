@@ -243,6 +243,11 @@ int64_t edt_workspace_bytes(int64_t n);
 hipError_t launch_volume_edt(const uint8_t *site, int nx, int ny, int nz, float step, int32_t cap, int32_t *out_d2, int32_t *out_nearest, float *out_dist,
                              void *workspace, hipStream_t s);
 
+// ccl_kernels.hip: connected components of a site volume
+int64_t ccl_workspace_bytes(int64_t n);
+hipError_t launch_volume_components(const uint8_t *site, int nx, int ny, int nz, int connectivity, int min_voxels, int32_t *out_label, int32_t *out_count,
+                                    int32_t *out_stats, int capacity, void *workspace, hipStream_t s);
+
 // raycast_kernels.hip: the first surface a ray meets in a baked volume
 constexpr float kRayMaxSamples = 131072.0f;  // a ray whose K exceeds this misses: unreachable under the entry point's 65536-step guard but for overflow
 struct RayParams {

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define D3F_ABI_VERSION 14
+#define D3F_ABI_VERSION 15
 
 #define D3F_OK 0
 #define D3F_ERR_INVALID_ARG (-1)  /* null pointer, negative count, bad enum               */
@@ -464,6 +464,31 @@ int d3f_band_sample_backward(const d3f_volume *vol, const d3f_band *band, const 
 int64_t d3f_volume_edt_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
 int d3f_volume_edt(const uint8_t *site, int32_t nx, int32_t ny, int32_t nz, float step, int32_t max_d2, int32_t *out_d2, int32_t *out_nearest,
                    float *out_dist, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* (ABI 15) Connected components of a volume of SITES.  site: as d3f_volume_edt, one byte per voxel, [nx,ny,nz]
+ * with z fastest, non-zero = site.
+ *   neighbours   two sites whose integer coordinates differ by at most 1 on every axis and by at most 1 / 2 / 3 in L1 for
+ *                connectivity 6 / 18 / 26.  Neighbourhood is spatial: (x, y, nz-1) and (x, y+1, 0) are adjacent in memory and are NOT
+ *                neighbours, nor are (x, ny-1, z) and (x+1, 0, z);
+ *   component    a class of the transitive closure; its ROOT is its smallest flat index (x*ny + y)*nz + z, its SIZE its voxel count, its
+ *                BOX the inclusive min and max of x, y and z;
+ *   found        the number of components; the KEPT ones are those with size >= min_voxels, numbered 1..K in ascending order of root;
+ *   out_label[v] the number of the voxel's component; 0 for a non-site or a component that is not kept;
+ *   out_count    {K, found}, two int32;
+ *   out_stats    row k-1 = {root, size, x0, y0, z0, x1, y1, z1} (int32) of component k, for k <= stats_capacity.  Rows beyond the capacity
+ *                are not written and out_count still reports K: count, then run again with room (as d3f_band_mark).  May be NULL
+ *                with stats_capacity 0.
+ * Every output is a function of the input alone -- integer min, max and add only -- and two runs give identical bytes.
+ * Union-find on the caller's stream (parents start at the z run, are merged lock-free with agent-scope atomic min, then flattened,
+ * counted and numbered by a prefix sum); no allocation, no synchronisation.  Shapes as d3f_volume_edt: extents in
+ * [1, D3F_EDT_MAX_EXTENT], at most 2^31 - 1 voxels.  workspace: d3f_volume_components_workspace_bytes (three int32 volumes and the
+ * prefix sum's scratch), 4-byte aligned, contents irrelevant; the function returns 0 exactly for a shape d3f_volume_components rejects.
+ * Status errors, nothing launched: site, out_label or out_count NULL, connectivity not 6 / 18 / 26, min_voxels < 1, stats_capacity < 0,
+ * out_stats NULL with stats_capacity > 0 (D3F_ERR_INVALID_ARG); a bad shape (D3F_ERR_BAD_SHAPE); an int32 pointer or the workspace not
+ * 4-byte aligned (D3F_ERR_BAD_LAYOUT); workspace NULL or too short (D3F_ERR_WORKSPACE). */
+int64_t d3f_volume_components_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
+int d3f_volume_components(const uint8_t *site, int32_t nx, int32_t ny, int32_t nz, int32_t connectivity, int32_t min_voxels, int32_t *out_label,
+                          int32_t *out_count, int32_t *out_stats, int32_t stats_capacity, void *workspace, int64_t workspace_bytes, void *stream);
 
 /* (ABI 12) The first surface a ray meets in a baked volume: a fixed-step march through `dist` with one linear interpolation at the
  * sign change.  Everything in fp32.  Ray i is p(t) = o + t*d; d need not be unit.
