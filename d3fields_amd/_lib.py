@@ -9,7 +9,7 @@ import os
 
 from . import build as _build
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 # status codes (include/d3fields_hip.h)
 OK = 0
@@ -33,6 +33,9 @@ MAX_MOMENT_CHANNELS = 2048
 VOLUME_MAX_CHANNELS = 4096
 RAYCAST_MAX_STEPS = 65536
 EDT_MAX_EXTENT = 16384
+POOL_MEAN, POOL_VOTES = 0, 1
+POOL_CHUNK = 256
+POOL_MAX_VOTE_CHANNELS = 256
 KERNEL_NAME_MAX = 80
 GAUSSIAN_MAX_RADIUS = 64
 DTYPE_F32 = 0
@@ -146,6 +149,9 @@ SIGNATURES = {
     "d3f_volume_edt": (ctypes.c_int, [_vp, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
     "d3f_volume_components_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "d3f_volume_components": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _i64, _vp]),
+    "d3f_volume_pool_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32, _i64, _i64]),
+    "d3f_volume_pool": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, ctypes.POINTER(VolumeSet), _i32, ctypes.POINTER(_i32), _i64, _vp, _vp, _vp,
+                                       ctypes.POINTER(_vp), _vp, _i64, _vp]),
     "d3f_volume_raycast": (ctypes.c_int, [ctypes.POINTER(Volume), _vp, _vp, _i64, ctypes.POINTER(Pinhole), _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp]),
     "d3f_fps_workspace_bytes": (_i64, [_i64]),
     "d3f_fps_pixels_workspace_bytes": (_i64, [_i64]),

@@ -21,6 +21,10 @@ Euclidean distance transform of the occupied voxels (d3f_volume_edt, csrc/edt_ke
 csrc/ccl_kernels.hip): a `Components` with the label volume, each component's root, size and box; small
 components are dropped by `min_voxels`, which `clearance(min_voxels=)` uses to keep floaters out of the transform.
 
+`BakedField.pool(components)` pools the field per component (d3f_volume_pool, csrc/pool_kernels.hip): the mean
+row of every baked set, hard votes over the channels of chosen sets, and each component's member count, centroid and covariance -- one
+call for all components, the same bytes on every run.
+
 There is no CPU path: volumes and points live on the ROCm device.
 """
 import ctypes
@@ -33,6 +37,7 @@ from . import _lib
 __all__ = ["BakedField", "Components"]
 
 _RESERVED = ("dist", "valid_mask", "grid_shape")
+_POOL_KEYS = ("count", "moments", "centroid", "covariance")     # output keys of pool, next to one name + '_votes' per voted set
 _RAY_KEYS = ("t", "depth", "hit_mask", "points", "normal")      # output keys of raycast / render: a set of that name cannot be asked for there
 
 
@@ -548,6 +553,89 @@ class BakedField:
         mask = self._site_mask("components", iso, unknown, sites)
         labels, kept, found, stats = self._label(mask, connectivity, min_voxels)
         return Components(self.origin, self.step, labels, kept, found, stats, mask, connectivity, min_voxels)
+
+    # ---- pooling --------------------------------------------------------------------------------------------------------------
+    def pool(self, components, return_names=None, votes=(), count=None):
+        """Pool the field over the voxels of every component in one call (d3f_volume_pool) -> a dict of tensors on the device.
+
+        components    a Components of this field's grid (components()), or an int32 [nx, ny, nz] label volume on this device together with
+                      count=K: label k in 1..K names component k, any other value belongs to none
+        return_names  the sets whose MEAN row every component gets (None: every baked set); votes: the sets (at most 256 channels) whose
+                      rows also cast a hard vote -- one per member, for the first channel that holds the row's maximum
+        A voxel is a member of its component if it is valid and, on a banded field, stored: a banded field pools exactly its rows.
+          'count'       int32 [K] members;  'moments' int64 [K, 9]: the sums of x, y, z, xx, xy, xz, yy, yz, zz over the members' voxel coordinates
+          'centroid'    float32 [K, 3] = origin + step * sum / count;  'covariance' float32 [K, 3, 3]: the population covariance of the member
+                        voxel centres in world units, in float64 from the integer moments (torch.linalg.eigh gives the principal axes)
+          name          float32 [K, C]: the members' rows summed in ascending flat index, in chunks of 256 (a fixed tree of float32 adds),
+                        divided by the count;  name + '_votes': int32 [K, C]
+        A component without members has count 0, NaN rows in 'centroid' and 'covariance', the set's fill row as its mean and no votes.
+        Reproducible: the same bytes on every run.  One host read (the member capacity).  No autograd: outputs never require grad.
+        A clearance field has no sets: it returns the count and the geometry."""
+        dev = self.device
+        nx, ny, nz = self.grid_shape
+        if isinstance(components, Components):
+            if count is not None:
+                raise ValueError("pool: count comes with a label tensor; a Components knows its own")
+            if tuple(components.grid_shape) != tuple(self.grid_shape):
+                raise ValueError("pool: the components are of a grid %s, the field of %s" % (tuple(components.grid_shape), tuple(self.grid_shape)))
+            labels, K = components.labels, components.count
+        elif isinstance(components, torch.Tensor):
+            if count is None or isinstance(count, bool) or not isinstance(count, int) or count < 0:
+                raise ValueError("pool: a label tensor needs count=K, an integer >= 0, got %r" % (count,))
+            if components.dtype != torch.int32 or tuple(components.shape) != tuple(self.grid_shape):
+                raise ValueError("pool: labels must be an int32 tensor of shape %s, got %s %s" % (tuple(self.grid_shape), components.dtype, tuple(components.shape)))
+            labels, K = components.detach(), count
+        else:
+            raise ValueError("pool: components must be a Components or an int32 label tensor, got %r" % type(components).__name__)
+        if labels.device != dev:
+            raise RuntimeError("pool: the labels are on %s, the field on %s" % (labels.device, dev))
+        if K > nx * ny * nz:
+            raise ValueError("pool: count = %d exceeds the %d voxels" % (K, nx * ny * nz))
+        names, voted = self._names(return_names), self._names(list(votes))
+        wide = [k for k in voted if self._channels(k) > _lib.POOL_MAX_VOTE_CHANNELS]
+        if wide:
+            raise ValueError("pool: votes over %s: more than %d channels" % (wide, _lib.POOL_MAX_VOTE_CHANNELS))
+        keys = _POOL_KEYS + tuple(k + "_votes" for k in voted)
+        clash = [k for k in names if k in keys]
+        if clash:
+            raise ValueError("pool: the set(s) %s carry the name of an output key %s" % (clash, keys))
+        if len(names) + len(voted) > _lib.MAX_MAPS:
+            raise ValueError("pool: at most %d means and votes per call" % _lib.MAX_MAPS)
+        labels = labels.contiguous()
+        out = {"count": torch.empty(K, dtype=torch.int32, device=dev), "moments": torch.empty((K, 9), dtype=torch.int64, device=dev)}
+        for k in names:
+            out[k] = torch.empty((K, self._channels(k)), dtype=torch.float32, device=dev)
+        for k in voted:
+            out[k + "_votes"] = torch.empty((K, self._channels(k)), dtype=torch.int32, device=dev)
+        no_rows = self.band is not None and self.band_voxels.shape[0] == 0      # an empty band has no row arrays to point at, and no members
+        call = [] if no_rows else [(k, _lib.POOL_MEAN, out[k]) for k in names] + [(k, _lib.POOL_VOTES, out[k + "_votes"]) for k in voted]
+        sets = self._set_array([k for k, _, _ in call])
+        modes = (ctypes.c_int32 * max(len(call), 1))(*[m for _, m, _ in call])
+        rows = (ctypes.c_void_p * max(len(call), 1))(*[t.data_ptr() for _, _, t in call])
+        capacity = int((labels > 0).sum())
+        members = torch.empty(1, dtype=torch.int64, device=dev)
+        mean_channels = sum(self._channels(k) for k, m, _ in call if m == _lib.POOL_MEAN)
+        ws_bytes = int(self._lib.d3f_volume_pool_workspace_bytes(nx, ny, nz, K, capacity, mean_channels))
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+        valid = self.valid.contiguous().view(torch.uint8)
+        with torch.cuda.device(dev):
+            if K > 0:                                                    # (no component: every output is empty, there is nothing to point at)
+                _lib.check(self._lib.d3f_volume_pool(_lib.ptr(labels), nx, ny, nz, K, _lib.ptr(valid), _lib.ptr(self.slot), sets, len(call), modes, capacity,
+                                                     _lib.ptr(members), _lib.ptr(out["count"]), _lib.ptr(out["moments"]), rows, _lib.ptr(ws), ws_bytes,
+                                                     _lib.current_stream_handle(dev)))
+        if no_rows:
+            for k in names:
+                out[k] = self.fill_row(k).expand(K, -1).contiguous()
+            for k in voted:
+                out[k + "_votes"].zero_()
+        m = out["moments"].to(torch.float64)
+        n = out["count"].to(torch.float64)[:, None]
+        mean = m[:, 0:3] / n                                         # 0 / 0 = NaN for a component without members
+        second = m[:, [3, 4, 5, 4, 6, 7, 5, 7, 8]].view(K, 3, 3) / n[:, :, None]
+        origin = torch.tensor(self.origin, dtype=torch.float64, device=dev)
+        out["centroid"] = (origin + self.step * mean).to(torch.float32)
+        out["covariance"] = ((second - mean[:, :, None] * mean[:, None, :]) * (self.step * self.step)).to(torch.float32)
+        return out
 
     def clearance(self, iso=0.0, unknown="free", signed=False, max_distance=None, sites=None, min_voxels=1, connectivity=26):
         """The exact Euclidean distance from every voxel centre to the centre of the nearest SITE, as a new field (d3f_volume_edt).

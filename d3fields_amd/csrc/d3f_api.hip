@@ -871,6 +871,78 @@ int d3f_volume_components(const uint8_t *site, int32_t nx, int32_t ny, int32_t n
     return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_components launch");
 }
 
+// ---- mean rows, votes and moments per component (pool_kernels.hip) ----
+static bool pool_shape_ok(int32_t nx, int32_t ny, int32_t nz, int32_t K)
+{
+    return edt_shape_ok(nx, ny, nz) && (int64_t)K <= (int64_t)nx * ny * nz;
+}
+
+int64_t d3f_volume_pool_workspace_bytes(int32_t nx, int32_t ny, int32_t nz, int32_t K, int64_t member_capacity, int64_t mean_channels)
+{
+    if (K < 0 || member_capacity < 0 || mean_channels < 0 || mean_channels > (int64_t)D3F_MAX_MAPS * D3F_VOLUME_MAX_CHANNELS) return 0;
+    if (!pool_shape_ok(nx, ny, nz, K)) return 0;
+    return d3f::pool_workspace_bytes((int64_t)nx * ny * nz, K, member_capacity, mean_channels);
+}
+
+int d3f_volume_pool(const int32_t *label, int32_t nx, int32_t ny, int32_t nz, int32_t K, const uint8_t *valid, const int32_t *slot,
+                    const d3f_volume_set *sets, int32_t n_sets, const int32_t *modes, int64_t member_capacity, int64_t *out_members,
+                    int32_t *out_count, int64_t *out_moments, void *const *out_rows, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (!label || !out_members || !out_count) return fail(D3F_ERR_INVALID_ARG, "volume_pool: label, out_members or out_count is NULL");
+    if (K < 0) return fail(D3F_ERR_INVALID_ARG, "volume_pool: K=%d is negative", K);
+    if (n_sets < 0 || n_sets > D3F_MAX_MAPS) return fail(D3F_ERR_INVALID_ARG, "volume_pool: n_sets=%d outside [0,%d]", n_sets, D3F_MAX_MAPS);
+    if (n_sets > 0 && (!sets || !modes || !out_rows)) return fail(D3F_ERR_INVALID_ARG, "volume_pool: sets, modes or out_rows is NULL with n_sets=%d", n_sets);
+    for (int s = 0; s < n_sets; ++s) {
+        if (!sets[s].data || !out_rows[s]) return fail(D3F_ERR_INVALID_ARG, "volume_pool: set %d: data or out_rows[%d] is NULL", s, s);
+        if (modes[s] != D3F_POOL_MEAN && modes[s] != D3F_POOL_VOTES) return fail(D3F_ERR_INVALID_ARG, "volume_pool: set %d: unknown mode %d", s, modes[s]);
+    }
+    if (member_capacity < 0) return fail(D3F_ERR_INVALID_ARG, "volume_pool: member_capacity=%lld is negative", (long long)member_capacity);
+    if (!edt_shape_ok(nx, ny, nz))
+        return fail(D3F_ERR_BAD_SHAPE, "volume_pool: nx=%d ny=%d nz=%d, every extent must be in [1, %d] and the volume at most 2^31 - 1 voxels", nx, ny, nz,
+                    D3F_EDT_MAX_EXTENT);
+    if (!pool_shape_ok(nx, ny, nz, K)) return fail(D3F_ERR_BAD_SHAPE, "volume_pool: K=%d exceeds the %lld voxels", K, (long long)nx * ny * nz);
+    int64_t mean_channels = 0;
+    for (int s = 0; s < n_sets; ++s) {
+        if (sets[s].C < 1 || sets[s].C > D3F_VOLUME_MAX_CHANNELS)
+            return fail(D3F_ERR_BAD_SHAPE, "volume_pool: set %d: C=%d outside [1,%d]", s, sets[s].C, D3F_VOLUME_MAX_CHANNELS);
+        if (modes[s] == D3F_POOL_VOTES && sets[s].C > D3F_POOL_MAX_VOTE_CHANNELS)
+            return fail(D3F_ERR_BAD_SHAPE, "volume_pool: set %d: votes over C=%d channels, more than %d", s, sets[s].C, D3F_POOL_MAX_VOTE_CHANNELS);
+        if (modes[s] == D3F_POOL_MEAN) mean_channels += sets[s].C;
+    }
+    if (!aligned(label, 4) || !aligned(slot, 4) || !aligned(out_members, 8) || !aligned(out_count, 4) || !aligned(out_moments, 8))
+        return fail(D3F_ERR_BAD_LAYOUT, "volume_pool: label / slot / out_members / out_count / out_moments must be aligned to their element size");
+    for (int s = 0; s < n_sets; ++s) {
+        if (sets[s].stride_voxel < sets[s].C)
+            return fail(D3F_ERR_BAD_LAYOUT, "volume_pool: set %d: stride_voxel=%lld < C=%d", s, (long long)sets[s].stride_voxel, sets[s].C);
+        if (!aligned(sets[s].data, 4) || !aligned(sets[s].fill, 4) || !aligned(out_rows[s], 4))
+            return fail(D3F_ERR_BAD_LAYOUT, "volume_pool: set %d: data / fill / out_rows must be 4-byte aligned", s);
+    }
+    const int64_t need = d3f_volume_pool_workspace_bytes(nx, ny, nz, K, member_capacity, mean_channels);
+    if (!workspace || workspace_bytes < need) return fail(D3F_ERR_WORKSPACE, "volume_pool: needs %lld workspace bytes", (long long)need);
+    if (!aligned(workspace, 8)) return fail(D3F_ERR_BAD_LAYOUT, "volume_pool: workspace must be 8-byte aligned");
+    hipError_t e;
+    if (K == 0) {
+        e = d3f::launch_pool_nothing(out_members, static_cast<hipStream_t>(stream));
+    } else {
+        d3f::PoolArgs A;
+        A.label = label;
+        A.nx = nx; A.ny = ny; A.nz = nz; A.K = K;
+        A.valid = valid;
+        A.slot = slot;
+        A.sets = sets;
+        A.n_sets = n_sets;
+        A.modes = modes;
+        A.member_capacity = member_capacity;
+        A.out_members = out_members;
+        A.out_count = out_count;
+        A.out_moments = out_moments;
+        A.out_rows = out_rows;
+        A.workspace = workspace;
+        e = d3f::launch_volume_pool(A, static_cast<hipStream_t>(stream));
+    }
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_pool launch");
+}
+
 // ---- the first surface a ray meets in a baked volume (raycast_kernels.hip) ----
 int d3f_volume_raycast(const d3f_volume *vol, const float *origins, const float *dirs, int64_t n, const d3f_pinhole *camera,
                        float march_step, float t_near, float t_far, float *out_t, uint8_t *out_hit, float *out_points,

@@ -248,6 +248,27 @@ int64_t ccl_workspace_bytes(int64_t n);
 hipError_t launch_volume_components(const uint8_t *site, int nx, int ny, int nz, int connectivity, int min_voxels, int32_t *out_label, int32_t *out_count,
                                     int32_t *out_stats, int capacity, void *workspace, hipStream_t s);
 
+// pool_kernels.hip: mean rows, votes and moments of the baked field per component
+struct PoolArgs {
+    const int32_t *label;
+    int32_t nx, ny, nz, K;
+    const uint8_t *valid;        // or nullptr
+    const int32_t *slot;         // or nullptr
+    const d3f_volume_set *sets;  // host memory
+    int32_t n_sets;
+    const int32_t *modes;        // host memory
+    int64_t member_capacity;
+    int64_t *out_members;
+    int32_t *out_count;
+    int64_t *out_moments;        // or nullptr
+    void *const *out_rows;       // host memory
+    void *workspace;
+};
+int64_t pool_workspace_bytes(int64_t n, int64_t K, int64_t cap, int64_t mean_channels);
+int pool_levels(int64_t cap);                                       // fold levels a member capacity needs: 1..4
+hipError_t launch_volume_pool(const PoolArgs &A, hipStream_t s);
+hipError_t launch_pool_nothing(int64_t *out_members, hipStream_t s);   // K == 0: out_members = 0
+
 // raycast_kernels.hip: the first surface a ray meets in a baked volume
 constexpr float kRayMaxSamples = 131072.0f;  // a ray whose K exceeds this misses: unreachable under the entry point's 65536-step guard but for overflow
 struct RayParams {

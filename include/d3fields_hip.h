@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define D3F_ABI_VERSION 15
+#define D3F_ABI_VERSION 16
 
 #define D3F_OK 0
 #define D3F_ERR_INVALID_ARG (-1)  /* null pointer, negative count, bad enum               */
@@ -489,6 +489,51 @@ int d3f_volume_edt(const uint8_t *site, int32_t nx, int32_t ny, int32_t nz, floa
 int64_t d3f_volume_components_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
 int d3f_volume_components(const uint8_t *site, int32_t nx, int32_t ny, int32_t nz, int32_t connectivity, int32_t min_voxels, int32_t *out_label,
                           int32_t *out_count, int32_t *out_stats, int32_t stats_capacity, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* (ABI 16) Pool the baked field per component: mean rows, votes and coordinate moments.
+ *   label        int32 [nx,ny,nz], z fastest, as d3f_volume_components writes it; K >= 0 the number of components;
+ *   valid        NULL, or one byte per voxel, non-zero = valid;  slot: NULL, or the int32 volume of a band (d3f_band_mark), -1 = no row;
+ *   sets         n_sets sets as d3f_volume_sample takes them: the row of voxel v is data + v*stride_voxel, with `slot` it is
+ *                data + slot[v]*stride_voxel (slot values are trusted to address a row);  modes[s]: D3F_POOL_MEAN or D3F_POOL_VOTES.
+ * MEMBER: voxel v is a member of component k if label[v] == k with 1 <= k <= K, valid is NULL or valid[v] != 0, and slot is NULL or
+ * slot[v] >= 0.  A label outside 1..K (negative, K+1, INT32_MIN) is no member and never indexes anything.
+ * Always written:
+ *   out_members  ONE device int64: the total member count;
+ *   out_count    int32 [K]: the members of each component.
+ * Written when out_members <= member_capacity:
+ *   out_moments  (may be NULL) int64 [K,9] = {Sx, Sy, Sz, Sxx, Sxy, Sxz, Syy, Syz, Szz} over the members' integer voxel coordinates, exact
+ *                (extents <= 16384 and fewer than 2^31 voxels: nothing overflows);
+ *   out_rows[s]  D3F_POOL_MEAN: float32 [K,C], mean_k = fold(the rows of the members of k in ascending flat index) / (float)count_k.
+ *                fold is a radix-256 left-to-right tree: for a list of at most D3F_POOL_CHUNK = 256 rows it is ((r0 + r1) + r2) + ...,
+ *                every + one IEEE float32 add per channel, starting from r0 and not from zero (fold of one row is that row; -0.0 rows
+ *                pool to -0.0); a longer list is cut into consecutive chunks of 256 with a ragged last chunk, and fold is applied to
+ *                the list of the chunks' folds.  The division is IEEE, (float)count rounds to nearest.  Channels are independent: the
+ *                vector and the scalar row path (the alignment rule of d3f_volume_sample) give the same bits.
+ *                D3F_POOL_VOTES (C <= D3F_POOL_MAX_VOTE_CHANNELS): int32 [K,C], entry [k-1][c] = the members of k whose row has its
+ *                maximum at channel c by `best = 0; for c in 1..C-1: if row[c] > row[best]: best = c` -- ties go to the lowest
+ *                channel, a NaN never wins, a NaN at channel 0 stays.
+ * A component without members: count 0, zero moments, zero votes, the set's fill row (NULL: zeros) as its mean.
+ * Over capacity (out_members > member_capacity): only out_members and out_count are defined, the status is D3F_OK, and the caller runs
+ * again with room (the protocol of d3f_band_mark).  K == 0: D3F_OK, only out_members = 0 is written.
+ * No allocation, no synchronisation, the caller's stream; no float atomic anywhere (counts, votes and moments use integer adds): every
+ * output is a function of the input alone and two runs give identical bytes.  The member list is built by a prefix sum and a stable
+ * radix sort by label; one wave folds one chunk of 256 rows, the levels above fold the partial rows per component in chunk order; as
+ * many levels are launched as member_capacity allows (ceil(log256), at most 4).
+ * workspace: d3f_volume_pool_workspace_bytes(nx, ny, nz, K, member_capacity, mean_channels) with mean_channels the sum of C over the
+ * mean sets; 8-byte aligned, contents irrelevant; the function returns 0 exactly for arguments d3f_volume_pool rejects.
+ * Status errors, nothing launched: NULL label / out_members / out_count, K < 0, n_sets outside 0..D3F_MAX_MAPS, n_sets > 0 with NULL sets /
+ * modes / out_rows or a NULL data / out_rows entry, an unknown mode, member_capacity < 0 (D3F_ERR_INVALID_ARG); extents outside
+ * [1, D3F_EDT_MAX_EXTENT], more than 2^31 - 1 voxels, K above the voxel count, C outside 1..D3F_VOLUME_MAX_CHANNELS, a votes set with
+ * C > 256 (D3F_ERR_BAD_SHAPE); a pointer not aligned to its element, stride_voxel < C (D3F_ERR_BAD_LAYOUT); workspace NULL or too short
+ * (D3F_ERR_WORKSPACE). */
+#define D3F_POOL_MEAN 0
+#define D3F_POOL_VOTES 1
+#define D3F_POOL_CHUNK 256
+#define D3F_POOL_MAX_VOTE_CHANNELS 256
+int64_t d3f_volume_pool_workspace_bytes(int32_t nx, int32_t ny, int32_t nz, int32_t K, int64_t member_capacity, int64_t mean_channels);
+int d3f_volume_pool(const int32_t *label, int32_t nx, int32_t ny, int32_t nz, int32_t K, const uint8_t *valid, const int32_t *slot,
+                    const d3f_volume_set *sets, int32_t n_sets, const int32_t *modes, int64_t member_capacity, int64_t *out_members,
+                    int32_t *out_count, int64_t *out_moments, void *const *out_rows, void *workspace, int64_t workspace_bytes, void *stream);
 
 /* (ABI 12) The first surface a ray meets in a baked volume: a fixed-step march through `dist` with one linear interpolation at the
  * sign change.  Everything in fp32.  Ray i is p(t) = o + t*d; d need not be unit.
