@@ -152,6 +152,11 @@ SIGNATURES = {
     "d3f_volume_pool_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32, _i64, _i64]),
     "d3f_volume_pool": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, ctypes.POINTER(VolumeSet), _i32, ctypes.POINTER(_i32), _i64, _vp, _vp, _vp,
                                        ctypes.POINTER(_vp), _vp, _i64, _vp]),
+    "d3f_volume_geodesic_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "d3f_volume_geodesic_init": (ctypes.c_int, [_vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "d3f_volume_geodesic_relax": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, ctypes.POINTER(_i32), _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "d3f_volume_geodesic_finish": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, ctypes.POINTER(_i32), _f32, _vp, _vp, _vp, _vp]),
+    "d3f_volume_follow": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     "d3f_volume_raycast": (ctypes.c_int, [ctypes.POINTER(Volume), _vp, _vp, _i64, ctypes.POINTER(Pinhole), _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp]),
     "d3f_fps_workspace_bytes": (_i64, [_i64]),
     "d3f_fps_pixels_workspace_bytes": (_i64, [_i64]),

@@ -25,6 +25,11 @@ components are dropped by `min_voxels`, which `clearance(min_voxels=)` uses to k
 row of every baked set, hard votes over the channels of chosen sets, and each component's member count, centroid and covariance -- one
 call for all components, the same bytes on every run.
 
+`BakedField.travel(goals, radius=)` answers "how do I get there, and how far is it along the way": the cost-to-go field of a goal set
+through the free voxels (d3f_volume_geodesic_*, csrc/geodesic_kernels.hip) -- exact shortest lattice paths with
+integer weights, as a new field whose `dist` is the travel distance and whose `next_voxel` names the voxel to step to; `path(starts)`
+walks it (d3f_volume_follow).
+
 There is no CPU path: volumes and points live on the ROCm device.
 """
 import ctypes
@@ -161,6 +166,10 @@ class BakedField:
     A CLEARANCE field (clearance()) has no sets; its dist is the distance to the nearest site, and it has d2 int32 [nx, ny, nz] (squared
     voxel distance), nearest_voxel int32 (flat index of that site, -1: none), sites bool, and nearest_site(pts).  They are None elsewhere.
 
+    A TRAVEL field (travel()) has no sets; its dist is the travel distance to the nearest goal along the cheapest lattice path through the
+    free voxels, and it has cost int32 [nx, ny, nz] (INT32_MAX: unreached), next_voxel int32 (the flat index of the voxel to step to; the
+    voxel itself at a goal, -1: unreached), free bool, and path(starts).  They are None elsewhere.
+
     A BANDED field (to_band / Fusion.bake(band=)) holds each set as [M, C] rows of the stored voxels instead, and has
     band (the world length), slot int32 [nx, ny, nz] (-1: no row), cell_band uint8 [nx-1, ny-1, nz-1], band_voxels int32 [M]
     (ascending flat indices), band_points() and stored_fraction; its lookups add 'in_band'.  A dense field has band = None.
@@ -184,6 +193,7 @@ class BakedField:
         self._axes = axes                 # the three axis tensors of the grid that was baked (Fusion.bake), or None: origin + i * step
         self.band = self.slot = self.cell_band = self.band_voxels = None
         self.d2 = self.nearest_voxel = self.sites = None      # a clearance field's (clearance()); None on every other field
+        self.cost = self.next_voxel = self.free = None         # a travel field's (travel()); None on every other field
         self.cell_valid = torch.empty((nx - 1, ny - 1, nz - 1), dtype=torch.uint8, device=self.device)
         vol = self._volume()
         with torch.cuda.device(self.device):
@@ -692,6 +702,146 @@ class BakedField:
         ok = voxel >= 0
         centres = self._voxel_centres(torch.clamp(voxel, min=0))
         return {"voxel": voxel, "points": torch.where(ok[:, None], centres, torch.full_like(centres, float("nan"))), "valid_mask": ok}
+
+    # ---- travel ---------------------------------------------------------------------------------------------------------------
+    _TRAVEL_FIRST_ROUNDS, _TRAVEL_MAX_ROUNDS = 16, 256      # rounds per d3f_volume_geodesic_relax call: 16 first, doubling up to 256
+
+    def _voxel_indices(self, who, what, t):
+        """int32 [N] flat voxel indices of float32 [N, 3] points (the one voxel rule, _voxel_of) or of an int32 / int64 index tensor; -1
+        for a point outside or with a NaN and for an index outside the volume"""
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("%s: %s must be a tensor of float32 [N, 3] points or of int32 / int64 flat voxel indices" % (who, what))
+        if t.device != self.device:
+            raise RuntimeError("%s: %s is on %s, the field on %s" % (who, what, t.device, self.device))
+        nx, ny, nz = self.grid_shape
+        if t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == 3:
+            inside, flat = _voxel_of(t, self.origin, self.step, self.grid_shape)
+        elif t.dtype in (torch.int32, torch.int64) and t.dim() == 1:
+            flat = t.detach().long()
+            inside = (flat >= 0) & (flat < nx * ny * nz)
+        else:
+            raise ValueError("%s: %s must be float32 [N, 3] points or a 1-D int32 / int64 tensor of flat voxel indices, got %s %s"
+                             % (who, what, t.dtype, tuple(t.shape)))
+        return torch.where(inside, flat, torch.full_like(flat, -1)).to(torch.int32).contiguous()
+
+    def travel(self, goals, radius=None, free=None, connectivity=26, weights=(3, 4, 5), penalty=None, max_distance=None):
+        """The cost-to-go field of a goal set: in every free voxel the cost of the cheapest lattice path to the nearest goal and the
+        neighbour to step to next (d3f_volume_geodesic_init / _relax / _finish), as a new field.
+
+        goals         float32 [G, 3] points on the device (rounded to their voxel as nearest_site does; points outside or with a NaN are
+                      dropped), or an int32 / int64 tensor of flat voxel indices.  A goal on a non-free voxel is ignored.
+        radius        (a clearance field only) free = valid & (dist >= radius): the voxels a body of that radius fits into.
+        free          or an explicit bool / uint8 [nx, ny, nz] volume on this device (non-zero = traversable).  Exactly one of the two.
+        connectivity  6, 18 or 26: a move joins two free voxels that differ by at most 1 on every axis and by at most 1 / 2 / 3 in L1.
+        weights       (w1, w2, w3), integers with 1 <= w1 <= w2 <= w3 <= 255: the cost of a face / edge / corner move.  The default
+                      (3, 4, 5) under connectivity 26 keeps cost / (3 * Euclidean voxel distance) inside [0.9428, 1.1055] in open space.
+        penalty       None, or an int32 [nx, ny, nz] volume on this device, >= 0, added to the cost of every move INTO a voxel (negative
+                      entries count as 0; a goal's own penalty is never charged).
+        max_distance  a world length or None: max_cost = floor(max_distance * w1 / step) caps the cost; voxels beyond it stay unreached.
+                      Rejected if max_cost would be below 1.
+
+        -> a BakedField (origin, step, boundaries of this one, no sets) with dist float32 = cost * (step / w1) (+inf where unreached),
+        cost int32 (INT32_MAX where unreached), next_voxel int32, free bool; valid = cost != INT32_MAX, so eval never blends an inf: a cell
+        with an unreached corner is "not valid".  eval(pts)['dist'] is the trilinear travel distance and its negative gradient points
+        along the way to the goal, without local minima; path(starts) gives the discrete route.
+        Exact and reproducible: integer costs, the unique fixed point of the relaxation, the same bytes on every run.  One host read per
+        batch of rounds.  No autograd: outputs never require grad."""
+        who = "travel"
+        dev = self.device
+        nx, ny, nz = self.grid_shape
+        n = nx * ny * nz
+        if connectivity not in (6, 18, 26):
+            raise ValueError("travel: connectivity must be 6, 18 or 26, got %r" % (connectivity,))
+        try:
+            w = tuple(weights)
+        except TypeError:
+            raise ValueError("travel: weights must be three integers, got %r" % (weights,))
+        if len(w) != 3 or any(isinstance(x, bool) or not isinstance(x, int) for x in w) or not 1 <= w[0] <= w[1] <= w[2] <= 255:
+            raise ValueError("travel: weights must be integers with 1 <= w1 <= w2 <= w3 <= 255, got %r" % (weights,))
+        if (radius is None) == (free is None):
+            raise ValueError("travel: give exactly one of radius= (on a clearance field) and free=")
+        if radius is not None:
+            if self.nearest_voxel is None:
+                raise ValueError("travel: radius needs a clearance field (BakedField.clearance()); pass free= on any other field")
+            radius = float(radius)
+            if not math.isfinite(radius):
+                raise ValueError("travel: radius must be finite, got %r" % radius)
+            mask = self.valid & (self.dist >= radius)
+        else:
+            mask = self._site_mask(who, 0.0, "free", free)
+        if penalty is not None:
+            if not isinstance(penalty, torch.Tensor) or penalty.dtype != torch.int32 or tuple(penalty.shape) != tuple(self.grid_shape):
+                raise ValueError("travel: penalty must be an int32 tensor of shape %s" % (tuple(self.grid_shape),))
+            if penalty.device != dev:
+                raise RuntimeError("travel: penalty is on %s, the field on %s" % (penalty.device, dev))
+            penalty = penalty.detach().contiguous()
+        max_cost = 2 ** 31 - 2
+        if max_distance is not None:
+            max_distance = float(max_distance)
+            if not (math.isfinite(max_distance) and max_distance > 0.0):
+                raise ValueError("travel: max_distance must be a finite length > 0, got %r" % max_distance)
+            max_cost = min(math.floor(max_distance * w[0] / self.step), 2 ** 31 - 2)
+            if max_cost < 1:
+                raise ValueError("travel: max_distance = %g allows no move (step / w1 = %g)" % (max_distance, self.step / w[0]))
+        seeds = self._voxel_indices(who, "goals", goals)
+        seeds = seeds[seeds >= 0].contiguous()
+        mask = mask.contiguous()
+        site = mask.view(torch.uint8)
+        cost = torch.empty((nx, ny, nz), dtype=torch.int32, device=dev)
+        nxt = torch.empty((nx, ny, nz), dtype=torch.int32, device=dev)
+        dist = torch.empty((nx, ny, nz), dtype=torch.float32, device=dev)
+        pending = torch.empty(1, dtype=torch.int32, device=dev)
+        ws_bytes = int(self._lib.d3f_volume_geodesic_workspace_bytes(nx, ny, nz))
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+        warr = (ctypes.c_int32 * 3)(*w)
+        with torch.cuda.device(dev):
+            stream = _lib.current_stream_handle(dev)
+            _lib.check(self._lib.d3f_volume_geodesic_init(_lib.ptr(site), nx, ny, nz, _lib.ptr(seeds), seeds.shape[0], _lib.ptr(cost), _lib.ptr(ws),
+                                                          ws_bytes, stream))
+            rounds, total = self._TRAVEL_FIRST_ROUNDS, 0
+            while True:
+                _lib.check(self._lib.d3f_volume_geodesic_relax(_lib.ptr(site), _lib.ptr(penalty), nx, ny, nz, connectivity, warr, max_cost, rounds,
+                                                               _lib.ptr(cost), _lib.ptr(pending), _lib.ptr(ws), ws_bytes, stream))
+                total += rounds
+                if int(pending.item()) == 0:
+                    break
+                if total > n:      # after k rounds every voxel whose cheapest path has at most k moves is final: never reached
+                    raise RuntimeError("travel: the relaxation did not settle within %d rounds" % total)
+                rounds = min(2 * rounds, self._TRAVEL_MAX_ROUNDS)
+            _lib.check(self._lib.d3f_volume_geodesic_finish(_lib.ptr(site), _lib.ptr(penalty), nx, ny, nz, connectivity, warr, self.step, _lib.ptr(cost),
+                                                            _lib.ptr(nxt), _lib.ptr(dist), stream))
+        t = type(self)(self.origin, self.step, dist, cost != 2 ** 31 - 1, {}, {}, boundaries=self.boundaries, axes=self._axes)
+        t.cost, t.next_voxel, t.free = cost, nxt, mask
+        return t
+
+    def path(self, starts, max_steps=None):
+        """The discrete route from each start to its goal: a pointer walk along next_voxel (a travel field only; d3f_volume_follow).
+
+        starts     float32 [N, 3] points (rounded to their voxel; outside or NaN: an empty path) or an int32 / int64 tensor of flat indices
+        max_steps  the row length L (default nx + ny + nz); a path cut by it has reached = False and a full row
+        -> {'voxels': int32 [N, L] the visited flat indices, the start voxel first, padded with -1; 'length': int32 [N]; 'reached': bool [N]
+            (the walk arrived at a goal); 'points': float32 [N, L, 3] the voxel centres, NaN rows for the padding}.
+        An unreached start (not valid on this field) has length 0 and reached = False.  No autograd: outputs never require grad."""
+        if self.next_voxel is None:
+            raise ValueError("path: this is not a travel field; BakedField.travel() makes one")
+        dev = self.device
+        nx, ny, nz = self.grid_shape
+        if max_steps is None:
+            max_steps = nx + ny + nz
+        if isinstance(max_steps, bool) or not isinstance(max_steps, int) or not 1 <= max_steps <= 2 ** 31 - 1:
+            raise ValueError("path: max_steps must be an integer >= 1, got %r" % (max_steps,))
+        s = self._voxel_indices("path", "starts", starts)
+        N = s.shape[0]
+        voxels = torch.empty((N, max_steps), dtype=torch.int32, device=dev)
+        length = torch.empty(N, dtype=torch.int32, device=dev)
+        reached = torch.empty(N, dtype=torch.bool, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.d3f_volume_follow(_lib.ptr(self.next_voxel), nx * ny * nz, _lib.ptr(s), N, max_steps, _lib.ptr(voxels), _lib.ptr(length),
+                                                   _lib.ptr(reached), _lib.current_stream_handle(dev)))
+        flat = voxels.view(-1)
+        centres = self._voxel_centres(torch.clamp(flat, min=0))
+        points = torch.where((flat >= 0)[:, None], centres, torch.full_like(centres, float("nan"))).view(N, max_steps, 3)
+        return {"voxels": voxels, "length": length, "reached": reached, "points": points}
 
     # ---- rays -----------------------------------------------------------------------------------------------------------------
     def _check_rays(self, origins, dirs):

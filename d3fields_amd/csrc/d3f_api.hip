@@ -943,6 +943,89 @@ int d3f_volume_pool(const int32_t *label, int32_t nx, int32_t ny, int32_t nz, in
     return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_pool launch");
 }
 
+// ---- cost-to-go through free space (geodesic_kernels.hip) ----
+static const char *geo_weights_bad(int32_t connectivity, const int32_t *w)
+{
+    if (connectivity != 6 && connectivity != 18 && connectivity != 26) return "connectivity must be 6, 18 or 26";
+    if (!w) return "w is NULL";
+    if (!(1 <= w[0] && w[0] <= w[1] && w[1] <= w[2] && w[2] <= 255)) return "weights must satisfy 1 <= w1 <= w2 <= w3 <= 255";
+    return nullptr;
+}
+
+int64_t d3f_volume_geodesic_workspace_bytes(int32_t nx, int32_t ny, int32_t nz)
+{
+    return edt_shape_ok(nx, ny, nz) ? d3f::geodesic_workspace_bytes(nx, ny, nz) : 0;
+}
+
+int d3f_volume_geodesic_init(const uint8_t *free, int32_t nx, int32_t ny, int32_t nz, const int32_t *seeds, int64_t n_seeds, int32_t *out_cost,
+                             void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (!free || !out_cost) return fail(D3F_ERR_INVALID_ARG, "volume_geodesic_init: free or out_cost is NULL");
+    if (n_seeds < 0) return fail(D3F_ERR_INVALID_ARG, "volume_geodesic_init: n_seeds=%lld is negative", (long long)n_seeds);
+    if (n_seeds > 0 && !seeds) return fail(D3F_ERR_INVALID_ARG, "volume_geodesic_init: seeds is NULL with n_seeds=%lld", (long long)n_seeds);
+    if (!edt_shape_ok(nx, ny, nz))
+        return fail(D3F_ERR_BAD_SHAPE, "volume_geodesic_init: nx=%d ny=%d nz=%d, every extent must be in [1, %d] and the volume at most 2^31 - 1 voxels", nx,
+                    ny, nz, D3F_EDT_MAX_EXTENT);
+    if (!aligned(seeds, 4) || !aligned(out_cost, 4)) return fail(D3F_ERR_BAD_LAYOUT, "volume_geodesic_init: seeds / out_cost must be 4-byte aligned");
+    const int64_t need = d3f_volume_geodesic_workspace_bytes(nx, ny, nz);
+    if (!workspace || workspace_bytes < need) return fail(D3F_ERR_WORKSPACE, "volume_geodesic_init: needs %lld workspace bytes", (long long)need);
+    if (!aligned(workspace, 4)) return fail(D3F_ERR_BAD_LAYOUT, "volume_geodesic_init: workspace must be 4-byte aligned");
+    hipError_t e = d3f::launch_geodesic_init(free, nx, ny, nz, seeds, n_seeds, out_cost, workspace, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_geodesic_init launch");
+}
+
+int d3f_volume_geodesic_relax(const uint8_t *free, const int32_t *penalty, int32_t nx, int32_t ny, int32_t nz, int32_t connectivity, const int32_t *w,
+                              int32_t max_cost, int32_t rounds, int32_t *cost, int32_t *out_pending, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (!free || !cost || !out_pending) return fail(D3F_ERR_INVALID_ARG, "volume_geodesic_relax: free, cost or out_pending is NULL");
+    if (const char *bad = geo_weights_bad(connectivity, w)) return fail(D3F_ERR_INVALID_ARG, "volume_geodesic_relax: %s", bad);
+    if (max_cost < 1 || max_cost > 0x7ffffffe) return fail(D3F_ERR_INVALID_ARG, "volume_geodesic_relax: max_cost=%d outside [1, INT32_MAX - 1]", max_cost);
+    if (rounds < 1) return fail(D3F_ERR_INVALID_ARG, "volume_geodesic_relax: rounds=%d, must be >= 1", rounds);
+    if (!edt_shape_ok(nx, ny, nz))
+        return fail(D3F_ERR_BAD_SHAPE, "volume_geodesic_relax: nx=%d ny=%d nz=%d, every extent must be in [1, %d] and the volume at most 2^31 - 1 voxels", nx,
+                    ny, nz, D3F_EDT_MAX_EXTENT);
+    if (!aligned(penalty, 4) || !aligned(cost, 4) || !aligned(out_pending, 4))
+        return fail(D3F_ERR_BAD_LAYOUT, "volume_geodesic_relax: penalty / cost / out_pending must be 4-byte aligned");
+    const int64_t need = d3f_volume_geodesic_workspace_bytes(nx, ny, nz);
+    if (!workspace || workspace_bytes < need) return fail(D3F_ERR_WORKSPACE, "volume_geodesic_relax: needs %lld workspace bytes", (long long)need);
+    if (!aligned(workspace, 4)) return fail(D3F_ERR_BAD_LAYOUT, "volume_geodesic_relax: workspace must be 4-byte aligned");
+    hipError_t e = d3f::launch_geodesic_relax(free, penalty, nx, ny, nz, connectivity, w, max_cost, rounds, cost, out_pending, workspace,
+                                              static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_geodesic_relax launch");
+}
+
+int d3f_volume_geodesic_finish(const uint8_t *free, const int32_t *penalty, int32_t nx, int32_t ny, int32_t nz, int32_t connectivity, const int32_t *w,
+                               float step, const int32_t *cost, int32_t *out_next, float *out_dist, void *stream)
+{
+    if (!free || !cost) return fail(D3F_ERR_INVALID_ARG, "volume_geodesic_finish: free or cost is NULL");
+    if (!out_next && !out_dist) return fail(D3F_ERR_INVALID_ARG, "volume_geodesic_finish: out_next and out_dist are both NULL");
+    if (const char *bad = geo_weights_bad(connectivity, w)) return fail(D3F_ERR_INVALID_ARG, "volume_geodesic_finish: %s", bad);
+    if (out_dist && (!(step > 0.0f) || step * 0.0f != 0.0f)) return fail(D3F_ERR_INVALID_ARG, "volume_geodesic_finish: step must be > 0 and finite with out_dist");
+    if (!edt_shape_ok(nx, ny, nz))
+        return fail(D3F_ERR_BAD_SHAPE, "volume_geodesic_finish: nx=%d ny=%d nz=%d, every extent must be in [1, %d] and the volume at most 2^31 - 1 voxels", nx,
+                    ny, nz, D3F_EDT_MAX_EXTENT);
+    if (!aligned(penalty, 4) || !aligned(cost, 4) || !aligned(out_next, 4) || !aligned(out_dist, 4))
+        return fail(D3F_ERR_BAD_LAYOUT, "volume_geodesic_finish: penalty / cost / out_next / out_dist must be 4-byte aligned");
+    hipError_t e = d3f::launch_geodesic_finish(free, penalty, nx, ny, nz, connectivity, w, step, cost, out_next, out_dist, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_geodesic_finish launch");
+}
+
+int d3f_volume_follow(const int32_t *next, int64_t n_voxels, const int32_t *starts, int64_t n, int32_t max_steps, int32_t *out_voxels, int32_t *out_length,
+                      uint8_t *out_reached, void *stream)
+{
+    if (n < 0) return fail(D3F_ERR_INVALID_ARG, "volume_follow: n=%lld is negative", (long long)n);
+    if (max_steps < 1) return fail(D3F_ERR_INVALID_ARG, "volume_follow: max_steps=%d, must be >= 1", max_steps);
+    if (n > 0 && (!next || !starts || !out_voxels || !out_length || !out_reached))
+        return fail(D3F_ERR_INVALID_ARG, "volume_follow: next, starts, out_voxels, out_length or out_reached is NULL with n=%lld", (long long)n);
+    if (n_voxels < 1 || n_voxels > 0x7fffffffLL) return fail(D3F_ERR_BAD_SHAPE, "volume_follow: n_voxels=%lld outside [1, 2^31 - 1]", (long long)n_voxels);
+    if ((n + d3f::kBlock - 1) / d3f::kBlock > 0x7fffffffLL) return fail(D3F_ERR_BAD_SHAPE, "volume_follow: n=%lld too large for one launch", (long long)n);
+    if (!aligned(next, 4) || !aligned(starts, 4) || !aligned(out_voxels, 4) || !aligned(out_length, 4))
+        return fail(D3F_ERR_BAD_LAYOUT, "volume_follow: next / starts / out_voxels / out_length must be 4-byte aligned");
+    if (n == 0) return D3F_OK;
+    hipError_t e = d3f::launch_volume_follow(next, n_voxels, starts, n, max_steps, out_voxels, out_length, out_reached, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_follow launch");
+}
+
 // ---- the first surface a ray meets in a baked volume (raycast_kernels.hip) ----
 int d3f_volume_raycast(const d3f_volume *vol, const float *origins, const float *dirs, int64_t n, const d3f_pinhole *camera,
                        float march_step, float t_near, float t_far, float *out_t, uint8_t *out_hit, float *out_points,

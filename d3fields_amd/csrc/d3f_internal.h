@@ -269,6 +269,17 @@ int pool_levels(int64_t cap);                                       // fold leve
 hipError_t launch_volume_pool(const PoolArgs &A, hipStream_t s);
 hipError_t launch_pool_nothing(int64_t *out_members, hipStream_t s);   // K == 0: out_members = 0
 
+// geodesic_kernels.hip: cost-to-go through free space, exact shortest paths on the lattice; w: host int32[3]
+int64_t geodesic_workspace_bytes(int nx, int ny, int nz);
+hipError_t launch_geodesic_init(const uint8_t *free, int nx, int ny, int nz, const int32_t *seeds, int64_t n_seeds, int32_t *out_cost, void *workspace,
+                                hipStream_t s);
+hipError_t launch_geodesic_relax(const uint8_t *free, const int32_t *penalty, int nx, int ny, int nz, int connectivity, const int32_t *w, int32_t max_cost,
+                                 int rounds, int32_t *cost, int32_t *out_pending, void *workspace, hipStream_t s);
+hipError_t launch_geodesic_finish(const uint8_t *free, const int32_t *penalty, int nx, int ny, int nz, int connectivity, const int32_t *w, float step,
+                                  const int32_t *cost, int32_t *out_next, float *out_dist, hipStream_t s);
+hipError_t launch_volume_follow(const int32_t *next, int64_t n_voxels, const int32_t *starts, int64_t n, int max_steps, int32_t *out_voxels, int32_t *out_length,
+                                uint8_t *out_reached, hipStream_t s);
+
 // raycast_kernels.hip: the first surface a ray meets in a baked volume
 constexpr float kRayMaxSamples = 131072.0f;  // a ray whose K exceeds this misses: unreachable under the entry point's 65536-step guard but for overflow
 struct RayParams {

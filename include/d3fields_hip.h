@@ -535,6 +535,64 @@ int d3f_volume_pool(const int32_t *label, int32_t nx, int32_t ny, int32_t nz, in
                     const d3f_volume_set *sets, int32_t n_sets, const int32_t *modes, int64_t member_capacity, int64_t *out_members,
                     int32_t *out_count, int64_t *out_moments, void *const *out_rows, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* (still ABI 16: these symbols are ADDED, no struct or earlier entry point changes, and D3F_ABI_VERSION stays 16 -- a client detects the
+ * feature by the symbols.)  Cost-to-go through free space: exact shortest paths on the voxel lattice.
+ *   free         uint8 [nx,ny,nz], z fastest, non-zero = traversable: the site-volume convention of d3f_volume_edt and
+ *                d3f_volume_components;
+ *   neighbours   the spatial rule of d3f_volume_components: coordinates differ by at most 1 on every axis and by at most 1 / 2 / 3 in L1
+ *                for connectivity 6 / 18 / 26.  Nothing wraps through memory;
+ *   moves        a move between neighbours u, v exists when both are free.  It costs w[|u - v|_1 - 1] + penalty[v].  w = (w1, w2, w3)
+ *                (HOST int32[3]) are integers with 1 <= w1 <= w2 <= w3 <= 255, for face / edge / corner moves; only the first one or two
+ *                are used under 6 / 18 (all three are validated).  penalty is an optional int32 volume of values >= 0, charged for
+ *                entering v.  NULL means zero.  A negative entry is read as 0;
+ *   cost[v]      (int32) the minimum over all move sequences from any seed to v of the summed move costs.  A seed has cost 0; its own
+ *                penalty is not charged.  Seeds are int32 flat indices (x*ny + y)*nz + z; a seed that is out of range or on a non-free
+ *                voxel is ignored; duplicates are harmless.  A candidate is formed in unsigned arithmetic, so it never wraps; a candidate
+ *                above max_cost is discarded.  max_cost lies in 1..INT32_MAX - 1 (the top of that range = no cap).  The cap is
+ *                consistent because a prefix of a cheapest path is never dearer than the path.  An unreached voxel holds INT32_MAX;
+ *   next[v]      (int32) among the neighbours u with cost[u] + w(u, v) + penalty[v] == cost[v], the one with the smallest flat index.
+ *                For a seed it is v itself.  Unreached: -1.  It is computed from the final costs in a pass of its own and is therefore
+ *                a function of the input alone.  Because w1 >= 1, following it strictly lowers the cost, so it cannot cycle;
+ *   dist[v]      (float32) = (float)cost[v] * (step / (float)w1), each operation correctly rounded, and +inf where unreached.
+ * With integer weights the result is the unique fixed point of a min-plus relaxation: exact, independent of the order in which anything
+ * happens on the device, the same bytes on every run.  With w = (3, 4, 5) under connectivity 26 in open space, cost / (3 * Euclidean
+ * voxel distance) lies in [2 sqrt(2) / 3, sqrt(11) / 3] = [0.9428, 1.1055] (the chamfer distance 3a + b + c of an offset a >= b >= c >= 0:
+ * lowest along (1, 1, 0), highest along (3, 1, 1)).
+ *
+ * The solve is tile-local relaxation with an active-tile list; the caller drives it:
+ *   d3f_volume_geodesic_init    cost = INT32_MAX everywhere and 0 at the accepted seeds; the tiles that hold a seed or a neighbour of one are listed; every
+ *                               workspace word is initialised (its contents before the call are irrelevant);
+ *   d3f_volume_geodesic_relax   enqueues `rounds` rounds with no synchronisation and leaves in out_pending (ONE device int32) the number
+ *                               of tiles listed for the round after the last.  The caller reads that word and calls again until it is 0;
+ *                               then `cost` is final.  State lives in `cost` and the workspace only: the library keeps none.  free,
+ *                               penalty, the shape, connectivity, w and max_cost must be the same in every call of one solve.  A round
+ *                               with an empty list costs two empty launches.  After k rounds every voxel whose cheapest path has at most
+ *                               k moves is final, so nx*ny*nz rounds always suffice;
+ *   d3f_volume_geodesic_finish  next and dist from the final costs (each output may be NULL, not both);
+ *   d3f_volume_follow           one lane per start voxel walks `next` (int32 [n_voxels]) for at most max_steps steps: out_voxels int32
+ *                               [n, max_steps] = the visited flat indices, starting with the start voxel, padded with -1; out_length
+ *                               int32 [n] = the number written; out_reached uint8 [n] = 1 if a seed (next[v] == v) was reached.  A start
+ *                               of -1 (or any index outside 0..n_voxels-1), or one whose next is -1, writes length 0.  A path cut by
+ *                               max_steps has out_reached 0 and a full row.  n == 0: D3F_OK, nothing launched.
+ * No allocation, no synchronisation, the caller's stream; no atomic on a cost word, no float atomic.  Shapes as d3f_volume_edt: extents in
+ * [1, D3F_EDT_MAX_EXTENT] (an extent of 1 is legal: a 2-D image is nz = 1), at most 2^31 - 1 voxels.  workspace:
+ * d3f_volume_geodesic_workspace_bytes (a small header, one flag word and one list word per tile), 4-byte aligned; the function returns 0
+ * exactly for a rejected shape.
+ * Status errors, nothing launched: NULL free / out_cost / cost / out_pending, NULL next / starts / outputs of follow with n > 0, both
+ * outputs of finish NULL, connectivity not 6 / 18 / 26, w NULL or outside the rule above, max_cost outside 1..INT32_MAX - 1, rounds < 1,
+ * n_seeds < 0, NULL seeds with n_seeds > 0, n < 0, max_steps < 1, out_dist with a step that is not finite and > 0
+ * (D3F_ERR_INVALID_ARG); an extent outside [1, 16384], more than 2^31 - 1 voxels, n_voxels outside 1..2^31 - 1 (D3F_ERR_BAD_SHAPE); an
+ * int32 / float pointer or the workspace not 4-byte aligned (D3F_ERR_BAD_LAYOUT); workspace NULL or too short (D3F_ERR_WORKSPACE). */
+int64_t d3f_volume_geodesic_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
+int d3f_volume_geodesic_init(const uint8_t *free, int32_t nx, int32_t ny, int32_t nz, const int32_t *seeds, int64_t n_seeds, int32_t *out_cost,
+                             void *workspace, int64_t workspace_bytes, void *stream);
+int d3f_volume_geodesic_relax(const uint8_t *free, const int32_t *penalty, int32_t nx, int32_t ny, int32_t nz, int32_t connectivity, const int32_t *w,
+                              int32_t max_cost, int32_t rounds, int32_t *cost, int32_t *out_pending, void *workspace, int64_t workspace_bytes, void *stream);
+int d3f_volume_geodesic_finish(const uint8_t *free, const int32_t *penalty, int32_t nx, int32_t ny, int32_t nz, int32_t connectivity, const int32_t *w,
+                               float step, const int32_t *cost, int32_t *out_next, float *out_dist, void *stream);
+int d3f_volume_follow(const int32_t *next, int64_t n_voxels, const int32_t *starts, int64_t n, int32_t max_steps, int32_t *out_voxels, int32_t *out_length,
+                      uint8_t *out_reached, void *stream);
+
 /* (ABI 12) The first surface a ray meets in a baked volume: a fixed-step march through `dist` with one linear interpolation at the
  * sign change.  Everything in fp32.  Ray i is p(t) = o + t*d; d need not be unit.
  *   once per ray: go_a = (o_a - origin_a) / h, gd_a = d_a / h (IEEE divisions), len = sqrtf(fma(d_z, d_z, fma(d_y, d_y, d_x*d_x)));
