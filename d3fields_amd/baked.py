@@ -30,10 +30,16 @@ through the free voxels (d3f_volume_geodesic_*, csrc/geodesic_kernels.hip; DESIG
 integer weights, as a new field whose `dist` is the travel distance and whose `next_voxel` names the voxel to step to; `path(starts)`
 walks it (d3f_volume_follow).
 
+`BakedField.straight(a, b)` answers "can I go straight?": the exact grid segment between two voxels against a free volume
+(d3f_volume_segments, csrc/segment_kernels.hip) -- whether it is clear, how far it gets, what blocks it and, on a
+clearance field, how narrow it gets on the way; `shortcut(paths)` keeps only the waypoints of a route that cannot be skipped
+(d3f_path_shorten).
+
 There is no CPU path: volumes and points live on the ROCm device.
 """
 import ctypes
 import math
+import operator
 
 import torch
 
@@ -169,6 +175,8 @@ class BakedField:
     A TRAVEL field (travel()) has no sets; its dist is the travel distance to the nearest goal along the cheapest lattice path through the
     free voxels, and it has cost int32 [nx, ny, nz] (INT32_MAX: unreached), next_voxel int32 (the flat index of the voxel to step to; the
     voxel itself at a goal, -1: unreached), free bool, and path(starts).  They are None elsewhere.
+    straight(a, b) tests grid segments against a free volume (a travel field's own, radius= on a clearance field, free= anywhere);
+    shortcut(paths) keeps only the waypoints of a travel field's route that cannot be skipped.
 
     A BANDED field (to_band / Fusion.bake(band=)) holds each set as [M, C] rows of the stored voxels instead, and has
     band (the world length), slot int32 [nx, ny, nz] (-1: no row), cell_band uint8 [nx-1, ny-1, nz-1], band_voxels int32 [M]
@@ -842,6 +850,144 @@ class BakedField:
         centres = self._voxel_centres(torch.clamp(flat, min=0))
         points = torch.where((flat >= 0)[:, None], centres, torch.full_like(centres, float("nan"))).view(N, max_steps, 3)
         return {"voxels": voxels, "length": length, "reached": reached, "points": points}
+
+    # ---- straight segments ------------------------------------------------------------------------------------------------------
+    def _segment_free(self, who, radius, free):
+        """the bool free volume of straight: radius on a clearance field, free= anywhere, a travel field's own free by default"""
+        if radius is not None and free is not None:
+            raise ValueError("%s: give radius= (on a clearance field) or free=, not both" % who)
+        if radius is not None:
+            if self.nearest_voxel is None:
+                raise ValueError("%s: radius needs a clearance field (BakedField.clearance()); pass free= on any other field" % who)
+            radius = float(radius)
+            if not math.isfinite(radius):
+                raise ValueError("%s: radius must be finite, got %r" % (who, radius))
+            return self.valid & (self.dist >= radius)
+        if free is not None:
+            return self._site_mask(who, 0.0, "free", free)
+        if self.free is None:
+            raise ValueError("%s: give radius= (on a clearance field) or free=; only a travel field has a free volume of its own" % who)
+        return self.free
+
+    def _points_or_nan(self, voxel):
+        """float32 [..., 3] centres of int32 flat indices, NaN rows for -1"""
+        flat = voxel.reshape(-1)
+        centres = self._voxel_centres(torch.clamp(flat, min=0))
+        return torch.where((flat >= 0)[:, None], centres, torch.full_like(centres, float("nan"))).view(tuple(voxel.shape) + (3,))
+
+    def straight(self, a, b, radius=None, free=None, cut_corners=False):
+        """Can I go straight?  The grid segment between the voxels of a and b against a free volume (d3f_volume_segments).
+
+        a, b         float32 [N, 3] points (rounded to their voxel; outside or NaN: not clear) or int32 / int64 tensors of flat indices; one of
+                     them may have a single row and is then broadcast.
+        radius       (a clearance field only) free = valid & (dist >= radius);  free  or an explicit bool / uint8 [nx, ny, nz] volume.  At
+                     most one of the two; with neither, a travel field uses its own free volume and any other field raises.
+        cut_corners  False (default): a voxel is touched when its closed cube meets the segment, so a segment through a lattice edge or
+                     corner also needs the cubes round that point; True: the open cube, under which every move of path() is clear.
+        -> {'clear': bool [N]; 'last_voxel': int32 [N] the last voxel reached before the first blocked one (b itself if clear, -1 if a is
+            blocked or an end lies outside); 'blocked_voxel': int32 [N] (-1 if clear); 'points': float32 [N, 3] the centre of last_voxel, a
+            NaN row for -1}, and on a clearance field also 'min_d2': int32 [N] the smallest d2 over the voxels touched before the blocked
+            one (INT32_MAX: none), 'min_voxel': int32 [N] where it is, 'clearance': float32 [N] = float32(step * sqrt(float64(min_d2))),
+            inf where none -- how narrow it gets on the way.
+        Integer-exact, the same bytes on every run.  No autograd: outputs never require grad."""
+        who = "straight"
+        dev = self.device
+        nx, ny, nz = self.grid_shape
+        mask = self._segment_free(who, radius, free).contiguous()
+        va, vb = self._voxel_indices(who, "a", a), self._voxel_indices(who, "b", b)
+        if va.shape[0] != vb.shape[0]:
+            if va.shape[0] == 1:
+                va = va.expand(vb.shape[0]).contiguous()
+            elif vb.shape[0] == 1:
+                vb = vb.expand(va.shape[0]).contiguous()
+            else:
+                raise ValueError("straight: a has %d rows and b %d; they must agree, or one of them have a single row" % (va.shape[0], vb.shape[0]))
+        N = va.shape[0]
+        value = self.d2.contiguous() if self.d2 is not None else None
+        clear = torch.empty(N, dtype=torch.bool, device=dev)
+        last = torch.empty(N, dtype=torch.int32, device=dev)
+        blocked = torch.empty(N, dtype=torch.int32, device=dev)
+        min_d2 = torch.empty(N, dtype=torch.int32, device=dev) if value is not None else None
+        min_voxel = torch.empty(N, dtype=torch.int32, device=dev) if value is not None else None
+        flags = _lib.SEGMENT_CUT_CORNERS if cut_corners else 0
+        with torch.cuda.device(dev):
+            if N > 0:                                  # (an empty tensor has no address: nothing to ask)
+                _lib.check(self._lib.d3f_volume_segments(_lib.ptr(mask.view(torch.uint8)), _lib.ptr(value), nx, ny, nz, _lib.ptr(va), _lib.ptr(vb), N, flags,
+                                                         _lib.ptr(clear), _lib.ptr(last), _lib.ptr(blocked), _lib.ptr(min_d2), _lib.ptr(min_voxel),
+                                                         _lib.current_stream_handle(dev)))
+        out = {"clear": clear, "last_voxel": last, "blocked_voxel": blocked, "points": self._points_or_nan(last)}
+        if value is not None:
+            world = (torch.sqrt(min_d2.double()) * self.step).float()
+            out.update({"min_d2": min_d2, "min_voxel": min_voxel,
+                        "clearance": torch.where(min_d2 == 2 ** 31 - 1, torch.full_like(world, float("inf")), world)})
+        return out
+
+    def _row_lengths(self, voxels, keep):
+        """float64 [N]: the summed Euclidean voxel distances between the consecutive kept entries of each row (keep bool [N, L] marks a
+        prefix of every row)"""
+        nx, ny, nz = self.grid_shape
+        q = torch.clamp(voxels.long(), min=0)
+        xyz = torch.stack((q // (ny * nz), (q // nz) % ny, q % nz), dim=2)
+        d = xyz[:, 1:] - xyz[:, :-1]
+        hop = torch.sqrt((d * d).sum(dim=2).double())
+        return torch.where(keep[:, 1:], hop, torch.zeros_like(hop)).sum(dim=1)
+
+    def shortcut(self, paths, cut_corners=False, max_span=None):
+        """Keep only the waypoints of a route that cannot be skipped (a travel field only; d3f_path_shorten): from each kept
+        waypoint the route jumps to the farthest later one, at most max_span entries ahead, that it can reach by a clear straight segment
+        through this field's free volume, and to the next one if there is none.
+
+        paths        the dict path() returns ('voxels' int32 [N, L], 'length' int32 [N], 'reached'), or anything path() takes as starts
+        cut_corners  as in straight().  Under the default strict rule an edge or corner move of the route whose side voxels are not all
+                     free is not clear; it is kept all the same.
+        max_span     how many entries ahead a jump may look (default: the row length L, no limit); any integer type
+        -> {'voxels': int32 [N, L] the kept waypoints, padded with -1; 'index': int32 [N, L] their positions in the input row, padded
+            with -1; 'length': int32 [N]; 'reached': passed through; 'points': float32 [N, L, 3], NaN rows for the padding; 'distance',
+            'distance_before': float64 [N] = step times the summed Euclidean voxel distances between consecutive kept waypoints / between
+            consecutive voxels of the input row}.
+        A row made by hand may hold entries outside the volume inside its length (path() never writes one): they are kept as waypoints and
+        never jumped to, but the two distances then mean nothing for that row -- such an entry is measured as if it were voxel 0.
+        Integer-exact, the same bytes on every run.  No autograd: outputs never require grad."""
+        if self.next_voxel is None:
+            raise ValueError("shortcut: this is not a travel field; BakedField.travel() makes one")
+        if not isinstance(paths, dict):
+            paths = self.path(paths)
+        dev = self.device
+        nx, ny, nz = self.grid_shape
+        if not all(k in paths for k in ("voxels", "length", "reached")):
+            raise ValueError("shortcut: paths must be the dict path() returns, with 'voxels', 'length' and 'reached'")
+        rows, length = paths["voxels"], paths["length"]
+        if not isinstance(rows, torch.Tensor) or rows.dtype != torch.int32 or rows.dim() != 2 or rows.shape[1] < 1:
+            raise ValueError("shortcut: paths['voxels'] must be an int32 [N, L] tensor with L >= 1")
+        if not isinstance(length, torch.Tensor) or length.dtype != torch.int32 or tuple(length.shape) != (rows.shape[0],):
+            raise ValueError("shortcut: paths['length'] must be an int32 [N] tensor")
+        for what, t in (("voxels", rows), ("length", length)):
+            if t.device != dev:
+                raise RuntimeError("shortcut: paths['%s'] is on %s, the field on %s" % (what, t.device, dev))
+        N, L = rows.shape
+        if max_span is None:
+            max_span = L
+        try:                                           # any integer type (a NumPy integer, a 0-d integer tensor); not a bool, not a float
+            span = None if isinstance(max_span, bool) else operator.index(max_span)
+        except TypeError:
+            span = None
+        if span is None or not 1 <= span <= 2 ** 31 - 1:
+            raise ValueError("shortcut: max_span must be an integer >= 1, got %r" % (max_span,))
+        max_span = span
+        rows, length = rows.detach().contiguous(), length.detach().contiguous()
+        mask = self.free.contiguous()
+        voxels = torch.empty((N, L), dtype=torch.int32, device=dev)
+        index = torch.empty((N, L), dtype=torch.int32, device=dev)
+        count = torch.empty(N, dtype=torch.int32, device=dev)
+        flags = _lib.SEGMENT_CUT_CORNERS if cut_corners else 0
+        with torch.cuda.device(dev):
+            if N > 0:
+                _lib.check(self._lib.d3f_path_shorten(_lib.ptr(mask.view(torch.uint8)), nx, ny, nz, _lib.ptr(rows), _lib.ptr(length), N, L, max_span, flags,
+                                                      _lib.ptr(index), _lib.ptr(voxels), _lib.ptr(count), _lib.current_stream_handle(dev)))
+        at = torch.arange(L, device=dev)[None, :]
+        return {"voxels": voxels, "index": index, "length": count, "reached": paths["reached"], "points": self._points_or_nan(voxels),
+                "distance": self._row_lengths(voxels, at < count[:, None]) * self.step,
+                "distance_before": self._row_lengths(rows, at < torch.clamp(length, 0, L)[:, None]) * self.step}
 
     # ---- rays -----------------------------------------------------------------------------------------------------------------
     def _check_rays(self, origins, dirs):

@@ -1026,6 +1026,51 @@ int d3f_volume_follow(const int32_t *next, int64_t n_voxels, const int32_t *star
     return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_follow launch");
 }
 
+// ---- exact grid segments and shortcuts of voxel rows (segment_kernels.hip) ----
+int d3f_volume_segments(const uint8_t *free, const int32_t *value, int32_t nx, int32_t ny, int32_t nz, const int32_t *a, const int32_t *b, int64_t n,
+                        uint32_t flags, uint8_t *out_clear, int32_t *out_last, int32_t *out_blocked, int32_t *out_min_value, int32_t *out_min_voxel, void *stream)
+{
+    if (n < 0) return fail(D3F_ERR_INVALID_ARG, "volume_segments: n=%lld is negative", (long long)n);
+    if (flags & ~D3F_SEGMENT_CUT_CORNERS) return fail(D3F_ERR_INVALID_ARG, "volume_segments: unknown flag bits 0x%x", flags & ~D3F_SEGMENT_CUT_CORNERS);
+    if (n > 0 && (!free || !a || !b)) return fail(D3F_ERR_INVALID_ARG, "volume_segments: free, a or b is NULL with n=%lld", (long long)n);
+    if (!out_clear && !out_last && !out_blocked && !out_min_value && !out_min_voxel)
+        return fail(D3F_ERR_INVALID_ARG, "volume_segments: every output is NULL");
+    if (!value && (out_min_value || out_min_voxel)) return fail(D3F_ERR_INVALID_ARG, "volume_segments: out_min_value / out_min_voxel need value");
+    if (!edt_shape_ok(nx, ny, nz))
+        return fail(D3F_ERR_BAD_SHAPE, "volume_segments: nx=%d ny=%d nz=%d, every extent must be in [1, %d] and the volume at most 2^31 - 1 voxels", nx, ny, nz,
+                    D3F_EDT_MAX_EXTENT);
+    if ((n + d3f::kBlock - 1) / d3f::kBlock > 0x7fffffffLL) return fail(D3F_ERR_BAD_SHAPE, "volume_segments: n=%lld too large for one launch", (long long)n);
+    if (!aligned(value, 4) || !aligned(a, 4) || !aligned(b, 4) || !aligned(out_last, 4) || !aligned(out_blocked, 4) || !aligned(out_min_value, 4) ||
+        !aligned(out_min_voxel, 4))
+        return fail(D3F_ERR_BAD_LAYOUT, "volume_segments: value / a / b / out_last / out_blocked / out_min_value / out_min_voxel must be 4-byte aligned");
+    if (n == 0) return D3F_OK;
+    hipError_t e = d3f::launch_volume_segments(free, value, nx, ny, nz, a, b, n, !(flags & D3F_SEGMENT_CUT_CORNERS), out_clear, out_last, out_blocked,
+                                               out_min_value, out_min_voxel, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_segments launch");
+}
+
+int d3f_path_shorten(const uint8_t *free, int32_t nx, int32_t ny, int32_t nz, const int32_t *voxels, const int32_t *length, int64_t n, int32_t row_len,
+                     int32_t max_span, uint32_t flags, int32_t *out_index, int32_t *out_voxels, int32_t *out_count, void *stream)
+{
+    if (n < 0) return fail(D3F_ERR_INVALID_ARG, "path_shorten: n=%lld is negative", (long long)n);
+    if (row_len < 1) return fail(D3F_ERR_INVALID_ARG, "path_shorten: row_len=%d, must be >= 1", row_len);
+    if (max_span < 1) return fail(D3F_ERR_INVALID_ARG, "path_shorten: max_span=%d, must be >= 1", max_span);
+    if (flags & ~D3F_SEGMENT_CUT_CORNERS) return fail(D3F_ERR_INVALID_ARG, "path_shorten: unknown flag bits 0x%x", flags & ~D3F_SEGMENT_CUT_CORNERS);
+    if (n > 0 && (!free || !voxels || !length)) return fail(D3F_ERR_INVALID_ARG, "path_shorten: free, voxels or length is NULL with n=%lld", (long long)n);
+    if (!out_count) return fail(D3F_ERR_INVALID_ARG, "path_shorten: out_count is NULL");
+    if (!out_index && !out_voxels) return fail(D3F_ERR_INVALID_ARG, "path_shorten: out_index and out_voxels are both NULL");
+    if (!edt_shape_ok(nx, ny, nz))
+        return fail(D3F_ERR_BAD_SHAPE, "path_shorten: nx=%d ny=%d nz=%d, every extent must be in [1, %d] and the volume at most 2^31 - 1 voxels", nx, ny, nz,
+                    D3F_EDT_MAX_EXTENT);
+    if ((n + 3) / 4 > 0x7fffffffLL) return fail(D3F_ERR_BAD_SHAPE, "path_shorten: n=%lld too large for one launch", (long long)n);
+    if (!aligned(voxels, 4) || !aligned(length, 4) || !aligned(out_index, 4) || !aligned(out_voxels, 4) || !aligned(out_count, 4))
+        return fail(D3F_ERR_BAD_LAYOUT, "path_shorten: voxels / length / out_index / out_voxels / out_count must be 4-byte aligned");
+    if (n == 0) return D3F_OK;
+    hipError_t e = d3f::launch_path_shorten(free, nx, ny, nz, voxels, length, n, row_len, max_span, !(flags & D3F_SEGMENT_CUT_CORNERS), out_index, out_voxels,
+                                            out_count, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "path_shorten launch");
+}
+
 // ---- the first surface a ray meets in a baked volume (raycast_kernels.hip) ----
 int d3f_volume_raycast(const d3f_volume *vol, const float *origins, const float *dirs, int64_t n, const d3f_pinhole *camera,
                        float march_step, float t_near, float t_far, float *out_t, uint8_t *out_hit, float *out_points,

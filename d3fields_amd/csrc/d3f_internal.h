@@ -280,6 +280,12 @@ hipError_t launch_geodesic_finish(const uint8_t *free, const int32_t *penalty, i
 hipError_t launch_volume_follow(const int32_t *next, int64_t n_voxels, const int32_t *starts, int64_t n, int max_steps, int32_t *out_voxels, int32_t *out_length,
                                 uint8_t *out_reached, hipStream_t s);
 
+// segment_kernels.hip: exact grid segments through a free volume and shortcuts of voxel rows
+hipError_t launch_volume_segments(const uint8_t *free, const int32_t *value, int nx, int ny, int nz, const int32_t *a, const int32_t *b, int64_t n, bool strict,
+                                  uint8_t *out_clear, int32_t *out_last, int32_t *out_blocked, int32_t *out_min_value, int32_t *out_min_voxel, hipStream_t s);
+hipError_t launch_path_shorten(const uint8_t *free, int nx, int ny, int nz, const int32_t *voxels, const int32_t *length, int64_t n, int row_len, int max_span,
+                               bool strict, int32_t *out_index, int32_t *out_voxels, int32_t *out_count, hipStream_t s);
+
 // raycast_kernels.hip: the first surface a ray meets in a baked volume
 constexpr float kRayMaxSamples = 131072.0f;  // a ray whose K exceeds this misses: unreachable under the entry point's 65536-step guard but for overflow
 struct RayParams {

@@ -593,6 +593,52 @@ int d3f_volume_geodesic_finish(const uint8_t *free, const int32_t *penalty, int3
 int d3f_volume_follow(const int32_t *next, int64_t n_voxels, const int32_t *starts, int64_t n, int32_t max_steps, int32_t *out_voxels, int32_t *out_length,
                       uint8_t *out_reached, void *stream);
 
+/* (still ABI 16: these symbols are ADDED, no struct or earlier entry point changes, and D3F_ABI_VERSION stays 16 -- a client detects the
+ * feature by the symbols.)  Can I go straight?  Exact grid segments through a free volume, and shortcuts of voxel rows.
+ *   free         uint8 [nx,ny,nz], z fastest, non-zero = traversable: the volume of d3f_volume_geodesic_*;
+ *   segment      voxel centres sit at the integer coordinates of index space; for two voxels a, b (int32 flat indices (x*ny + y)*nz + z)
+ *                the segment is {a + t (b - a), 0 <= t <= 1};
+ *   touched      strict (default): the closed cube [v - 1/2, v + 1/2]^3 meets the segment -- the supercover: where the segment passes
+ *                exactly through an edge or a corner of the lattice, every cube round that point counts.  D3F_SEGMENT_CUT_CORNERS: the
+ *                open cube meets it.  The ends are integers, so a segment never runs inside a face plane and the two rules differ only at
+ *                isolated edge and corner crossings.  Under the open rule every move of a d3f_volume_follow path touches its two ends only;
+ *                under the strict rule an edge move also touches its 2 side voxels and a corner move its 6.  Every touched voxel lies in the
+ *                box spanned by a and b: nothing outside the volume is ever read;
+ *   the walk     all in int32 ((2k + 1) * n < 2^29 for extents up to 16384).  n_i = |b_i - a_i|, s_i = sign(b_i - a_i), k_i = 0, cur = a.
+ *                Axis i crosses its next plane at t_i = (2 k_i + 1) / (2 n_i); two such values are compared by cross-multiplication.
+ *                Event 0 touches {a}.  Every further event takes the set E of the axes with k_i < n_i that share the smallest t_i; under the
+ *                strict rule with |E| >= 2 it touches cur + sum of s_i e_i over every non-empty proper subset of E (2 side voxels for
+ *                |E| = 2, 6 for |E| = 3); then cur and k advance on all of E and the event touches the new cur.  There are at most
+ *                n_x + n_y + n_z + 1 events, their union is the touched set of the rule, and they come in non-decreasing t.
+ * d3f_volume_segments, per segment i of n (every output may be NULL, not all of them):
+ *   out_clear      uint8: 1 when every touched voxel is free;
+ *   out_last       int32: cur of the last event before the first event that touches a non-free voxel; b if the segment is clear, -1 if
+ *                  event 0 is already blocked;
+ *   out_blocked    int32: the smallest flat index among the non-free voxels of that first blocking event, -1 if clear;
+ *   out_min_value, out_min_voxel   (only with `value`, an int32 [nx,ny,nz] volume such as the clearance field's d2) the minimum of value over
+ *                  all voxels touched by the events before the first blocking event (all events if clear) and where it is taken: among equal
+ *                  minima the earliest event wins, then the smallest flat index within that event.  INT32_MAX and -1 if event 0 is blocked;
+ *   an a or b outside 0 .. nx*ny*nz - 1 gives clear = 0, last = blocked = min_voxel = -1, min_value = INT32_MAX.
+ * d3f_path_shorten, per row r of n: voxels int32 [n, row_len] holds p_0 .. p_{L-1}, L = length[r] clamped into 0 .. row_len (what follows is
+ *   not read).  Anchors: i_0 = 0; from anchor i the next anchor is the LARGEST j in i + 1 .. min(L - 1, i + max_span) whose segment
+ *   (p_i, p_j) is clear, and j = i + 1 if there is none (an original move is always kept, clear or not); until L - 1.  Visibility along a
+ *   row is not monotone: a nearer j may be blocked while a farther one is clear.  out_index int32 [n, row_len] = the positions
+ *   i_0 < i_1 < ..., padded with -1; out_voxels int32 [n, row_len] = the p at those positions, padded with -1 (one of the two may be NULL);
+ *   out_count int32 [n].  L = 0 gives count 0, L = 1 count 1.  A row need not be a lattice path: any sequence of indices is legal, and an
+ *   entry outside the volume is never the end of a clear segment.
+ * One lane per segment; one wave per row, the candidates of an anchor in chunks of 64 from the far end inwards.  No allocation, no
+ * synchronisation, no workspace, no atomics, the caller's stream; every loop is bounded by nx + ny + nz, ceil(max_span / 64) and L.
+ * Integer-exact: the same bytes on every run.
+ * Status errors, nothing launched: NULL free / a / b / voxels / length with n > 0, every output of d3f_volume_segments NULL, out_min_value
+ * or out_min_voxel without value, NULL out_count, out_voxels and out_index both NULL, unknown flag bits, n < 0, row_len < 1, max_span < 1
+ * (D3F_ERR_INVALID_ARG); an extent outside [1, 16384], more than 2^31 - 1 voxels, more segments or rows than one launch holds
+ * (D3F_ERR_BAD_SHAPE); an int32 pointer not 4-byte aligned (D3F_ERR_BAD_LAYOUT).  n == 0: D3F_OK, nothing launched. */
+#define D3F_SEGMENT_CUT_CORNERS 1u
+int d3f_volume_segments(const uint8_t *free, const int32_t *value, int32_t nx, int32_t ny, int32_t nz, const int32_t *a, const int32_t *b, int64_t n,
+                        uint32_t flags, uint8_t *out_clear, int32_t *out_last, int32_t *out_blocked, int32_t *out_min_value, int32_t *out_min_voxel, void *stream);
+int d3f_path_shorten(const uint8_t *free, int32_t nx, int32_t ny, int32_t nz, const int32_t *voxels, const int32_t *length, int64_t n, int32_t row_len,
+                     int32_t max_span, uint32_t flags, int32_t *out_index, int32_t *out_voxels, int32_t *out_count, void *stream);
+
 /* (ABI 12) The first surface a ray meets in a baked volume: a fixed-step march through `dist` with one linear interpolation at the
  * sign change.  Everything in fp32.  Ray i is p(t) = o + t*d; d need not be unit.
  *   once per ray: go_a = (o_a - origin_a) / h, gd_a = d_a / h (IEEE divisions), len = sqrtf(fma(d_z, d_z, fma(d_y, d_y, d_x*d_x)));
