@@ -34,6 +34,7 @@ VOLUME_MAX_CHANNELS = 4096
 RAYCAST_MAX_STEPS = 65536
 EDT_MAX_EXTENT = 16384
 SEGMENT_CUT_CORNERS = 1
+PEAKS_MAX_RADIUS = 8
 POOL_MEAN, POOL_VOTES = 0, 1
 POOL_CHUNK = 256
 POOL_MAX_VOTE_CHANNELS = 256
@@ -160,6 +161,7 @@ SIGNATURES = {
     "d3f_volume_follow": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     "d3f_volume_segments": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _i64, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "d3f_path_shorten": (ctypes.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _u32, _vp, _vp, _vp, _vp]),
+    "d3f_volume_peaks": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i64, _i32, _i64, _i32, _f32, _vp, _i64, _vp, _vp, _i64, _vp]),
     "d3f_volume_raycast": (ctypes.c_int, [ctypes.POINTER(Volume), _vp, _vp, _i64, ctypes.POINTER(Pinhole), _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp]),
     "d3f_fps_workspace_bytes": (_i64, [_i64]),
     "d3f_fps_pixels_workspace_bytes": (_i64, [_i64]),

@@ -35,6 +35,10 @@ walks it (d3f_volume_follow).
 clearance field, how narrow it gets on the way; `shortcut(paths)` keeps only the waypoints of a route that cannot be skipped
 (d3f_path_shorten).
 
+`BakedField.peaks(values)` answers "where are the optima?": exact, order-independent non-maximum suppression of K value columns through
+the slot volume (d3f_volume_peaks, csrc/peaks_kernels.hip) and the k best survivors per column, with a sub-voxel
+refinement; `locate(descriptors, name)` runs it on the descriptor distances of a set: where in this observation are these descriptors?
+
 There is no CPU path: volumes and points live on the ROCm device.
 """
 import ctypes
@@ -177,6 +181,8 @@ class BakedField:
     voxel itself at a goal, -1: unreached), free bool, and path(starts).  They are None elsewhere.
     straight(a, b) tests grid segments against a free volume (a travel field's own, radius= on a clearance field, free= anywhere);
     shortcut(paths) keeps only the waypoints of a travel field's route that cannot be skipped.
+    peaks(values, ...) gives the spatially distinct local optima of value columns on any field; locate(descriptors, name, ...) the k best
+    spatially distinct matches of reference descriptors among the rows of a set.
 
     A BANDED field (to_band / Fusion.bake(band=)) holds each set as [M, C] rows of the stored voxels instead, and has
     band (the world length), slot int32 [nx, ny, nz] (-1: no row), cell_band uint8 [nx-1, ny-1, nz-1], band_voxels int32 [M]
@@ -988,6 +994,214 @@ class BakedField:
         return {"voxels": voxels, "index": index, "length": count, "reached": paths["reached"], "points": self._points_or_nan(voxels),
                 "distance": self._row_lengths(voxels, at < count[:, None]) * self.step,
                 "distance_before": self._row_lengths(rows, at < torch.clamp(length, 0, L)[:, None]) * self.step}
+
+    # ---- peaks ----------------------------------------------------------------------------------------------------------------
+    def _peak_radius(self, who, radius_voxels, separation):
+        """r of peaks / locate from exactly one of radius_voxels and separation (a world length: r = max(1, ceil(separation / step) - 1)
+        in float64, so that two peaks lie at least `separation` apart along some axis)"""
+        if (radius_voxels is None) == (separation is None):
+            raise ValueError("%s: give exactly one of radius_voxels and separation" % who)
+        if separation is not None:
+            sep = float(separation)
+            if not (sep > 0.0 and math.isfinite(sep)):
+                raise ValueError("%s: separation must be a finite length > 0, got %r" % (who, separation))
+            r = max(1, int(math.ceil(sep / self.step)) - 1)
+        else:
+            try:
+                r = None if isinstance(radius_voxels, bool) else operator.index(radius_voxels)
+            except TypeError:
+                r = None
+            if r is None or r < 1:
+                raise ValueError("%s: radius_voxels must be an integer >= 1, got %r" % (who, radius_voxels))
+        if r > _lib.PEAKS_MAX_RADIUS:
+            raise ValueError("%s: a suppression radius of %d voxels is not built; the largest is %d (separation <= %g at this step)"
+                             % (who, r, _lib.PEAKS_MAX_RADIUS, (_lib.PEAKS_MAX_RADIUS + 1) * self.step))
+        return r
+
+    def _peak_mask(self, who, mask):
+        if mask is None:
+            return None
+        if not isinstance(mask, torch.Tensor) or tuple(mask.shape) != tuple(self.grid_shape) or mask.dtype not in (torch.bool, torch.uint8):
+            raise ValueError("%s: mask must be a bool or uint8 tensor of shape %s" % (who, tuple(self.grid_shape)))
+        if mask.device != self.device:
+            raise RuntimeError("%s: mask is on %s, the field on %s" % (who, mask.device, self.device))
+        return mask.detach().contiguous().view(torch.uint8)
+
+    @staticmethod
+    def _peak_k(who, k):
+        try:
+            kk = None if isinstance(k, bool) else operator.index(k)
+        except TypeError:
+            kk = None
+        if kk is None or not 1 <= kk <= 8:
+            raise ValueError("%s: k must be an integer in 1..8 (more is not built), got %r" % (who, k))
+        return kk
+
+    def _peaks_rows(self, work, rows_banded, r, k, threshold, mask, refine):
+        """peaks of the columns of work float32 [M, K] (contiguous; minima): d3f_volume_peaks, d3f_topk_smallest, the rows' voxels, and the
+        refinement -> (voxel int32 [K, k], value float32 [K, k], count int32 [K], offset float64 [K, k, 3] in voxel units or None)"""
+        dev = self.device
+        nx, ny, nz = self.grid_shape
+        M, K = work.shape
+        if K == 0:                                     # no column: nothing is launched
+            return (torch.empty((0, k), dtype=torch.int32, device=dev), torch.empty((0, k), dtype=torch.float32, device=dev),
+                    torch.empty(0, dtype=torch.int32, device=dev), torch.empty((0, k, 3), dtype=torch.float64, device=dev) if refine else None)
+        slot = self.slot if rows_banded else None
+        sup = torch.empty((M, K), dtype=torch.float32, device=dev)
+        count = torch.zeros(K, dtype=torch.int32, device=dev)
+        idx = torch.full((k, K), -1, dtype=torch.int64, device=dev)
+        val = torch.full((k, K), float("inf"), dtype=torch.float32, device=dev)
+        if M > 0:                                      # (an empty tensor has no address: nothing to ask)
+            ws_bytes = int(self._lib.d3f_pairwise_topk_workspace_bytes(M, K))
+            ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+            with torch.cuda.device(dev):
+                stream = _lib.current_stream_handle(dev)
+                _lib.check(self._lib.d3f_volume_peaks(_lib.ptr(slot), _lib.ptr(mask), nx, ny, nz, _lib.ptr(work), M, K, K, r, threshold, _lib.ptr(sup), K,
+                                                      _lib.ptr(count), None, 0, stream))
+                _lib.check(self._lib.d3f_topk_smallest(_lib.ptr(sup), M, K, k, _lib.ptr(idx), _lib.ptr(val), _lib.ptr(ws), ws_bytes, stream))
+        idx, val = idx.t().contiguous(), val.t().contiguous()
+        hit = (idx >= 0) & (val < float("inf"))       # fewer than k peaks: the list goes on with rows that hold +Inf (or, with M < k, none)
+        row = torch.where(hit, idx, torch.zeros_like(idx))
+        value = torch.where(hit, val, torch.full_like(val, float("inf")))
+        if M == 0:
+            flat = row
+        else:
+            flat = self.band_voxels.long()[row] if rows_banded else row
+        voxel = torch.where(hit, flat, torch.full_like(flat, -1)).to(torch.int32)
+        offset = None
+        if refine:
+            offset = self._peak_offsets(work, slot, mask, flat, row, hit)
+        return voxel, value, count, offset
+
+    def _peak_offsets(self, work, slot, mask, flat, row, hit):
+        """float64 [K, k, 3]: per axis 0.5 (f- - f+) / (f- - 2 f0 + f+) at the hits, clamped to [-0.5, 0.5]; 0 where a neighbour does not take
+        part or lies outside the volume, 0 where the denominator is not > 0; NaN rows where `hit` is false.  Plain float64 torch on K*k hits."""
+        nx, ny, nz = self.grid_shape
+        K, k = flat.shape
+        col = torch.arange(K, device=self.device)[:, None].expand(K, k)
+        inf = float("inf")
+        if work.shape[0] == 0:
+            return torch.full((K, k, 3), float("nan"), dtype=torch.float64, device=self.device)
+        f0 = work[row, col].double()
+        coords = (flat // (ny * nz), (flat // nz) % ny, flat % nz)
+        offs = []
+        for a, (n, stride) in enumerate(((nx, ny * nz), (ny, nz), (nz, 1))):
+            side = []
+            for sign in (-1, 1):
+                c = coords[a] + sign
+                inside = hit & (c >= 0) & (c < n)
+                u = torch.where(inside, flat + sign * stride, torch.zeros_like(flat))
+                m = u if slot is None else slot.view(-1)[u].long()
+                part = inside & (m >= 0)
+                if mask is not None:
+                    part = part & (mask.view(-1)[u] != 0)
+                f = work[torch.clamp(m, min=0), col]
+                part = part & (f < inf)
+                side.append((f.double(), part))
+            (fm, pm), (fp, pp) = side
+            den = fm - 2.0 * f0 + fp
+            off = torch.clamp(0.5 * (fm - fp) / den, -0.5, 0.5)
+            offs.append(torch.where(pm & pp & (den > 0), off, torch.zeros_like(off)))
+        out = torch.stack(offs, dim=2)
+        return torch.where(hit[..., None], out, torch.full_like(out, float("nan")))
+
+    def _peaks_result(self, key, voxel, value, count, offset, largest):
+        points = self._points_or_nan(voxel)
+        out = {"voxel": voxel, key: -value if largest else value, "points": points, "count": count}
+        if offset is not None:
+            out["refined"] = points.double() + offset * self.step
+        return out
+
+    def peaks(self, values, radius_voxels=None, separation=None, k=8, threshold=None, largest=False, mask=None, refine=True):
+        """Spatially distinct local optima of K value columns: exact, order-independent non-maximum suppression (d3f_volume_peaks,
+        csrc/peaks_kernels.hip) and the k best survivors per column (d3f_topk_smallest).
+
+        values         float32 [nx, ny, nz] or [nx, ny, nz, K] on any field; on a banded field also [M] or [M, K], one row per stored voxel
+                       (voxels without a row then take no part)
+        radius_voxels  the suppression radius r in voxels, 1..8; or  separation  a world length: r = max(1, ceil(separation / step) - 1),
+                       so that two peaks lie at least `separation` apart along some axis.  Exactly one of the two; r > 8 is not built.
+        k              how many peaks per column to return, 1..8;   threshold   only peaks with value <= threshold (>= under largest)
+        largest        False: minima.  True: maxima (the values are negated on the way in and out, which is exact)
+        mask           bool / uint8 [nx, ny, nz]: only these voxels take part;   refine   also return sub-voxel positions
+        A voxel takes part when it has a row, passes the mask and its value is < +Inf (not NaN, not +Inf; > -Inf under largest).  It is a
+        peak when no other voxel that takes part within r on all three axes has a smaller value, or the same value and a lower flat index.
+        -> {'voxel': int32 [K, k] flat indices by ascending value (descending under largest), ties to the lower index, padded with -1;
+            'value': float32 [K, k], padded with +Inf (-Inf under largest); 'points': float32 [K, k, 3] voxel centres, NaN rows as
+            padding; 'count': int32 [K] the number of peaks, which may exceed k; with refine 'refined': float64 [K, k, 3] = the centre +
+            step * offset, per axis offset = 0.5 (f- - f+) / (f- - 2 f0 + f+) clamped to [-0.5, 0.5], 0 where a neighbour does not take
+            part or lies outside the volume or the denominator is not > 0}.  A [nx, ny, nz] or [M] input is one column: K = 1.
+        The same bytes on every run.  No autograd: outputs never require grad."""
+        who = "peaks"
+        dev = self.device
+        nx, ny, nz = self.grid_shape
+        if not isinstance(values, torch.Tensor) or values.dtype != torch.float32:
+            raise TypeError("peaks: values must be a float32 tensor")
+        if not values.is_cuda or values.device != dev:
+            raise RuntimeError("peaks: values must be on %s (where the volume lives); there is no CPU path" % dev)
+        if values.dim() in (3, 4) and tuple(values.shape[:3]) == (nx, ny, nz):
+            rows_banded = False
+            work = values.detach().reshape(nx * ny * nz, -1)
+        elif values.dim() in (1, 2) and self.band is not None and values.shape[0] == self.band_voxels.shape[0]:
+            rows_banded = True
+            work = values.detach().reshape(values.shape[0], -1)
+        else:
+            raise ValueError("peaks: values must be [nx, ny, nz] or [nx, ny, nz, K] with the grid %s%s, got %s"
+                             % (tuple(self.grid_shape), "" if self.band is None else ", or [M] / [M, K] with M = %d stored voxels" % self.band_voxels.shape[0],
+                                tuple(values.shape)))
+        r = self._peak_radius(who, radius_voxels, separation)
+        k = self._peak_k(who, k)
+        mask = self._peak_mask(who, mask)
+        thr = float("inf") if threshold is None else (-float(threshold) if largest else float(threshold))
+        if math.isnan(thr):
+            raise ValueError("peaks: threshold must not be NaN")
+        work = (-work if largest else work).contiguous()
+        voxel, value, count, offset = self._peaks_rows(work, rows_banded, r, k, thr, mask, refine)
+        return self._peaks_result("value", voxel, value, count, offset, largest)
+
+    def locate(self, descriptors, name, k=8, radius_voxels=None, separation=None, max_distance=None, dist_type="l2", mask=None, max_bytes=1 << 30):
+        """Where are these descriptors?  For each of K reference descriptors the k best spatially distinct matches among the rows of set
+        `name`: the distances of d3f_pairwise_similarity (D3F_SIM_DIST) as a [M, Kc] matrix, then peaks() on it.
+
+        descriptors   float32 [K, C] on the field's device, C the width of `name`
+        name          a baked set.  On a dense field its rows are all voxels and mask defaults to `valid`; on a banded field the stored rows
+        k, radius_voxels, separation, mask   as in peaks();   max_distance   only matches with distance <= max_distance
+        dist_type     "l2" or "square", as in corr_utils
+        max_bytes     the columns are taken in chunks so that the distances and the suppressed copy of one chunk stay under this
+        -> what peaks() returns, with 'distance' for 'value'; 'refined' interpolates the distances.  No autograd."""
+        from .corr_utils import _dist_code
+        who = "locate"
+        names = self._names([name])
+        code = _dist_code(dist_type)
+        dev = self.device
+        if not isinstance(descriptors, torch.Tensor) or descriptors.dim() != 2:
+            raise ValueError("locate: descriptors must be a [K, C] tensor")
+        if not descriptors.is_cuda or descriptors.device != dev:
+            raise RuntimeError("locate: descriptors must be on %s (where the volume lives); there is no CPU path" % dev)
+        C = self._channels(names[0])
+        if descriptors.shape[1] != C:
+            raise ValueError("locate: descriptors have %d channels, set %r has %d" % (descriptors.shape[1], name, C))
+        r = self._peak_radius(who, radius_voxels, separation)
+        k = self._peak_k(who, k)
+        banded = self.band is not None
+        mask = self._peak_mask(who, self.valid if (mask is None and not banded) else mask)
+        thr = float("inf") if max_distance is None else float(max_distance)
+        if math.isnan(thr):
+            raise ValueError("locate: max_distance must not be NaN")
+        rows = self._sets[names[0]].reshape(-1, C).contiguous()
+        tgt = descriptors.detach().to(torch.float32).contiguous()
+        M, K = rows.shape[0], tgt.shape[0]
+        per_chunk = K if M == 0 else max(1, min(K, int(max_bytes) // (8 * M)))
+        parts = []
+        for q0 in range(0, max(K, 1), max(per_chunk, 1)):          # (K = 0: one empty chunk, which launches nothing)
+            Kc = min(per_chunk, K - q0)
+            dist = torch.empty((M, Kc), dtype=torch.float32, device=dev)
+            if M > 0 and Kc > 0:
+                with torch.cuda.device(dev):
+                    _lib.check(self._lib.d3f_pairwise_similarity(_lib.ptr(rows), _lib.ptr(tgt[q0:q0 + Kc]), M, Kc, C, 1.0, code, _lib.SIM_DIST, _lib.ptr(dist),
+                                                                 None, None, 0, _lib.current_stream_handle(dev)))
+            parts.append(self._peaks_rows(dist, banded, r, k, thr, mask, True))
+        voxel, value, count, offset = (torch.cat([p[i] for p in parts], dim=0) for i in range(4))
+        return self._peaks_result("distance", voxel, value, count, offset, False)
 
     # ---- rays -----------------------------------------------------------------------------------------------------------------
     def _check_rays(self, origins, dirs):

@@ -1071,6 +1071,49 @@ int d3f_path_shorten(const uint8_t *free, int32_t nx, int32_t ny, int32_t nz, co
     return e == hipSuccess ? D3F_OK : hip_fail(e, "path_shorten launch");
 }
 
+// ---- exact non-maximum suppression through the slot volume (peaks_kernels.hip) ----
+int d3f_volume_peaks(const int32_t *slot, const uint8_t *mask, int32_t nx, int32_t ny, int32_t nz, const float *score, int64_t M, int32_t K,
+                     int64_t stride_row, int32_t radius, float threshold, float *out, int64_t out_stride, int32_t *out_count, void *workspace,
+                     int64_t workspace_bytes, void *stream)
+{
+    (void)workspace;
+    (void)workspace_bytes;
+    if (K < 0 || M < 0) return fail(D3F_ERR_INVALID_ARG, "volume_peaks: M=%lld K=%d, neither may be negative", (long long)M, K);
+    if (radius < 1 || radius > D3F_PEAKS_MAX_RADIUS) return fail(D3F_ERR_INVALID_ARG, "volume_peaks: radius=%d outside [1, %d]", radius, D3F_PEAKS_MAX_RADIUS);
+    if (threshold != threshold) return fail(D3F_ERR_INVALID_ARG, "volume_peaks: threshold is NaN (+Inf means none)");
+    if (stride_row < K || out_stride < K)
+        return fail(D3F_ERR_INVALID_ARG, "volume_peaks: stride_row=%lld out_stride=%lld, both must be >= K=%d", (long long)stride_row, (long long)out_stride, K);
+    if (M > 0 && K > 0 && (!score || !out)) return fail(D3F_ERR_INVALID_ARG, "volume_peaks: score or out is NULL with M=%lld K=%d", (long long)M, K);
+    if (!edt_shape_ok(nx, ny, nz))
+        return fail(D3F_ERR_BAD_SHAPE, "volume_peaks: nx=%d ny=%d nz=%d, every extent must be in [1, %d] and the volume at most 2^31 - 1 voxels", nx, ny, nz,
+                    D3F_EDT_MAX_EXTENT);
+    const int64_t n_voxels = (int64_t)nx * ny * nz;
+    if (!slot && M != n_voxels) return fail(D3F_ERR_INVALID_ARG, "volume_peaks: M=%lld without slot, must equal nx*ny*nz=%lld", (long long)M, (long long)n_voxels);
+    if (slot && M > n_voxels) return fail(D3F_ERR_INVALID_ARG, "volume_peaks: M=%lld rows for %lld voxels", (long long)M, (long long)n_voxels);
+    if (!aligned(slot, 4) || !aligned(score, 4) || !aligned(out, 4) || !aligned(out_count, 4))
+        return fail(D3F_ERR_BAD_LAYOUT, "volume_peaks: slot / score / out / out_count must be 4-byte aligned");
+    if (M > 0 && K > 0) {
+        if (stride_row > ((int64_t)1 << 60) / M || out_stride > ((int64_t)1 << 60) / M)      // (the byte spans below stay inside 64 bits)
+            return fail(D3F_ERR_BAD_SHAPE, "volume_peaks: stride_row=%lld out_stride=%lld too large for M=%lld rows", (long long)stride_row, (long long)out_stride,
+                        (long long)M);
+        const uintptr_t s0 = (uintptr_t)score, s1 = s0 + (uintptr_t)((M - 1) * stride_row + K) * 4;
+        const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (uintptr_t)((M - 1) * out_stride + K) * 4;
+        if (s0 < o1 && o0 < s1) return fail(D3F_ERR_INVALID_ARG, "volume_peaks: out overlaps score");
+    }
+    const d3f::PeaksPlan plan = d3f::peaks_plan(nx, ny, nz, K, radius);
+    if (plan.chunks > 65535 || plan.tiles > 0x7fffffffLL)
+        return fail(D3F_ERR_BAD_SHAPE, "volume_peaks: K=%d columns are %lld chunks, too large for one launch (65535)", K, (long long)plan.chunks);
+    if (K == 0) return D3F_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (out_count) {
+        hipError_t e = hipMemsetAsync(out_count, 0, (size_t)K * sizeof(int32_t), s);
+        if (e != hipSuccess) return hip_fail(e, "volume_peaks memset");
+    }
+    if (M == 0) return D3F_OK;
+    hipError_t e = d3f::launch_volume_peaks(slot, mask, nx, ny, nz, score, K, stride_row, radius, threshold, out, out_stride, out_count, s);
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_peaks launch");
+}
+
 // ---- the first surface a ray meets in a baked volume (raycast_kernels.hip) ----
 int d3f_volume_raycast(const d3f_volume *vol, const float *origins, const float *dirs, int64_t n, const d3f_pinhole *camera,
                        float march_step, float t_near, float t_far, float *out_t, uint8_t *out_hit, float *out_points,

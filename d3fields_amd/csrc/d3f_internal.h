@@ -286,6 +286,15 @@ hipError_t launch_volume_segments(const uint8_t *free, const int32_t *value, int
 hipError_t launch_path_shorten(const uint8_t *free, int nx, int ny, int nz, const int32_t *voxels, const int32_t *length, int64_t n, int row_len, int max_span,
                                bool strict, int32_t *out_index, int32_t *out_voxels, int32_t *out_count, hipStream_t s);
 
+// peaks_kernels.hip: exact non-maximum suppression through the slot volume
+struct PeaksPlan {
+    int tile, log_ck, hzp, tiles_y, tiles_z;     // tile edge, log2 of the column chunk, padded z line of the staged box
+    int64_t tiles, chunks, lds_bytes;            // grid.x, grid.y, dynamic LDS of one workgroup
+};
+PeaksPlan peaks_plan(int nx, int ny, int nz, int K, int radius);
+hipError_t launch_volume_peaks(const int32_t *slot, const uint8_t *mask, int nx, int ny, int nz, const float *score, int K, int64_t stride_row, int radius,
+                               float threshold, float *out, int64_t out_stride, int32_t *out_count, hipStream_t s);
+
 // raycast_kernels.hip: the first surface a ray meets in a baked volume
 constexpr float kRayMaxSamples = 131072.0f;  // a ray whose K exceeds this misses: unreachable under the entry point's 65536-step guard but for overflow
 struct RayParams {

@@ -639,6 +639,42 @@ int d3f_volume_segments(const uint8_t *free, const int32_t *value, int32_t nx, i
 int d3f_path_shorten(const uint8_t *free, int32_t nx, int32_t ny, int32_t nz, const int32_t *voxels, const int32_t *length, int64_t n, int32_t row_len,
                      int32_t max_span, uint32_t flags, int32_t *out_index, int32_t *out_voxels, int32_t *out_count, void *stream);
 
+/* (still ABI 16: one symbol and one constant are ADDED, no struct or earlier entry point changes, and D3F_ABI_VERSION stays 16 -- a client
+ * detects the feature by the symbol.)  Where is this descriptor?  Exact, order-independent non-maximum suppression of K score columns through
+ * the band's slot volume.
+ *   volume       nx x ny x nz, z fastest, flat index (x*ny + y)*nz + z, extents in [1, D3F_EDT_MAX_EXTENT], at most 2^31 - 1 voxels;
+ *   slot         NULL, or an int32 volume exactly as d3f_band_mark writes it (-1 = no row).  With NULL, row m is voxel m and M must equal
+ *                nx*ny*nz.  Slot values are trusted to be < M, as in d3f_band_sample;
+ *   mask         NULL, or one byte per voxel (non-zero = takes part);
+ *   score        float32: row m, column q at score[m*stride_row + q], 0 <= q < K, stride_row >= K;
+ *   radius       r in [1, D3F_PEAKS_MAX_RADIUS];   threshold   a float that is not NaN; +Inf means no threshold.
+ *   takes part   for a column q, voxel v with row m = slot[v] takes part when m >= 0, mask[v] != 0 (when a mask is given) and
+ *                score[m, q] < +Inf -- a comparison that is false for NaN and for +Inf; -Inf takes part;
+ *   peak         v is a peak of column q when it takes part, score[m, q] <= threshold, and for every OTHER voxel u that takes part and has
+ *                |u_a - v_a| <= r on all three axes the pair (score_u, flat_u) is lexicographically greater than (score_v, flat_v).  The
+ *                neighbourhood is spatial and clipped to the volume: (x, y, nz-1) and (x, y+1, 0) are no neighbours.  Scores compare as
+ *                IEEE floats, so -0.0 == +0.0.  The threshold filters peaks; it does not stop a voxel above it from suppressing others.
+ *   Consequences: two peaks of one column differ by more than r on some axis; a constant volume has exactly one peak, voxel 0; the result
+ *   does not depend on any order of execution.  Minima only: a caller who wants maxima negates, which is exact.
+ *   out          out[m*out_stride + q] = score[m, q] (its very bits) where the voxel of row m is a peak of column q, +Inf otherwise.  Every
+ *                row 0 .. M-1 and column 0 .. K-1 is written; the padding between K and the stride is not touched.  out must not overlap
+ *                score (checked on the host);
+ *   out_count    int32 [K], may be NULL: the number of peaks of column q (zeroed by the call, then integer adds).
+ * One workgroup per tile of voxels and chunk of columns: (ordered float, flat index) keys of the tile and a halo of r in LDS, the box minimum as
+ * three 1-D window minima of 64-bit keys (associative, so exactly separable), a voxel is a peak when the box minimum is its own key.  A tile
+ * without a stored voxel leaves before any score load.  No float atomics, nothing waits for another workgroup, every loop bound is known at
+ * launch, the caller's stream, no allocation, no synchronisation.  The call needs NO workspace: `workspace` / `workspace_bytes` are
+ * reserved, may be NULL / 0 and are never read, so D3F_ERR_WORKSPACE is never returned and there is no _workspace_bytes companion.
+ * Status errors, checked on the host before any HIP call, nothing launched: K < 0, M < 0, a radius outside [1, 8], a NaN threshold, a stride
+ * below K, NULL score / out with M*K > 0, out overlapping score, M != nx*ny*nz without slot, M > nx*ny*nz with it (D3F_ERR_INVALID_ARG); an
+ * extent outside [1, 16384], more than 2^31 - 1 voxels, more column chunks than one launch holds (65535 chunks of 1 to 8 columns), M times a
+ * stride above 2^60 (D3F_ERR_BAD_SHAPE); slot, score, out or out_count not 4-byte aligned (D3F_ERR_BAD_LAYOUT).  M == 0 or K == 0: D3F_OK, no kernel
+ * launched; a given out_count is still zeroed when K > 0. */
+#define D3F_PEAKS_MAX_RADIUS 8
+int d3f_volume_peaks(const int32_t *slot, const uint8_t *mask, int32_t nx, int32_t ny, int32_t nz, const float *score, int64_t M, int32_t K,
+                     int64_t stride_row, int32_t radius, float threshold, float *out, int64_t out_stride, int32_t *out_count, void *workspace,
+                     int64_t workspace_bytes, void *stream);
+
 /* (ABI 12) The first surface a ray meets in a baked volume: a fixed-step march through `dist` with one linear interpolation at the
  * sign change.  Everything in fp32.  Ray i is p(t) = o + t*d; d need not be unit.
  *   once per ray: go_a = (o_a - origin_a) / h, gd_a = d_a / h (IEEE divisions), len = sqrtf(fma(d_z, d_z, fma(d_y, d_y, d_x*d_x)));
