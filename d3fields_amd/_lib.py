@@ -35,6 +35,9 @@ RAYCAST_MAX_STEPS = 65536
 EDT_MAX_EXTENT = 16384
 SEGMENT_CUT_CORNERS = 1
 PEAKS_MAX_RADIUS = 8
+ALIGN_ROW_DOUBLES, ALIGN_STATE_DOUBLES = 32, 96
+ALIGN_RUNNING, ALIGN_CONVERGED, ALIGN_STALLED, ALIGN_NO_GRADIENT, ALIGN_FAILED = 0, 1, 2, 3, 4
+ALIGN_CHUNK = 256
 POOL_MEAN, POOL_VOTES = 0, 1
 POOL_CHUNK = 256
 POOL_MAX_VOTE_CHANNELS = 256
@@ -50,6 +53,7 @@ _i32 = ctypes.c_int32
 _i64 = ctypes.c_int64
 _u32 = ctypes.c_uint32
 _f32 = ctypes.c_float
+_f64 = ctypes.c_double
 
 
 class Views(ctypes.Structure):
@@ -162,6 +166,11 @@ SIGNATURES = {
     "d3f_volume_segments": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _i64, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "d3f_path_shorten": (ctypes.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _u32, _vp, _vp, _vp, _vp]),
     "d3f_volume_peaks": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i64, _i32, _i64, _i32, _f32, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "d3f_volume_align_workspace_bytes": (_i64, [_i64, _i64]),
+    "d3f_volume_align_centroid": (ctypes.c_int, [_vp, _vp, _i64, _i64, _vp, _vp]),
+    "d3f_volume_align_accumulate": (ctypes.c_int, [ctypes.POINTER(Volume), ctypes.POINTER(Band), ctypes.POINTER(VolumeSet), _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                   _i64, _i64, _f32, _f32, _f32, _vp, _vp, _i64, _vp]),
+    "d3f_volume_align_step": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _i32, _i32, _f64, _f64, _vp, _vp, _vp, _vp]),
     "d3f_volume_raycast": (ctypes.c_int, [ctypes.POINTER(Volume), _vp, _vp, _i64, ctypes.POINTER(Pinhole), _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp]),
     "d3f_fps_workspace_bytes": (_i64, [_i64]),
     "d3f_fps_pixels_workspace_bytes": (_i64, [_i64]),

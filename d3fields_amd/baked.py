@@ -39,6 +39,10 @@ clearance field, how narrow it gets on the way; `shortcut(paths)` keeps only the
 the slot volume (d3f_volume_peaks, csrc/peaks_kernels.hip) and the k best survivors per column, with a sub-voxel
 refinement; `locate(descriptors, name)` runs it on the descriptor distances of a set: where in this observation are these descriptors?
 
+`BakedField.align(points, name, targets)` answers "where did it go?": the rigid motion that puts point sets with descriptors onto the field,
+by damped Gauss-Newton on the device (d3f_volume_align_*, csrc/align_kernels.hip) -- a pose, a cost and a verdict per
+instance; `normal_equations(points, rot, trans)` gives the 6 x 6 systems alone.
+
 There is no CPU path: volumes and points live on the ROCm device.
 """
 import ctypes
@@ -1202,6 +1206,155 @@ class BakedField:
             parts.append(self._peaks_rows(dist, banded, r, k, thr, mask, True))
         voxel, value, count, offset = (torch.cat([p[i] for p in parts], dim=0) for i in range(4))
         return self._peaks_result("distance", voxel, value, count, offset, False)
+
+    # ---- alignment ------------------------------------------------------------------------------------------------------------
+    def _align_tensor(self, who, what, t, shape):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape):
+            raise ValueError("%s: %s must be a tensor of shape %s, got %s" % (who, what, list(shape), list(getattr(t, "shape", ())) or type(t).__name__))
+        if not t.is_cuda or t.device != self.device:
+            raise RuntimeError("%s: %s must be on %s (where the volume lives); there is no CPU path" % (who, what, self.device))
+        if t.dtype != torch.float32:
+            raise TypeError("%s: %s must be float32, got %s" % (who, what, t.dtype))
+        return t.detach().contiguous()
+
+    def _align_problem(self, who, points, name, targets, dist_targets, weights, dist_weight, feat_weight, outside):
+        """the checked, contiguous inputs of one alignment problem and the model centroids (d3f_volume_align_centroid)"""
+        if not isinstance(points, torch.Tensor) or points.dim() != 3 or points.shape[2] != 3:
+            raise ValueError("%s: points must be [I, n, 3], got %s" % (who, list(getattr(points, "shape", ())) or type(points).__name__))
+        I, n = int(points.shape[0]), int(points.shape[1])
+        pts = self._align_tensor(who, "points", points, (I, n, 3))
+        names = self._names([] if name is None else [name])
+        if name is None and targets is not None:
+            raise ValueError("%s: targets need the name of the set they are descriptors of" % who)
+        if name is not None and targets is None:
+            raise ValueError("%s: set %r needs targets [I, n, %d]" % (who, name, self._channels(name)))
+        tg = None if name is None else self._align_tensor(who, "targets", targets, (I, n, self._channels(name)))
+        dt = None if dist_targets is None else self._align_tensor(who, "dist_targets", dist_targets, (I, n))
+        wt = None if weights is None else self._align_tensor(who, "weights", weights, (I, n))
+        terms = {"dist_weight": float(dist_weight), "feat_weight": float(feat_weight)}
+        terms["outside"] = 4.0 * self.step * terms["dist_weight"] if outside is None else float(outside)
+        for k, v in terms.items():
+            if not (v >= 0.0 and math.isfinite(v)):
+                raise ValueError("%s: %s must be finite and >= 0, got %r" % (who, k, v))
+        centroid = torch.zeros((I, 3), dtype=torch.float32, device=self.device)
+        if I > 0 and n > 0:
+            with torch.cuda.device(self.device):
+                _lib.check(self._lib.d3f_volume_align_centroid(_lib.ptr(pts), _lib.ptr(wt), I, n, _lib.ptr(centroid), _lib.current_stream_handle(self.device)))
+        ws_bytes = int(self._lib.d3f_volume_align_workspace_bytes(I, n))
+        ws = torch.empty(max(ws_bytes, 8) // 8, dtype=torch.float64, device=self.device)
+        return {"I": I, "n": n, "pts": pts, "names": names, "targets": tg, "dist_targets": dt, "weights": wt, "terms": terms, "centroid": centroid, "ws": ws,
+                "ws_bytes": ws_bytes}
+
+    def _align_pose(self, who, I, rot, trans):
+        """[I, 12] float32: the kernels' R (the TRANSPOSE of the row-vector `rot`) row-major, then t"""
+        dev = self.device
+        rot = torch.eye(3, dtype=torch.float32, device=dev).expand(I, 3, 3) if rot is None else self._align_tensor(who, "rot", rot, (I, 3, 3))
+        trans = torch.zeros((I, 3), dtype=torch.float32, device=dev) if trans is None else self._align_tensor(who, "trans", trans, (I, 3))
+        return torch.cat((rot.transpose(1, 2).reshape(I, 9), trans), dim=1).contiguous()
+
+    def _align_accumulate(self, prob, pose, skip, out):
+        dev = self.device
+        vol = self._volume()
+        band = None if self.band is None else ctypes.byref(self._band_struct())
+        sets = self._set_array(prob["names"]) if prob["names"] else None
+        t = prob["terms"]
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.d3f_volume_align_accumulate(ctypes.byref(vol), band, sets, _lib.ptr(prob["pts"]), _lib.ptr(prob["weights"]), _lib.ptr(prob["targets"]),
+                                                             _lib.ptr(prob["dist_targets"]), _lib.ptr(pose), _lib.ptr(prob["centroid"]), _lib.ptr(skip), prob["I"],
+                                                             prob["n"], t["dist_weight"], t["feat_weight"], t["outside"], _lib.ptr(out), _lib.ptr(prob["ws"]),
+                                                             prob["ws_bytes"], _lib.current_stream_handle(dev)))
+
+    def normal_equations(self, points, rot, trans, name=None, targets=None, dist_targets=None, weights=None, dist_weight=1.0, feat_weight=1.0, outside=None):
+        """The Gauss-Newton normal equations of aligning point sets to this field at given poses (d3f_volume_align_accumulate,
+        csrc/align_kernels.hip), for callers with their own solver or their own priors.
+
+        points        float32 [I, n, 3]: I instances of n model points;  weights  float32 [I, n] >= 0 or None (ones; 0 is padding)
+        rot, trans    float32 [I, 3, 3] and [I, 3] in rigid.rigid_transform's row-vector convention, x = p @ rot + trans (None: the identity).
+                      The kernels' R is the transpose of `rot`.
+        name, targets one baked set and float32 [I, n, C] descriptors the points should meet, or None: the distance term alone
+        dist_targets  float32 [I, n] distances the points should meet, or None (zeros: the points lie on the surface)
+        dist_weight, feat_weight   the weights of the two kinds of residual;  outside  the residual of a weighted point that is not valid
+                      (None: 4 * step * dist_weight), which enters the cost and nothing else
+        Residuals: dist_weight (dist(x) - d) at every valid point and feat_weight (f_k(x) - s_k) per channel where the point has rows (valid;
+        on a banded field in_band).  The parameters are (w, v): x <- c + Exp(w)(x - c) + v about the pivot c, the weighted centroid of the
+        transformed points.
+        -> {'H': float64 [I, 6, 6] = sum w_j J^T J (symmetric), 'b': float64 [I, 6] = sum w_j J^T r, 'cost': float64 [I] = sum w_j r^2,
+            'valid': int32 [I] the weighted points that are valid, 'in_band': int32 [I] those that have rows, 'pivot': float64 [I, 3]}.
+        The same bytes on every run.  No autograd: outputs never require grad."""
+        who = "normal_equations"
+        prob = self._align_problem(who, points, name, targets, dist_targets, weights, dist_weight, feat_weight, outside)
+        I, dev = prob["I"], self.device
+        pose = self._align_pose(who, I, rot, trans)
+        out = torch.zeros((I, _lib.ALIGN_ROW_DOUBLES), dtype=torch.float64, device=dev)
+        if I > 0 and prob["n"] > 0:
+            self._align_accumulate(prob, pose, None, out)
+        iu = torch.triu_indices(6, 6, device=dev)
+        H = torch.zeros((I, 6, 6), dtype=torch.float64, device=dev)
+        H[:, iu[0], iu[1]] = out[:, :21]
+        H[:, iu[1], iu[0]] = out[:, :21]
+        m = prob["centroid"]
+        pivot = (pose[:, :9].reshape(I, 3, 3).double() @ m.double()[:, :, None])[:, :, 0] + pose[:, 9:].double()
+        return {"H": H, "b": out[:, 21:27].clone(), "cost": out[:, 27].clone(), "valid": out[:, 28].to(torch.int32), "in_band": out[:, 29].to(torch.int32),
+                "pivot": pivot}
+
+    def align(self, points, name=None, targets=None, rot=None, trans=None, iters=20, rot_tol=1e-5, trans_tol=None, dist_targets=None, weights=None,
+              dist_weight=1.0, feat_weight=1.0, outside=None):
+        """Where did it go?  The rigid motion that puts point sets onto this field: damped Gauss-Newton (Levenberg-Marquardt) on the residuals
+        of normal_equations(), every instance on its own, the whole loop on the device (d3f_volume_align_accumulate / d3f_volume_align_step,
+        csrc/align_kernels.hip): 2 iters + 2 launches on the current stream, no synchronisation.
+
+        points, name, targets, dist_targets, weights, dist_weight, feat_weight, outside   as in normal_equations()
+        rot, trans    the starting poses, float32 [I, 3, 3] and [I, 3] in rigid.rigid_transform's row-vector convention (None: the identity);
+                      they come out in the same convention: rigid_transform(points, fit['rot'], fit['trans']) is fit['points'].  The kernels' R
+                      is the transpose of `rot`.
+        iters         the number of iterations after the first evaluation;  rot_tol (rad), trans_tol (None: 1e-3 * step)  a step smaller than
+                      both ends the instance as CONVERGED: one that was accepted, or one proposed at a pose that was just accepted (it is not
+                      taken: it would lower the cost by less than the fp32 sums resolve)
+        Iteration 0 evaluates the start.  Each further one solves (H + lambda D) delta = -b, D_jj = max(H_jj, 1e-9 max H), evaluates the
+        candidate and accepts it when the cost fell (lambda / 10, at least 1e-9), else rejects it (10 lambda, at most 1e6).  lambda starts at
+        1e-3.  status: 0 RUNNING (the iterations ran out), 1 CONVERGED, 2 STALLED (lambda reached its maximum), 3 NO_GRADIENT (no valid point
+        or a flat field: the pose is unchanged), 4 FAILED (a Cholesky pivot that is not positive and finite; the pose is the last accepted one).
+        -> {'rot': float32 [I, 3, 3], 'trans': float32 [I, 3], 'points': float32 [I, n, 3] the points at the final pose, 'cost': float64 [I],
+            'valid': int32 [I], 'status': int32 [I], 'steps': int32 [I] accepted steps, 'history': float64 [I, iters + 1] the accepted cost
+            after every iteration (its last column is the final cost)}.
+        Many starts are just more instances: repeat the points with k starting poses -- the k candidates of locate(), say -- and keep
+        argmin(cost) among the CONVERGED ones.  The same bytes on every run, and an instance's result does not depend on the others.
+        No autograd: outputs never require grad."""
+        who = "align"
+        iters = operator.index(iters)
+        if iters < 0:
+            raise ValueError("align: iters must be >= 0, got %d" % iters)
+        rot_tol = float(rot_tol)
+        trans_tol = 1e-3 * self.step if trans_tol is None else float(trans_tol)
+        for k, v in (("rot_tol", rot_tol), ("trans_tol", trans_tol)):
+            if not (v >= 0.0 and math.isfinite(v)):
+                raise ValueError("align: %s must be finite and >= 0, got %r" % (k, v))
+        prob = self._align_problem(who, points, name, targets, dist_targets, weights, dist_weight, feat_weight, outside)
+        I, n, dev = prob["I"], prob["n"], self.device
+        pose = self._align_pose(who, I, rot, trans)
+        state = torch.zeros((I, _lib.ALIGN_STATE_DOUBLES), dtype=torch.float64, device=dev)
+        state[:, 0:12] = pose
+        state[:, 12:24] = pose
+        state[:, 24:27] = prob["centroid"]
+        state[:, 27] = 1e-3
+        history = torch.zeros((I, iters + 1), dtype=torch.float64, device=dev)
+        if I > 0 and n > 0:
+            skip = torch.zeros(I, dtype=torch.int32, device=dev)
+            out = torch.zeros((I, _lib.ALIGN_ROW_DOUBLES), dtype=torch.float64, device=dev)
+            for it in range(iters + 1):
+                self._align_accumulate(prob, pose, skip, None)
+                with torch.cuda.device(dev):
+                    _lib.check(self._lib.d3f_volume_align_step(_lib.ptr(state), _lib.ptr(prob["ws"]), prob["ws_bytes"], I, n, _lib.ptr(out), it, iters, rot_tol,
+                                                               trans_tol, _lib.ptr(pose), _lib.ptr(skip), _lib.ptr(history), _lib.current_stream_handle(dev)))
+        else:
+            state[:, 29] = _lib.ALIGN_NO_GRADIENT          # no point at all: nothing to align to
+        R = state[:, 0:9].to(torch.float32).reshape(I, 3, 3)
+        t = state[:, 9:12].to(torch.float32)
+        p = prob["pts"]
+        # the chain of the kernels, element by element (so that an instance's points do not depend on how many instances there are)
+        moved = torch.addcmul(torch.addcmul(p[:, :, 0:1] * R[:, None, :, 0], p[:, :, 1:2], R[:, None, :, 1]), p[:, :, 2:3], R[:, None, :, 2]) + t[:, None, :]
+        return {"rot": R.transpose(1, 2).contiguous(), "trans": t.contiguous(), "points": moved, "cost": state[:, 28].clone(),
+                "valid": state[:, 31].to(torch.int32), "status": state[:, 29].to(torch.int32), "steps": state[:, 30].to(torch.int32), "history": history}
 
     # ---- rays -----------------------------------------------------------------------------------------------------------------
     def _check_rays(self, origins, dirs):

@@ -1114,6 +1114,109 @@ int d3f_volume_peaks(const int32_t *slot, const uint8_t *mask, int32_t nx, int32
     return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_peaks launch");
 }
 
+// ---- rigid alignment of point sets to the baked field (align_kernels.hip) ----
+static bool align_counts_ok(int64_t I, int64_t n) { return I >= 0 && n >= 0; }
+static bool finite_nonneg(double v) { return v >= 0.0 && v * 0.0 == 0.0; }
+
+int64_t d3f_volume_align_workspace_bytes(int64_t I, int64_t n)
+{
+    if (I <= 0 || n <= 0) return 0;
+    const int64_t chunks = d3f::align_chunks(n);
+    if (chunks > 0x7fffffffLL / I) return 0;
+    return I * chunks * d3f::kAlignRow * (int64_t)sizeof(double);
+}
+
+int d3f_volume_align_centroid(const float *points, const float *weights, int64_t I, int64_t n, float *centroids_out, void *stream)
+{
+    if (!align_counts_ok(I, n)) return fail(D3F_ERR_INVALID_ARG, "volume_align_centroid: I=%lld n=%lld, a count is negative", (long long)I, (long long)n);
+    if (I > 0x7fffffffLL) return fail(D3F_ERR_BAD_SHAPE, "volume_align_centroid: I=%lld is too large for one launch", (long long)I);
+    if (I == 0) return D3F_OK;
+    if (!centroids_out || (n > 0 && !points)) return fail(D3F_ERR_INVALID_ARG, "volume_align_centroid: points / centroids_out is NULL");
+    if (!aligned(points, 4) || !aligned(weights, 4) || !aligned(centroids_out, 4))
+        return fail(D3F_ERR_BAD_LAYOUT, "volume_align_centroid: points / weights / centroids_out must be 4-byte aligned");
+    hipError_t e = d3f::launch_align_centroid(points, weights, I, n, centroids_out, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_align_centroid launch");
+}
+
+int d3f_volume_align_accumulate(const d3f_volume *vol, const d3f_band *band, const d3f_volume_set *set, const float *points, const float *weights,
+                                const float *targets, const float *dist_targets, const float *pose, const float *centroids, const int32_t *skip,
+                                int64_t I, int64_t n, float dist_weight, float feat_weight, float outside, double *out, void *workspace,
+                                int64_t workspace_bytes, void *stream)
+{
+    const char *who = "volume_align_accumulate";
+    if (!align_counts_ok(I, n)) return fail(D3F_ERR_INVALID_ARG, "%s: I=%lld n=%lld, a count is negative", who, (long long)I, (long long)n);
+    if (!finite_nonneg(dist_weight) || !finite_nonneg(feat_weight) || !finite_nonneg(outside))
+        return fail(D3F_ERR_INVALID_ARG, "%s: dist_weight / feat_weight / outside must be finite and not negative", who);
+    if (band && (band->n_rows < 0 || band->n_rows > 0x7fffffffLL))
+        return fail(D3F_ERR_BAD_SHAPE, "%s: band->n_rows=%lld outside [0, 2^31 - 1]", who, (long long)band->n_rows);
+    const bool empty_band = band && band->n_rows == 0;
+    d3f::AlignParams A;
+    // (volume_common answers n == 0 with "nothing to do": the instances only scale the count)
+    const int rc = volume_common(who, vol, points, I == 0 ? 0 : n, set, set ? 1 : 0, A.V, empty_band);
+    if (rc != D3F_OK) return rc == 1 ? D3F_OK : rc;
+    const int64_t chunks = d3f::align_chunks(n);
+    if (chunks > 0x7fffffffLL / I) return fail(D3F_ERR_BAD_SHAPE, "%s: I=%lld instances of %lld workgroups are too many for one launch", who, (long long)I, (long long)chunks);
+    if (!pose || !centroids || !workspace || (set && !targets)) return fail(D3F_ERR_INVALID_ARG, "%s: pose / centroids / workspace (and targets with a set) must be non-NULL", who);
+    if (band && !empty_band && (!band->slot || !band->cell_band)) return fail(D3F_ERR_INVALID_ARG, "%s: band->slot / band->cell_band must be non-NULL with n_rows > 0", who);
+    if (!aligned(weights, 4) || !aligned(targets, 4) || !aligned(dist_targets, 4) || !aligned(pose, 4) || !aligned(centroids, 4) || !aligned(skip, 4) ||
+        (band && !aligned(band->slot, 4)))
+        return fail(D3F_ERR_BAD_LAYOUT, "%s: float and int32 arrays must be 4-byte aligned", who);
+    if (!aligned(out, 8) || !aligned(workspace, 8)) return fail(D3F_ERR_BAD_LAYOUT, "%s: out / workspace must be 8-byte aligned", who);
+    if (workspace_bytes < d3f_volume_align_workspace_bytes(I, n))
+        return fail(D3F_ERR_WORKSPACE, "%s: needs %lld workspace bytes", who, (long long)d3f_volume_align_workspace_bytes(I, n));
+    if (set && !aligned(targets, 16)) A.V.sets[0].vec = 0;
+    A.slot = (band && !empty_band) ? band->slot : nullptr;
+    A.cell_band = (band && !empty_band) ? band->cell_band : nullptr;
+    A.banded = band ? 1 : 0;
+    A.I = (int32_t)I;
+    A.weights = weights;
+    A.targets = targets;
+    A.dist_targets = dist_targets;
+    A.pose = pose;
+    A.centroid = centroids;
+    A.skip = skip;
+    A.wd = dist_weight;
+    A.wf = feat_weight;
+    A.outside = outside;
+    A.chunks = chunks;
+    A.partial = static_cast<double *>(workspace);
+    hipError_t e = d3f::launch_align_accumulate(A, out, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_align_accumulate launch");
+}
+
+int d3f_volume_align_step(double *state, const void *workspace, int64_t workspace_bytes, int64_t I, int64_t n, double *out, int32_t it, int32_t iters,
+                          double rot_tol, double trans_tol, float *pose_out, int32_t *skip_out, double *history, void *stream)
+{
+    const char *who = "volume_align_step";
+    if (!align_counts_ok(I, n)) return fail(D3F_ERR_INVALID_ARG, "%s: I=%lld n=%lld, a count is negative", who, (long long)I, (long long)n);
+    if (iters < 0 || it < 0 || it > iters) return fail(D3F_ERR_INVALID_ARG, "%s: it=%d outside [0, iters=%d]", who, it, iters);
+    if (!finite_nonneg(rot_tol) || !finite_nonneg(trans_tol)) return fail(D3F_ERR_INVALID_ARG, "%s: rot_tol / trans_tol must be finite and not negative", who);
+    if (I == 0 || n == 0) return D3F_OK;
+    const int64_t chunks = d3f::align_chunks(n);
+    if (chunks > 0x7fffffffLL / I) return fail(D3F_ERR_BAD_SHAPE, "%s: I=%lld instances of %lld workgroups are too many for one launch", who, (long long)I, (long long)chunks);
+    if (!state || !workspace || !out || !pose_out || !skip_out || !history)
+        return fail(D3F_ERR_INVALID_ARG, "%s: state / workspace / out / pose_out / skip_out / history must be non-NULL", who);
+    if (!aligned(state, 8) || !aligned(workspace, 8) || !aligned(out, 8) || !aligned(history, 8))
+        return fail(D3F_ERR_BAD_LAYOUT, "%s: state / workspace / out / history must be 8-byte aligned", who);
+    if (!aligned(pose_out, 4) || !aligned(skip_out, 4)) return fail(D3F_ERR_BAD_LAYOUT, "%s: pose_out / skip_out must be 4-byte aligned", who);
+    if (workspace_bytes < d3f_volume_align_workspace_bytes(I, n))
+        return fail(D3F_ERR_WORKSPACE, "%s: needs %lld workspace bytes", who, (long long)d3f_volume_align_workspace_bytes(I, n));
+    d3f::AlignStep S;
+    S.state = state;
+    S.partial = static_cast<const double *>(workspace);
+    S.chunks = chunks;
+    S.out = out;
+    S.it = it;
+    S.iters = iters;
+    S.rot_tol = rot_tol;
+    S.trans_tol = trans_tol;
+    S.pose_out = pose_out;
+    S.skip_out = skip_out;
+    S.history = history;
+    hipError_t e = d3f::launch_align_step(S, I, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_align_step launch");
+}
+
 // ---- the first surface a ray meets in a baked volume (raycast_kernels.hip) ----
 int d3f_volume_raycast(const d3f_volume *vol, const float *origins, const float *dirs, int64_t n, const d3f_pinhole *camera,
                        float march_step, float t_near, float t_far, float *out_t, uint8_t *out_hit, float *out_points,

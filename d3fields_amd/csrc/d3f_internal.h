@@ -295,6 +295,41 @@ PeaksPlan peaks_plan(int nx, int ny, int nz, int K, int radius);
 hipError_t launch_volume_peaks(const int32_t *slot, const uint8_t *mask, int nx, int ny, int nz, const float *score, int K, int64_t stride_row, int radius,
                                float threshold, float *out, int64_t out_stride, int32_t *out_count, hipStream_t s);
 
+// align_kernels.hip: the normal equations of a rigid alignment to the baked field and the damped Gauss-Newton step
+constexpr int kAlignRow = D3F_ALIGN_ROW_DOUBLES;        // one row of sums: 21 + 6 + 1 + 2 counts + 2 zeros
+constexpr int kAlignState = D3F_ALIGN_STATE_DOUBLES;
+struct AlignParams {
+    VolParams V;               // dist, cell, the lattice; pts = the MODEL points [I, n, 3], n = points per instance; sets[0] (n_sets 0 or 1) the descriptor set
+    const int32_t *slot;       // banded: [nx, ny, nz]; nullptr with banded: no row is stored, no point is in the band
+    const uint8_t *cell_band;
+    int32_t banded;
+    int32_t I;
+    const float *weights;      // [I, n] or nullptr (ones)
+    const float *targets;      // [I, n, C] with a set
+    const float *dist_targets; // [I, n] or nullptr (zeros)
+    const float *pose;         // [I, 12]: R row-major, then t
+    const float *centroid;     // [I, 3]: the model's weighted centroid
+    const int32_t *skip;       // [I] or nullptr: non-zero = the instance is final, its workgroups leave at once
+    float wd, wf, outside;
+    int64_t chunks;            // workgroups per instance
+    double *partial;           // [I, chunks, kAlignRow]
+};
+struct AlignStep {
+    double *state;             // [I, kAlignState]
+    const double *partial;     // [I, chunks, kAlignRow]
+    int64_t chunks;
+    double *out;               // [I, kAlignRow]
+    int32_t it, iters;
+    double rot_tol, trans_tol;
+    float *pose_out;           // [I, 12]
+    int32_t *skip_out;         // [I]
+    double *history;           // [I, iters + 1]
+};
+int64_t align_chunks(int64_t n);
+hipError_t launch_align_centroid(const float *pts, const float *weights, int64_t I, int64_t n, float *out, hipStream_t s);
+hipError_t launch_align_accumulate(const AlignParams &A, double *out, hipStream_t s);
+hipError_t launch_align_step(const AlignStep &S, int64_t I, hipStream_t s);
+
 // raycast_kernels.hip: the first surface a ray meets in a baked volume
 constexpr float kRayMaxSamples = 131072.0f;  // a ray whose K exceeds this misses: unreachable under the entry point's 65536-step guard but for overflow
 struct RayParams {

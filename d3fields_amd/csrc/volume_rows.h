@@ -16,11 +16,11 @@ struct Cell {
     float tx, ty, tz;
 };
 
+// the point (px, py, pz) itself (align_kernels.hip locates transformed points, which live in no array)
 // cell: the flat CELL index of a valid point (untouched otherwise)
-__device__ __forceinline__ Cell locate(const VolParams &P, int64_t i, int64_t &cell)
+__device__ __forceinline__ Cell locate_at(const VolParams &P, float px, float py, float pz, int64_t &cell)
 {
-    const float *p = P.pts + 3 * i;
-    const float gx = (p[0] - P.ox) / P.h, gy = (p[1] - P.oy) / P.h, gz = (p[2] - P.oz) / P.h;
+    const float gx = (px - P.ox) / P.h, gy = (py - P.oy) / P.h, gz = (pz - P.oz) / P.h;
     Cell c;
     c.base = kNotValid;
     c.tx = c.ty = c.tz = 0.0f;
@@ -38,6 +38,13 @@ __device__ __forceinline__ Cell locate(const VolParams &P, int64_t i, int64_t &c
         }
     }
     return c;
+}
+
+// point i of P.pts
+__device__ __forceinline__ Cell locate(const VolParams &P, int64_t i, int64_t &cell)
+{
+    const float *p = P.pts + 3 * i;
+    return locate_at(P, p[0], p[1], p[2], cell);
 }
 
 __device__ __forceinline__ Cell locate(const VolParams &P, int64_t i)

@@ -675,6 +675,69 @@ int d3f_volume_peaks(const int32_t *slot, const uint8_t *mask, int32_t nx, int32
                      int64_t stride_row, int32_t radius, float threshold, float *out, int64_t out_stride, int32_t *out_count, void *workspace,
                      int64_t workspace_bytes, void *stream);
 
+/* (ABI 16, additive) Rigid alignment of point sets to a baked field: the 6 x 6 normal equations of a damped Gauss-Newton
+ * (Levenberg-Marquardt) step, summed per instance on the device without atomics, and the step itself.
+ * Per instance i: model points p_j (points [I, n, 3]), weights w_j >= 0 (weights [I, n] or NULL = ones; w_j <= 0 or NaN: the point is
+ * padding and adds nothing), a pose (R, t) = pose[i, 0..8] row-major and pose[i, 9..11], the model's weighted centroid m = centroids[i].
+ *   x_a = fma(R_a2, p_z, fma(R_a1, p_y, R_a0 * p_x)) + t_a in fp32; the pivot c = the same chain on m; xs = x - c in float64;
+ *   x is located as d3f_volume_sample locates a point (g, cell, t, valid); in_band = valid on a dense field (band NULL), valid &&
+ *   cell_band[cell] with a band (n_rows == 0: never);
+ *   a valid point has the residual r = wd (dist(x) - d_j) with g = (wd / h) d dist / d t (dist_targets [I, n] or NULL = zeros) and, with a
+ *   set and where in_band, per channel k the residual r = wf (f_k(x) - s_jk) with g = (wf / h) d f_k / d t (targets [I, n, C]); values by
+ *   the chain of d3f_volume_sample, derivatives by the chain of d3f_volume_sample_backward, wd / h and wf / h as wd * (1 / h);
+ *   per point in fp32, one fma per term, channels in the sixteen-lane order of the wide sampler, the distance term last:
+ *     G = sum g g^T,  q = sum g r,  e = sum r^2;   then in float64 with X = [xs]_x:  J^T J = [[X G X^T, X G], [G X^T, G]],  J^T r = [X q; q];
+ *   the parameters are delta = (w_x, w_y, w_z, v_x, v_y, v_z): x <- c + Exp(w)(x - c) + v, so J = [(xs x g)^T, g^T] per residual.
+ * A row of D3F_ALIGN_ROW_DOUBLES float64: [0, 21) the upper triangle of H = sum w_j J^T J row by row, [21, 27) b = sum w_j J^T r, [27] cost =
+ * sum w_j r^2 + sum over the weighted points that are NOT valid of w_j outside^2, [28] the weighted points that are valid, [29] those in_band,
+ * [30, 32) zero.  Sums across points are float64 in a fixed order: two runs give the same bytes.
+ *
+ * d3f_volume_align_centroid: centroids_out[i] = sum w_j p_j / sum w_j over the weighted points with finite coordinates, in float64, rounded to
+ * float32 (zeros when there is none).
+ * d3f_volume_align_accumulate: one launch writes one row per (instance, 256 points) to the workspace (d3f_volume_align_workspace_bytes, 8-byte
+ * aligned); with `out` [I, D3F_ALIGN_ROW_DOUBLES] not NULL a second launch adds them per instance in ascending order.  skip: NULL, or [I]
+ * int32 -- a non-zero entry makes the instance's workgroups leave at once and leaves its rows as they are.  set: NULL (the distance term
+ * alone) or ONE set as d3f_volume_sample takes it (with a band: the compacted rows); 16-byte vectors where C % 4 == 0, stride_voxel % 4 == 0
+ * and data / targets are 16-byte aligned.
+ *
+ * The state block of d3f_volume_align_step, D3F_ALIGN_STATE_DOUBLES float64 per instance (the caller fills [0, 28) and zeros the rest):
+ *   [0, 9) R and [9, 12) t of the ACCEPTED pose;  [12, 21) R and [21, 24) t of the CANDIDATE (initially the same), all float32 values;
+ *   [24, 27) the model centroid m;  [27] lambda (initially 1e-3);  [28] the accepted cost;  [29] status (D3F_ALIGN_*);  [30] accepted steps;
+ *   [31] valid and [32] in_band of the accepted pose;  [33, 39) the delta that led to the candidate;  [39, 60) H and [60, 66) b of the
+ *   accepted pose;  the rest reserved.
+ * d3f_volume_align_step(it): one wave per instance, float64.  A final instance only copies its cost to history[i, it].  Otherwise the
+ * rows of the accumulate at the candidate are added (and written to out[i]) and
+ *   it == 0 or cost < accepted cost: the candidate is accepted; for it > 0 lambda = max(lambda / 10, 1e-9), steps += 1 and, with
+ *           |w| < rot_tol and |v| < trans_tol of the delta that led to it, status = CONVERGED;
+ *   otherwise (equal or NaN included): rejected, lambda = min(10 lambda, 1e6), and STALLED once lambda has reached 1e6;
+ *   history[i, it] = the accepted cost.  Still RUNNING and it < iters: hmax = max_j H_jj, not > 0: NO_GRADIENT; D_jj = max(H_jj, 1e-9 hmax);
+ *   Cholesky of H + lambda D, a pivot that is not in (0, inf): FAILED; delta = -(H + lambda D)^-1 b.  A delta below both tolerances that was
+ *   solved at a pose accepted in this very call also ends the instance as CONVERGED, without being taken: it would lower the cost by less
+ *   than the fp32 sums resolve, so it could never be accepted.  Otherwise the candidate R = Exp(w) R, t = c + Exp(w)(t - c) + v with
+ *   Rodrigues in float64, rounded to float32, goes to the state and to pose_out[i].
+ *   A final instance, and every instance at it == iters, gets pose_out[i] = its accepted pose; a final one also skip_out[i] = 1.
+ * A solve is accumulate(pose, skip), step(0), accumulate, step(1), ... step(iters) on one stream: 2 iters + 2 launches, no allocation, no
+ * synchronisation, no atomics, and no kernel waits for another workgroup.
+ * Status errors, on the host before any HIP call: NULL vol / points / pose / centroids / workspace / state / outputs, negative I or n, a weight
+ * of a term (or outside, or a tolerance) that is negative or not finite, it outside [0, iters] (D3F_ERR_INVALID_ARG); the volume checks, C outside
+ * [1, D3F_VOLUME_MAX_CHANNELS], more than 2^31 - 1 workgroups (D3F_ERR_BAD_SHAPE); a float / int32 pointer off 4 bytes or a double pointer off 8,
+ * stride_voxel < C (D3F_ERR_BAD_LAYOUT); a short workspace (D3F_ERR_WORKSPACE).  I == 0 or n == 0: D3F_OK, nothing launched. */
+#define D3F_ALIGN_ROW_DOUBLES 32
+#define D3F_ALIGN_STATE_DOUBLES 96
+#define D3F_ALIGN_RUNNING 0
+#define D3F_ALIGN_CONVERGED 1
+#define D3F_ALIGN_STALLED 2
+#define D3F_ALIGN_NO_GRADIENT 3
+#define D3F_ALIGN_FAILED 4
+int64_t d3f_volume_align_workspace_bytes(int64_t I, int64_t n);
+int d3f_volume_align_centroid(const float *points, const float *weights, int64_t I, int64_t n, float *centroids_out, void *stream);
+int d3f_volume_align_accumulate(const d3f_volume *vol, const d3f_band *band, const d3f_volume_set *set, const float *points, const float *weights,
+                                const float *targets, const float *dist_targets, const float *pose, const float *centroids, const int32_t *skip,
+                                int64_t I, int64_t n, float dist_weight, float feat_weight, float outside, double *out, void *workspace,
+                                int64_t workspace_bytes, void *stream);
+int d3f_volume_align_step(double *state, const void *workspace, int64_t workspace_bytes, int64_t I, int64_t n, double *out, int32_t it, int32_t iters,
+                          double rot_tol, double trans_tol, float *pose_out, int32_t *skip_out, double *history, void *stream);
+
 /* (ABI 12) The first surface a ray meets in a baked volume: a fixed-step march through `dist` with one linear interpolation at the
  * sign change.  Everything in fp32.  Ray i is p(t) = o + t*d; d need not be unit.
  *   once per ray: go_a = (o_a - origin_a) / h, gd_a = d_a / h (IEEE divisions), len = sqrtf(fma(d_z, d_z, fma(d_y, d_y, d_x*d_x)));
