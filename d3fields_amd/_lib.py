@@ -38,6 +38,7 @@ PEAKS_MAX_RADIUS = 8
 ALIGN_ROW_DOUBLES, ALIGN_STATE_DOUBLES = 32, 96
 ALIGN_RUNNING, ALIGN_CONVERGED, ALIGN_STALLED, ALIGN_NO_GRADIENT, ALIGN_FAILED = 0, 1, 2, 3, 4
 ALIGN_CHUNK = 256
+CONSENSUS_MAX_POINTS, CONSENSUS_MAX_CANDIDATES, CONSENSUS_MAX_SURVIVORS = 64, 8, 1 << 16
 POOL_MEAN, POOL_VOTES = 0, 1
 POOL_CHUNK = 256
 POOL_MAX_VOTE_CHANNELS = 256
@@ -171,6 +172,11 @@ SIGNATURES = {
     "d3f_volume_align_accumulate": (ctypes.c_int, [ctypes.POINTER(Volume), ctypes.POINTER(Band), ctypes.POINTER(VolumeSet), _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                                    _i64, _i64, _f32, _f32, _f32, _vp, _vp, _i64, _vp]),
     "d3f_volume_align_step": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _i32, _i32, _f64, _f64, _vp, _vp, _vp, _vp]),
+    "d3f_pose_consensus_workspace_bytes": (_i64, [_i32, _i32, _i64, _i64]),
+    "d3f_pose_consensus_score": (ctypes.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _i64, _f32, _f64, _f64, _f64, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "d3f_pose_consensus_select": (ctypes.c_int, [_vp, _vp, _i32, _i32, _vp, _i64, _f32, _f64, _f64, _f64, _vp, _i32, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp,
+                                                 _vp, _i64, _vp]),
+    "d3f_pose_refit": (ctypes.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, _f32, _vp, _vp, _vp, _vp]),
     "d3f_volume_raycast": (ctypes.c_int, [ctypes.POINTER(Volume), _vp, _vp, _i64, ctypes.POINTER(Pinhole), _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp]),
     "d3f_fps_workspace_bytes": (_i64, [_i64]),
     "d3f_fps_pixels_workspace_bytes": (_i64, [_i64]),

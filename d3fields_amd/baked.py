@@ -1356,6 +1356,48 @@ class BakedField:
         return {"rot": R.transpose(1, 2).contiguous(), "trans": t.contiguous(), "points": moved, "cost": state[:, 28].clone(),
                 "valid": state[:, 31].to(torch.int32), "status": state[:, 29].to(torch.int32), "steps": state[:, 30].to(torch.int32), "history": history}
 
+    def relocate(self, points, name, targets, k=4, separation=None, radius_voxels=None, tau=None, n_poses=8, iters=20, min_inliers=4, shared=3,
+                 side_tol=None, min_side=None, min_sin=0.2, max_triplets=None, seed=0, max_survivors=65536, max_distance=None, dist_type="l2", **align_terms):
+        """Where is it now, from no start at all?  locate(targets) gives k candidate places per model point, consensus.consensus_poses turns
+        them into the n_poses best mutually distinct rigid motions (csrc/consensus_kernels.hip), and align() refines the refit
+        poses as n_poses instances.  ONE model per call.
+
+        points        float32 [M, 3], 3 <= M <= 64: the model's keypoints;  targets  float32 [M, C]: their descriptors in set `name`
+        k, separation, radius_voxels, max_distance, dist_type   as in locate() (neither separation nor radius_voxels: radius_voxels = 2)
+        tau           the inlier radius of the consensus, a world length (None: 2 * step)
+        n_poses, min_inliers, shared, side_tol, min_side, min_sin, max_triplets, seed, max_survivors   as in consensus_poses() (its `triplets` and
+                      `refit` are not taken: all or a seeded subset of the triplets, and always the refit);  iters and **align_terms (rot_tol, trans_tol, weights
+                      [n_poses, M], dist_weight, feat_weight, outside)   as in align()
+        -> what align() returns for the n_poses instances (a rank the consensus did not fill starts at a NaN pose and ends NO_GRADIENT), with
+           'consensus': the dict of consensus_poses() and 'best': int64 [] the argmin of 'cost' among the CONVERGED instances, -1 if none.
+        Host synchronisation: the consensus and the alignment add none in the steady state -- only what consensus_poses() states: the first
+        call with a new (M, max_triplets, seed) uploads the triplet table.  locate() itself builds small tensors from host values and so makes
+        the host wait for the stream, as it does on its own.  No autograd: outputs never require grad."""
+        from .consensus import consensus_poses
+        who = "relocate"
+        if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError("relocate: points must be [M, 3] (one model), got %s" % (list(getattr(points, "shape", ())) or type(points).__name__))
+        M = int(points.shape[0])
+        if not 3 <= M <= _lib.CONSENSUS_MAX_POINTS:             # (before locate runs: the consensus would refuse it only afterwards)
+            raise ValueError("relocate: M = %d model points, must be 3..%d" % (M, _lib.CONSENSUS_MAX_POINTS))
+        k = self._peak_k(who, k)
+        pts = self._align_tensor(who, "points", points, (M, 3))
+        tg = self._align_tensor(who, "targets", targets, (M, self._channels(self._names([name])[0])))
+        if separation is None and radius_voxels is None:
+            radius_voxels = 2
+        tau = 2.0 * self.step if tau is None else float(tau)
+        hits = self.locate(tg, name, k=k, radius_voxels=radius_voxels, separation=separation, max_distance=max_distance, dist_type=dist_type)
+        cons = consensus_poses(pts, hits["refined"].to(torch.float32), tau, n_poses=n_poses, min_inliers=min_inliers, shared=shared, side_tol=side_tol,
+                               min_side=min_side, min_sin=min_sin, max_triplets=max_triplets, seed=seed, max_survivors=max_survivors)
+        H = cons["refit_rot"].shape[0]
+        fit = self.align(pts[None].expand(H, M, 3), name, tg[None].expand(H, M, tg.shape[1]), rot=cons["refit_rot"], trans=cons["refit_trans"], iters=iters,
+                         **align_terms)
+        done = fit["status"] == _lib.ALIGN_CONVERGED
+        cost = torch.where(done, fit["cost"], torch.full_like(fit["cost"], float("inf")))
+        fit["best"] = torch.where(done.any(), torch.argmin(cost), torch.full((), -1, dtype=torch.int64, device=self.device))
+        fit["consensus"] = cons
+        return fit
+
     # ---- rays -----------------------------------------------------------------------------------------------------------------
     def _check_rays(self, origins, dirs):
         for who, t in (("origins", origins), ("dirs", dirs)):

@@ -1217,6 +1217,177 @@ int d3f_volume_align_step(double *state, const void *workspace, int64_t workspac
     return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_align_step launch");
 }
 
+// ---- consensus poses from (model point, candidate) triples (consensus_kernels.hip) ----
+namespace {
+
+int64_t up256(int64_t b) { return (b + 255) / 256 * 256; }
+
+// the pieces of the workspace, in order; -> total bytes
+struct ConsensusLayout {
+    int64_t head, eq, fl, scan, surv_h, surv_count, alive, surv_assign, total;
+};
+ConsensusLayout consensus_layout(int64_t T, int64_t max_survivors)
+{
+    const int64_t nb = d3f::consensus_blocks(T);
+    ConsensusLayout L;
+    L.head = 0;
+    L.eq = up256(d3f::kConsHeadWords * 4);
+    L.fl = L.eq + up256(nb * 4);
+    L.scan = L.fl + up256(nb * 4);
+    L.surv_h = L.scan + up256(d3f::scan_scratch_bytes(nb));
+    L.surv_count = L.surv_h + up256(max_survivors * 4);
+    L.alive = L.surv_count + up256(max_survivors);
+    L.surv_assign = L.alive + up256(max_survivors);
+    L.total = L.surv_assign + up256(max_survivors * d3f::kConsMaxM);
+    return L;
+}
+
+// M, k, n_trip -> T, or a status
+int consensus_shape(const char *who, int32_t M, int32_t k, int64_t n_trip, int64_t &T)
+{
+    if (n_trip < 0) return fail(D3F_ERR_INVALID_ARG, "%s: n_trip=%lld is negative", who, (long long)n_trip);
+    if (M < 3 || M > D3F_CONSENSUS_MAX_POINTS || k < 1 || k > D3F_CONSENSUS_MAX_CANDIDATES)
+        return fail(D3F_ERR_BAD_SHAPE, "%s: M=%d outside [3, %d] or k=%d outside [1, %d]", who, M, D3F_CONSENSUS_MAX_POINTS, k, D3F_CONSENSUS_MAX_CANDIDATES);
+    const int64_t k3 = (int64_t)k * k * k;
+    if (n_trip > 0x7fffffffLL / k3) return fail(D3F_ERR_BAD_SHAPE, "%s: n_trip=%lld times k^3=%lld is above 2^31 - 1 hypotheses", who, (long long)n_trip, (long long)k3);
+    T = n_trip * k3;
+    return D3F_OK;
+}
+
+int consensus_terms(const char *who, float tau2, double side_tol, double min_side, double min_sin)
+{
+    if (!(tau2 > 0.0f) || !finite_nonneg(tau2)) return fail(D3F_ERR_INVALID_ARG, "%s: tau2 must be finite and positive", who);
+    if (!finite_nonneg(side_tol) || !finite_nonneg(min_side) || !finite_nonneg(min_sin) || min_sin > 1.0)
+        return fail(D3F_ERR_INVALID_ARG, "%s: side_tol / min_side must be finite and not negative, min_sin in [0, 1]", who);
+    return D3F_OK;
+}
+
+}  // namespace
+
+int64_t d3f_pose_consensus_workspace_bytes(int32_t M, int32_t k, int64_t n_trip, int64_t max_survivors)
+{
+    int64_t T = 0;
+    if (consensus_shape("pose_consensus_workspace_bytes", M, k, n_trip, T) != D3F_OK) return 0;
+    if (max_survivors < 1 || max_survivors > D3F_CONSENSUS_MAX_SURVIVORS) return 0;
+    return consensus_layout(T, max_survivors).total;
+}
+
+int d3f_pose_consensus_score(const float *model, const float *cand, int32_t M, int32_t k, const int32_t *triplets, const int32_t *triplets_host,
+                             int64_t n_trip, float tau2, double side_tol, double min_side, double min_sin, uint8_t *count_out, float *pose_out,
+                             int8_t *assign_out, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    const char *who = "pose_consensus_score";
+    int64_t T = 0;
+    int rc = consensus_terms(who, tau2, side_tol, min_side, min_sin);
+    if (rc != D3F_OK) return rc;
+    rc = consensus_shape(who, M, k, n_trip, T);
+    if (rc != D3F_OK) return rc;
+    if (n_trip == 0) return D3F_OK;
+    if (!model || !cand || !triplets || !triplets_host || !count_out || !workspace)
+        return fail(D3F_ERR_INVALID_ARG, "%s: model / cand / triplets / triplets_host / count_out / workspace must be non-NULL", who);
+    for (int64_t t = 0; t < n_trip; ++t) {
+        const int32_t i = triplets_host[3 * t], j = triplets_host[3 * t + 1], l = triplets_host[3 * t + 2];
+        if (!(0 <= i && i < j && j < l && l < M)) return fail(D3F_ERR_BAD_SHAPE, "%s: triplet %lld = (%d, %d, %d) is not 0 <= i < j < l < M=%d", who, (long long)t, i, j, l, M);
+    }
+    if (!aligned(model, 4) || !aligned(cand, 4) || !aligned(triplets, 4) || !aligned(pose_out, 4) || !aligned(workspace, 16))
+        return fail(D3F_ERR_BAD_LAYOUT, "%s: model / cand / triplets / pose_out must be 4-byte aligned, the workspace 16-byte aligned", who);
+    if (workspace_bytes < up256(d3f::kConsHeadWords * 4)) return fail(D3F_ERR_WORKSPACE, "%s: needs %lld workspace bytes", who, (long long)up256(d3f::kConsHeadWords * 4));
+    d3f::ConsensusParams C;
+    C.model = model;
+    C.cand = cand;
+    C.trip = triplets;
+    C.M = M;
+    C.k = k;
+    C.T = T;
+    C.tau2 = tau2;
+    C.side_tol = side_tol;
+    C.min_side = min_side;
+    C.min_sin2 = min_sin * min_sin;
+    C.count = count_out;
+    C.pose_dbg = pose_out;
+    C.assign_dbg = assign_out;
+    C.head = static_cast<uint32_t *>(workspace);
+    hipError_t e = d3f::launch_consensus_score(C, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "pose_consensus_score launch");
+}
+
+int d3f_pose_consensus_select(const float *model, const float *cand, int32_t M, int32_t k, const int32_t *triplets, int64_t n_trip, float tau2,
+                              double side_tol, double min_side, double min_sin, const uint8_t *count, int32_t min_inliers, int32_t shared,
+                              int64_t max_survivors, int32_t n_poses, int32_t *hyp_out, int32_t *inliers_out, int8_t *assign_out, float *pose_out,
+                              int32_t *stats_out, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    const char *who = "pose_consensus_select";
+    int64_t T = 0;
+    int rc = consensus_terms(who, tau2, side_tol, min_side, min_sin);
+    if (rc != D3F_OK) return rc;
+    if (min_inliers < 3 || min_inliers > D3F_CONSENSUS_MAX_POINTS || shared < 1 || shared > D3F_CONSENSUS_MAX_POINTS)
+        return fail(D3F_ERR_INVALID_ARG, "%s: min_inliers=%d outside [3, 64] or shared=%d outside [1, 64]", who, min_inliers, shared);
+    if (max_survivors < 1 || max_survivors > D3F_CONSENSUS_MAX_SURVIVORS)
+        return fail(D3F_ERR_INVALID_ARG, "%s: max_survivors=%lld outside [1, %d]", who, (long long)max_survivors, D3F_CONSENSUS_MAX_SURVIVORS);
+    rc = consensus_shape(who, M, k, n_trip, T);
+    if (rc != D3F_OK) return rc;
+    if (n_poses < 1 || n_poses > D3F_CONSENSUS_MAX_POINTS) return fail(D3F_ERR_BAD_SHAPE, "%s: n_poses=%d outside [1, 64]", who, n_poses);
+    if (n_trip == 0) return D3F_OK;
+    if (!model || !cand || !triplets || !count || !hyp_out || !inliers_out || !assign_out || !pose_out || !stats_out || !workspace)
+        return fail(D3F_ERR_INVALID_ARG, "%s: model / cand / triplets / count / the outputs / workspace must be non-NULL", who);
+    if (!aligned(model, 4) || !aligned(cand, 4) || !aligned(triplets, 4) || !aligned(hyp_out, 4) || !aligned(inliers_out, 4) || !aligned(assign_out, 4) ||
+        !aligned(pose_out, 4) || !aligned(stats_out, 4) || !aligned(workspace, 16))
+        return fail(D3F_ERR_BAD_LAYOUT, "%s: float / int32 arrays and assign_out must be 4-byte aligned, the workspace 16-byte aligned", who);
+    const ConsensusLayout L = consensus_layout(T, max_survivors);
+    if (workspace_bytes < L.total) return fail(D3F_ERR_WORKSPACE, "%s: needs %lld workspace bytes", who, (long long)L.total);
+    unsigned char *ws = static_cast<unsigned char *>(workspace);
+    d3f::ConsensusSelect S;
+    S.C.model = model;
+    S.C.cand = cand;
+    S.C.trip = triplets;
+    S.C.M = M;
+    S.C.k = k;
+    S.C.T = T;
+    S.C.tau2 = tau2;
+    S.C.side_tol = side_tol;
+    S.C.min_side = min_side;
+    S.C.min_sin2 = min_sin * min_sin;
+    S.C.count = const_cast<uint8_t *>(count);
+    S.C.pose_dbg = nullptr;
+    S.C.assign_dbg = nullptr;
+    S.C.head = reinterpret_cast<uint32_t *>(ws + L.head);
+    S.min_inliers = min_inliers;
+    S.shared = shared;
+    S.n_poses = n_poses;
+    S.max_survivors = (uint32_t)max_survivors;
+    S.eq_block = reinterpret_cast<uint32_t *>(ws + L.eq);
+    S.fl_block = reinterpret_cast<uint32_t *>(ws + L.fl);
+    S.scan_scratch = ws + L.scan;
+    S.surv_h = reinterpret_cast<int32_t *>(ws + L.surv_h);
+    S.surv_count = ws + L.surv_count;
+    S.alive = ws + L.alive;
+    S.surv_assign = reinterpret_cast<int8_t *>(ws + L.surv_assign);
+    S.hyp_out = hyp_out;
+    S.count_out = inliers_out;
+    S.stats_out = stats_out;
+    S.assign_out = assign_out;
+    S.pose_out = pose_out;
+    hipError_t e = d3f::launch_consensus_select(S, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "pose_consensus_select launch");
+}
+
+int d3f_pose_refit(const float *model, const float *cand, int32_t M, int32_t k, const int8_t *assign, int32_t n_poses, float tau2, float *pose_out,
+                   double *rmse_out, int32_t *inliers_out, void *stream)
+{
+    const char *who = "pose_refit";
+    int64_t T = 0;
+    if (!(tau2 > 0.0f) || !finite_nonneg(tau2)) return fail(D3F_ERR_INVALID_ARG, "%s: tau2 must be finite and positive", who);
+    int rc = consensus_shape(who, M, k, 0, T);
+    if (rc != D3F_OK) return rc;
+    if (n_poses < 0 || n_poses > D3F_CONSENSUS_MAX_POINTS) return fail(D3F_ERR_BAD_SHAPE, "%s: n_poses=%d outside [0, 64]", who, n_poses);
+    if (n_poses == 0) return D3F_OK;
+    if (!model || !cand || !assign || !pose_out || !rmse_out || !inliers_out) return fail(D3F_ERR_INVALID_ARG, "%s: model / cand / assign / the outputs must be non-NULL", who);
+    if (!aligned(model, 4) || !aligned(cand, 4) || !aligned(pose_out, 4) || !aligned(inliers_out, 4) || !aligned(rmse_out, 8))
+        return fail(D3F_ERR_BAD_LAYOUT, "%s: float / int32 arrays must be 4-byte aligned, rmse_out 8-byte aligned", who);
+    hipError_t e = d3f::launch_pose_refit(model, cand, M, k, assign, n_poses, tau2, pose_out, rmse_out, inliers_out, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "pose_refit launch");
+}
+
 // ---- the first surface a ray meets in a baked volume (raycast_kernels.hip) ----
 int d3f_volume_raycast(const d3f_volume *vol, const float *origins, const float *dirs, int64_t n, const d3f_pinhole *camera,
                        float march_step, float t_near, float t_far, float *out_t, uint8_t *out_hit, float *out_points,

@@ -330,6 +330,42 @@ hipError_t launch_align_centroid(const float *pts, const float *weights, int64_t
 hipError_t launch_align_accumulate(const AlignParams &A, double *out, hipStream_t s);
 hipError_t launch_align_step(const AlignStep &S, int64_t I, hipStream_t s);
 
+// consensus_kernels.hip: consensus poses from (model point, candidate) triples
+constexpr int kConsMaxM = D3F_CONSENSUS_MAX_POINTS, kConsMaxK = D3F_CONSENSUS_MAX_CANDIDATES;
+constexpr int kConsHeadWords = 128;      // the head of the workspace: [0, 65) the histogram of counts, then the words below
+constexpr int kConsGated = 65, kConsCut = 66, kConsTake = 67, kConsSurvivors = 68;
+struct ConsensusParams {
+    const float *model;        // [M, 3]
+    const float *cand;         // [M, k, 3]
+    const int32_t *trip;       // [n_trip, 3]
+    int32_t M, k;
+    int64_t T;                 // n_trip * k^3
+    float tau2;
+    double side_tol, min_side, min_sin2;
+    uint8_t *count;            // [T]
+    float *pose_dbg;           // [T, 12] or nullptr
+    int8_t *assign_dbg;        // [T, M] or nullptr
+    uint32_t *head;            // [kConsHeadWords]
+};
+struct ConsensusSelect {
+    ConsensusParams C;         // count is read here; pose_dbg / assign_dbg unused
+    int32_t min_inliers, shared, n_poses;
+    uint32_t max_survivors;
+    uint32_t *eq_block, *fl_block;      // [ceil(T / 256)] each
+    void *scan_scratch;
+    int32_t *surv_h;           // [max_survivors]
+    uint8_t *surv_count, *alive;
+    int8_t *surv_assign;       // [max_survivors, 64]
+    int32_t *hyp_out, *count_out, *stats_out;
+    int8_t *assign_out;        // [n_poses, 64]
+    float *pose_out;           // [n_poses, 12]
+};
+int64_t consensus_blocks(int64_t T);
+hipError_t launch_consensus_score(const ConsensusParams &C, hipStream_t s);
+hipError_t launch_consensus_select(const ConsensusSelect &S, hipStream_t s);
+hipError_t launch_pose_refit(const float *model, const float *cand, int M, int k, const int8_t *assign, int n_poses, float tau2, float *pose_out, double *rmse_out,
+                             int32_t *count_out, hipStream_t s);
+
 // raycast_kernels.hip: the first surface a ray meets in a baked volume
 constexpr float kRayMaxSamples = 131072.0f;  // a ray whose K exceeds this misses: unreachable under the entry point's 65536-step guard but for overflow
 struct RayParams {

@@ -738,6 +738,61 @@ int d3f_volume_align_accumulate(const d3f_volume *vol, const d3f_band *band, con
 int d3f_volume_align_step(double *state, const void *workspace, int64_t workspace_bytes, int64_t I, int64_t n, double *out, int32_t it, int32_t iters,
                           double rot_tol, double trans_tol, float *pose_out, int32_t *skip_out, double *history, void *stream);
 
+/* (ABI 16, additive: four symbols and three constants; a client detects the feature by the symbol.)  Which pose explains these matches?
+ * Consensus poses from M model points with k candidate places each (csrc/consensus_kernels.hip).
+ *   model      float32 [M, 3], 3 <= M <= D3F_CONSENSUS_MAX_POINTS;
+ *   cand       float32 [M, k, 3], 1 <= k <= D3F_CONSENSUS_MAX_CANDIDATES; a row with a NaN coordinate is padding;
+ *   triplets   int32 [n_trip, 3] on the DEVICE, triplets_host the same table in HOST memory (it is what the call validates: 0 <= i < j < l < M;
+ *              a device entry that fails this test rejects its hypotheses, so a wrong copy cannot read out of bounds);
+ *   a hypothesis is h = (trip * k + a) * k * k + b * k + c: triplet (i, j, l) with the candidate digits (a, b, c); T = n_trip k^3 <= 2^31 - 1.
+ * The arithmetic contract.  Only IEEE + - * / sqrt in the stated order and NO fma, so that a NumPy restatement gives the same bits.
+ *   gate, in float64 from the float32 inputs:  u = p_j - p_i, v = p_l - p_i, w = v - u;  U = c_jb - c_ia, V = c_lc - c_ia, W = V - U;
+ *     |x|^2 = (x0 x0 + x1 x1) + x2 x2;  a x b = (a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 - a1 b0).  Rejected: a NaN among the nine candidate
+ *     coordinates; not (|u|, |v|, |w| >= min_side); not (||U| - |u||, ||V| - |v||, ||W| - |w|| <= side_tol); not (|u x v|^2 >= (min_sin^2
+ *     |u|^2) |v|^2), or not the same of (U, V).  A NaN rejects.  A rejected hypothesis has count 0 and takes no further part;
+ *   pose, in float64:  e1 = u / |u|, e3 = (u x v) / |u x v|, e2 = e3 x e1;  f1, f3, f2 the same of (U, V);  R_ab = (f1_a e1_b + f2_a e2_b)
+ *     + f3_a e3_b;  ps = ((p_i + p_j) + p_l) / 3, cs = ((c_ia + c_jb) + c_lc) / 3;  t_a = cs_a - ((R_a0 ps_0 + R_a1 ps_1) + R_a2 ps_2); every
+ *     entry is rounded once to float32.  A pose is 12 floats: R row-major, then t (x = R p + t);
+ *   score, in float32, per model point q and candidate s:  x_a = ((R_a0 p_x + R_a1 p_y) + R_a2 p_z) + t_a, d = x - c_qs,
+ *     d2 = (dx dx + dy dy) + dz dz; the assignment of q is the s with the smallest d2 <= tau2, ties to the lower s, else none (-1); a NaN
+ *     compares false; tau2 is the caller's float32; count = the number of assigned points;
+ *   selection:  the survivors are the hypotheses with count >= min_inliers, ordered by (count descending, h ascending); only the best
+ *     max_survivors are kept.  Then n_poses rounds: take the best live survivor and kill every survivor that shares at least `shared`
+ *     identical (point, candidate) assignments with it (the winner included).  Integer-exact and independent of any order of execution;
+ *   refit:  Horn's closed form in float64 over the assigned pairs (p_q, c_{q, s_q}), ascending q: centroids pm, cm (sum / n), S_ab = sum
+ *     (p - pm)_a (c - cm)_b, the symmetric 4 x 4 matrix N of S, its largest eigenvector by 12 cyclic Jacobi sweeps (zero entries are
+ *     skipped), R = the quaternion's matrix / |quat|^2, t = cm - R pm, rounded to float32;  rmse = sqrt(sum |R32 p + t32 - c|^2 / n) in float64.
+ * d3f_pose_consensus_score: count_out uint8 [T]; pose_out float32 [T, 12] and assign_out int8 [T, M] may be NULL (they exist for tests; a
+ *   rejected hypothesis has a pose of zeros and assignments of -1).  Zeroes the head of the workspace and leaves there the histogram of counts
+ *   and the number of hypotheses that passed the gate, which d3f_pose_consensus_select reads: the two are called in this order with the same
+ *   arguments and the same workspace (d3f_pose_consensus_workspace_bytes, 16-byte aligned).
+ * d3f_pose_consensus_select: hyp_out int32 [n_poses] (-1: no such rank), inliers_out int32 [n_poses] (-1), assign_out int8 [n_poses, 64]
+ *   (-1: none, and beyond M), pose_out float32 [n_poses, 12] (NaN), stats_out int32 [4]: poses found, hypotheses that passed the gate,
+ *   survivors, the count at the cut.  max_survivors is at most D3F_CONSENSUS_MAX_SURVIVORS = 65536: the rounds run in ONE workgroup, which reads every
+ *   live survivor's 64-byte row once per round (at 65536 survivors and 64 rounds 256 MB through one compute unit); a longer list is not built.
+ * d3f_pose_refit: assign int8 [n_poses, 64] as select writes it; a row with fewer than 3 assigned points gives a NaN pose, a NaN rmse and
+ *   count -1.  pose_out float32 [n_poses, 12], rmse_out float64 [n_poses], inliers_out int32 [n_poses]: the count of the score at the refit pose.
+ * Caller's stream, no allocation, no synchronisation, no float atomic; no kernel waits for another workgroup.  Status errors, on the host
+ * before any HIP call: a NULL pointer, tau2 / side_tol / min_side / min_sin not finite or out of range (tau2 > 0, the others >= 0),
+ * min_inliers outside [3, 64], shared outside [1, 64], max_survivors outside [1, D3F_CONSENSUS_MAX_SURVIVORS], n_trip < 0
+ * (D3F_ERR_INVALID_ARG); M, k or n_poses (1..64) out of range, a triplet that is not 0 <= i < j < l < M, T above 2^31 - 1 (D3F_ERR_BAD_SHAPE);
+ * a pointer not aligned to its element, the workspace not to 16 bytes (D3F_ERR_BAD_LAYOUT); a short workspace (D3F_ERR_WORKSPACE).
+ * n_trip == 0 (and n_poses == 0 for the refit): D3F_OK, nothing launched, no output is written: there are zero poses, and the caller's
+ * outputs keep the padding it put there. */
+#define D3F_CONSENSUS_MAX_POINTS 64
+#define D3F_CONSENSUS_MAX_CANDIDATES 8
+#define D3F_CONSENSUS_MAX_SURVIVORS (1 << 16)
+int64_t d3f_pose_consensus_workspace_bytes(int32_t M, int32_t k, int64_t n_trip, int64_t max_survivors);
+int d3f_pose_consensus_score(const float *model, const float *cand, int32_t M, int32_t k, const int32_t *triplets, const int32_t *triplets_host,
+                             int64_t n_trip, float tau2, double side_tol, double min_side, double min_sin, uint8_t *count_out, float *pose_out,
+                             int8_t *assign_out, void *workspace, int64_t workspace_bytes, void *stream);
+int d3f_pose_consensus_select(const float *model, const float *cand, int32_t M, int32_t k, const int32_t *triplets, int64_t n_trip, float tau2,
+                              double side_tol, double min_side, double min_sin, const uint8_t *count, int32_t min_inliers, int32_t shared,
+                              int64_t max_survivors, int32_t n_poses, int32_t *hyp_out, int32_t *inliers_out, int8_t *assign_out, float *pose_out,
+                              int32_t *stats_out, void *workspace, int64_t workspace_bytes, void *stream);
+int d3f_pose_refit(const float *model, const float *cand, int32_t M, int32_t k, const int8_t *assign, int32_t n_poses, float tau2, float *pose_out,
+                   double *rmse_out, int32_t *inliers_out, void *stream);
+
 /* (ABI 12) The first surface a ray meets in a baked volume: a fixed-step march through `dist` with one linear interpolation at the
  * sign change.  Everything in fp32.  Ray i is p(t) = o + t*d; d need not be unit.
  *   once per ray: go_a = (o_a - origin_a) / h, gd_a = d_a / h (IEEE divisions), len = sqrtf(fma(d_z, d_z, fma(d_y, d_y, d_x*d_x)));
