@@ -84,6 +84,8 @@ struct EvalParams {
     // device-side "this tensor holds a non-finite value" words written by d3f_map_check (depth first, then one per map);
     // n_words == 0: the host's D3F_FLAG_FINITE_MAPS alone decides.  All words zero <=> the exact invalid-view skip is allowed.
     int32_t n_words;
+    int32_t walk_snake;    // lattice walk: 1 = the 16-tile macro-bricks are walked as a serpentine (fuse_common.h: walk_tile; set by
+                           // the channel-sliced family for fp32 maps).  Here it takes the four bytes that were padding.
     const uint32_t *words[D3F_MAX_MAPS + 1];
     // device-side choice between the window kernel and the cell-run kernel for a cloud (fuse_common.h: gated_out)
     const uint32_t *gate;  // nullptr: this launch is not gated

@@ -526,6 +526,7 @@ inline bool sliced_row(const Query &q, d3f::EvalParams &P, const Plan &pl)
         for (int s = 0; s < q.n_maps; ++s) P.maps[s] = keep_maps[s];
         return false;
     }
+    P.walk_snake = (pl.walk && !half_sl) ? 1 : 0;      // fp32 maps: consecutive macro-bricks of the walk share a face (fuse_common.h: walk_tile)
     return true;
 }
 

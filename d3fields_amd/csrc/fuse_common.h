@@ -535,6 +535,7 @@ __device__ __forceinline__ void fetch_point(const EvalParams &P, int64_t i, floa
 // the Infinity-Cache window all eight XCDs share), 8^3-tile sub-bricks (the contiguous eighth one XCD takes, its L2
 // window), 4^3-tile mini-bricks, tiles row-major inside.  Blocks at the upper faces are clipped, not padded, so every
 // workgroup has work and the count is exactly ceil(nx/tx)*ceil(ny/ty)*ceil(nz/tz).  Wave-uniform integer arithmetic.
+// The channel-sliced family walks the macro-bricks as a serpentine instead (walk_level_snake below).
 struct TileBox {
     int ox, oy, oz;     // first point of the tile (lattice coordinates)
     int sx, sy, sz;     // clipped size in points
@@ -559,13 +560,48 @@ __device__ __forceinline__ void walk_level(uint32_t &rem, int b, int &ox, int &o
     ex = bx; ey = by; ez = min(b, ez - (int)k * b);
 }
 
+// position j of the block holding `rem` along one axis of a level: the blocks hold `full` positions each, except the clipped
+// one at the upper face (`last` positions), which a REVERSED walk meets first; rem becomes the position inside the block
+__device__ __forceinline__ uint32_t walk_snake_index(uint32_t &rem, uint32_t full, uint32_t last, bool rev)
+{
+    if (!rev) { const uint32_t j = rem / full; rem -= j * full; return j; }
+    if (rem < last) return 0u;
+    rem -= last;
+    const uint32_t j = rem / full;
+    rem -= j * full;
+    return j + 1u;
+}
+
+// walk_level for the macro-bricks as a SERPENTINE (EvalParams::walk_snake: the channel-sliced family): the y index runs backwards
+// in every other x slab, the z index in every other y row of the walk, so consecutive macro-bricks share a face where the
+// row-major order jumps back to the start of the next row (the texels a brick leaves in the Infinity Cache are those of its
+// neighbour).  Same bricks, same contents, same order inside: a coordinate flip, and still a bijection of the tiles.
+__device__ __forceinline__ void walk_level_snake(uint32_t &rem, int b, int &ox, int &oy, int &oz, int &ex, int &ey, int &ez)
+{
+    const uint32_t slab = (uint32_t)b * (uint32_t)ey * (uint32_t)ez;
+    const uint32_t i = rem / slab;
+    rem -= i * slab;
+    const int bx = min(b, ex - (int)i * b);
+    const int ny = (ey + b - 1) / b, nz = (ez + b - 1) / b;
+    const bool rev_y = (i & 1u) != 0u;
+    const uint32_t j = walk_snake_index(rem, (uint32_t)bx * (uint32_t)b * (uint32_t)ez, (uint32_t)bx * (uint32_t)(ey - (ny - 1) * b) * (uint32_t)ez, rev_y);
+    const int jc = rev_y ? ny - 1 - (int)j : (int)j;
+    const int by = min(b, ey - jc * b);
+    const bool rev_z = ((i * (uint32_t)ny + j) & 1u) != 0u;
+    const uint32_t k = walk_snake_index(rem, (uint32_t)bx * (uint32_t)by * (uint32_t)b, (uint32_t)bx * (uint32_t)by * (uint32_t)(ez - (nz - 1) * b), rev_z);
+    const int kc = rev_z ? nz - 1 - (int)k : (int)k;
+    ox += (int)i * b; oy += jc * b; oz += kc * b;
+    ex = bx; ey = by; ez = min(b, ez - kc * b);
+}
+
 __device__ __forceinline__ TileBox walk_tile(const EvalParams &P, int64_t t)
 {
     int ex = (P.walk_nx + P.walk_tx - 1) / P.walk_tx, ey = (P.walk_ny + P.walk_ty - 1) / P.walk_ty,
         ez = (P.walk_nz + P.walk_tz - 1) / P.walk_tz;
     int ox = 0, oy = 0, oz = 0;
     uint32_t rem = (uint32_t)t;
-    walk_level(rem, 16, ox, oy, oz, ex, ey, ez);
+    if (P.walk_snake) walk_level_snake(rem, 16, ox, oy, oz, ex, ey, ez);
+    else walk_level(rem, 16, ox, oy, oz, ex, ey, ez);
     walk_level(rem, 8, ox, oy, oz, ex, ey, ez);
     walk_level(rem, 4, ox, oy, oz, ex, ey, ez);
     const uint32_t yz = (uint32_t)ey * (uint32_t)ez;

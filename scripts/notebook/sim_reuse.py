@@ -76,8 +76,9 @@ def bricks(bx, by, bz, inner="rowmajor"):
     return np.argsort(key * (bx * by * bz) + sub, kind="stable")
 
 
-def lattice_walk(t=(2, 2, 2)):
-    """the three-level blocked order of fuse_eval.hip (16^3 / 8^3 / 4^3 tiles, clipped), tiles of t points"""
+def lattice_walk(t=(2, 2, 2), snake=False):
+    """the three-level blocked order of fuse_eval.hip (16^3 / 8^3 / 4^3 tiles, clipped), tiles of t points; snake: the macro-bricks
+    as a serpentine (walk_tile with EvalParams::walk_snake: y backwards in odd x slabs, z backwards in odd rows of the walk)"""
     tx, ty, tz = ix // t[0], iy // t[1], iz // t[2]
     key = np.zeros(N, np.int64)
     ex, ey, ez = (nx + t[0] - 1) // t[0], (ny + t[1] - 1) // t[1], (nz + t[2] - 1) // t[2]
@@ -88,7 +89,11 @@ def lattice_walk(t=(2, 2, 2)):
         comps.append((tx // b, ty // b, tz // b))
     key = np.zeros(N, np.int64)
     for lvl, (a, b_, c) in enumerate(comps):
-        if lvl == 0:
+        if lvl == 0 and snake:
+            nby, nbz = (ey + 15) // 16, (ez + 15) // 16
+            row = a * nby + np.where(a % 2 == 1, nby - 1 - b_, b_)
+            loc = row * nbz + np.where(row % 2 == 1, nbz - 1 - c, c)
+        elif lvl == 0:
             loc = (a * (ey // 16 + 1) + b_) * (ez // 16 + 1) + c
         else:
             bb = (16, 8, 4, 1)[lvl - 1] // (16, 8, 4, 1)[lvl]
@@ -144,6 +149,7 @@ orders = [
     ("Morton, 16-mm cells, stable (round 1)", morton_cells(0.016)),
     ("Morton, 4-mm cells", morton_cells(0.004)),
     ("blocked lattice walk 16/8/4 tiles of 2x2x2 (round 2)", lattice_walk()),
+    ("the same, macro-bricks as a serpentine (sliced family)", lattice_walk(snake=True)),
     ("bricks 8x8x8 row-major", bricks(8, 8, 8)),
     ("bricks 4x4x32 (z columns)", bricks(4, 4, 32)),
     ("bricks 16x16x2 (xy slabs)", bricks(16, 16, 2)),
