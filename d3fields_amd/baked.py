@@ -25,6 +25,10 @@ components are dropped by `min_voxels`, which `clearance(min_voxels=)` uses to k
 row of every baked set, hard votes over the channels of chosen sets, and each component's member count, centroid and covariance -- one
 call for all components, the same bytes on every run.
 
+`BakedField.parts(name, rule=, tau=)` answers "which part is this?": two neighbouring occupied voxels belong together only if their stored
+rows agree (d3f_volume_links, csrc/parts_kernels.hip; d3f_volume_components_linked) -- a `Components` in which touching
+objects with different descriptors are separate; `links()` gives the link volume alone and `components(links=)` labels over any such volume.
+
 `BakedField.travel(goals, radius=)` answers "how do I get there, and how far is it along the way": the cost-to-go field of a goal set
 through the free voxels (d3f_volume_geodesic_*, csrc/geodesic_kernels.hip) -- exact shortest lattice paths with
 integer weights, as a new field whose `dist` is the travel distance and whose `next_voxel` names the voxel to step to; `path(starts)`
@@ -540,9 +544,10 @@ class BakedField:
 
     _STATS_ROWS = 4096      # the stats rows the first launch of _label has room for
 
-    def _label(self, mask, connectivity, min_voxels, want_stats=True):
-        """d3f_volume_components on a bool volume -> (labels int32 [nx,ny,nz], K, found, stats int32 [K, 8] or None); one host read of
-        the count; more kept components than the first launch had rows for cost one re-run with the count (as _mark)"""
+    def _label(self, mask, connectivity, min_voxels, want_stats=True, links=None):
+        """d3f_volume_components on a bool volume (with a link volume: d3f_volume_components_linked) -> (labels int32 [nx,ny,nz], K, found,
+        stats int32 [K, 8] or None); one host read of the count; more kept components than the first launch had rows for cost one re-run
+        with the count (as _mark)"""
         dev = self.device
         nx, ny, nz = self.grid_shape
         site = mask.contiguous().view(torch.uint8)
@@ -552,9 +557,13 @@ class BakedField:
         ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
 
         def launch(stats, capacity):
+            tail = (nx, ny, nz, connectivity, min_voxels, _lib.ptr(labels), _lib.ptr(count), _lib.ptr(stats), capacity, _lib.ptr(ws), ws_bytes,
+                    _lib.current_stream_handle(dev))
             with torch.cuda.device(dev):
-                _lib.check(self._lib.d3f_volume_components(_lib.ptr(site), nx, ny, nz, connectivity, min_voxels, _lib.ptr(labels), _lib.ptr(count),
-                                                           _lib.ptr(stats), capacity, _lib.ptr(ws), ws_bytes, _lib.current_stream_handle(dev)))
+                if links is None:
+                    _lib.check(self._lib.d3f_volume_components(_lib.ptr(site), *tail))
+                else:
+                    _lib.check(self._lib.d3f_volume_components_linked(_lib.ptr(site), _lib.ptr(links), *tail))
             return count.tolist()
 
         if not want_stats:
@@ -568,7 +577,89 @@ class BakedField:
             launch(stats, kept)
         return labels, kept, found, stats[:kept].clone() if kept < stats.shape[0] else stats
 
-    def components(self, iso=0.0, unknown="free", connectivity=26, min_voxels=1, sites=None):
+    def _check_links(self, who, links):
+        """a caller's link volume: uint16 (or int16, the same bits) [nx, ny, nz] on this device"""
+        if not isinstance(links, torch.Tensor) or tuple(links.shape) != tuple(self.grid_shape) or links.dtype not in (torch.uint16, torch.int16):
+            raise ValueError("%s: links must be a uint16 (or int16) tensor of shape %s, as links() returns it" % (who, tuple(self.grid_shape)))
+        if links.device != self.device:
+            raise RuntimeError("%s: links is on %s, the field on %s" % (who, links.device, self.device))
+        return links.detach().contiguous()
+
+    def _members(self, sites):
+        """the voxels of a site mask whose row exists: valid and, on a banded field, stored"""
+        mask = sites & self.valid
+        return mask if self.band is None else mask & (self.slot >= 0)
+
+    def _link_rule(self, who, name, rule, tau, cos):
+        """-> (the enum, the float threshold the kernel compares with) of links() / parts()"""
+        if not self._sets:
+            raise ValueError("%s: this field holds no sets (a clearance or travel field); link the field it came from" % who)
+        self._names([name])
+        if rule == "l2":
+            if cos is not None or tau is None:
+                raise ValueError("%s: rule 'l2' takes tau (a distance between rows) and no cos" % who)
+            tau = float(tau)
+            if not tau >= 0.0:
+                raise ValueError("%s: tau must be a distance >= 0 (math.inf links every pair of finite rows), got %r" % (who, tau))
+            t = torch.tensor(tau, dtype=torch.float32)
+            return _lib.LINK_L2, float(t * t)              # float32(tau)^2, squared in float32
+        if rule == "cosine":
+            if tau is not None or cos is None:
+                raise ValueError("%s: rule 'cosine' takes cos (the smallest cosine that links) and no tau" % who)
+            cos = float(cos)
+            if not 0.0 <= cos <= 1.0:
+                raise ValueError("%s: cos must lie in [0, 1], got %r" % (who, cos))
+            return _lib.LINK_COSINE, cos
+        if rule == "argmax":
+            if tau is not None or cos is not None:
+                raise ValueError("%s: rule 'argmax' takes neither tau nor cos" % who)
+            return _lib.LINK_ARGMAX, 0.0
+        raise ValueError("%s: rule must be 'l2', 'cosine' or 'argmax', got %r" % (who, rule))
+
+    def _links(self, name, rule, threshold, members, connectivity):
+        """d3f_volume_links over a member mask (already reduced to valid and stored voxels) -> uint16 [nx, ny, nz]"""
+        dev = self.device
+        nx, ny, nz = self.grid_shape
+        if self.band is not None and self.band_voxels.shape[0] == 0:      # an empty band has no row array to point at, and no member
+            return torch.zeros((nx, ny, nz), dtype=torch.uint16, device=dev)
+        out = torch.empty((nx, ny, nz), dtype=torch.uint16, device=dev)
+        site = members.contiguous().view(torch.uint8)
+        sets = self._set_array([name])
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.d3f_volume_links(_lib.ptr(site), None, _lib.ptr(self.slot), nx, ny, nz, sets, rule, threshold, connectivity, _lib.ptr(out),
+                                                  _lib.current_stream_handle(dev)))
+        return out
+
+    def links(self, name, rule="l2", tau=None, cos=None, iso=0.0, sites=None, connectivity=26):
+        """Which neighbouring voxels belong together by their stored rows (d3f_volume_links) -> uint16 [nx, ny, nz].
+
+        Bit j of voxel v names its neighbour at offset j = 9*(dx+1) + 3*(dy+1) + (dz+1), j = 0..12 -- the 13 neighbours of lower flat index
+        -- and is set iff both voxels are members, the connectivity allows the offset and the rule accepts their rows of `name`:
+          rule="l2"      |a - b|^2 <= float32(tau)^2 (tau a distance between rows; math.inf links every pair of finite rows)
+          rule="cosine"  the cosine of the two rows is at least cos in [0, 1] (a zero row links to nothing)
+          rule="argmax"  both rows have their first maximum at the same channel: pool's vote rule, exact, for an instance-mask set
+        Members are the sites -- valid & (dist <= iso), or the caller's bool / uint8 volume -- that are valid and, on a banded field,
+        stored.  The sums are float32 in ascending channel order and reproducible bit for bit.  Callers may AND criteria of their own into
+        the result (view it as int16 for torch's bitwise operators) and hand it to components(links=).  Not differentiable."""
+        if connectivity not in (6, 18, 26):
+            raise ValueError("links: connectivity must be 6, 18 or 26, got %r" % (connectivity,))
+        code, threshold = self._link_rule("links", name, rule, tau, cos)
+        members = self._members(self._site_mask("links", iso, "free", sites))
+        return self._links(name, code, threshold, members, connectivity)
+
+    def parts(self, name, rule="l2", tau=None, cos=None, iso=0.0, sites=None, connectivity=26, min_voxels=1):
+        """The components of the occupied voxels whose neighbouring rows of `name` agree: links(), then the labelling over those links
+        (d3f_volume_components_linked) -> Components, whose `sites` is the member mask (the sites that are valid and stored).  Two touching
+        objects with different descriptors are two parts where components() sees one; on an instance-mask set rule="argmax" gives one part
+        per spatially connected piece of each instance.  pool, mask, largest, label_at, boxes_world and clearance(sites=) take the result."""
+        self._check_ccl("parts", connectivity, min_voxels)
+        code, threshold = self._link_rule("parts", name, rule, tau, cos)
+        members = self._members(self._site_mask("parts", iso, "free", sites))
+        links = self._links(name, code, threshold, members, connectivity)
+        labels, kept, found, stats = self._label(members, connectivity, min_voxels, links=links)
+        return Components(self.origin, self.step, labels, kept, found, stats, members, connectivity, min_voxels)
+
+    def components(self, iso=0.0, unknown="free", connectivity=26, min_voxels=1, sites=None, links=None):
         """The connected components of the occupied voxels (d3f_volume_components) -> Components.
 
         sites         the mask of clearance(): valid & (dist <= iso), plus the invalid voxels for unknown="occupied"; or an explicit
@@ -576,10 +667,15 @@ class BakedField:
         connectivity  6, 18 or 26: two sites are neighbours if they differ by at most 1 on every axis and by at most 1 / 2 / 3 in L1
         min_voxels    components with fewer voxels are dropped: their voxels get label 0 and the kept ones are numbered 1..count in
                       ascending order of their root, the smallest flat index
+        links         None, or a uint16 [nx, ny, nz] link volume (links(), possibly ANDed with the caller's own criteria): two neighbouring sites
+                      are then united only if the higher one's bit for that offset is set (d3f_volume_components_linked); a bit that points
+                      outside the volume or at a non-site is ignored
         Exact and reproducible: integer data, the same bytes on every run.  Works on a dense, a banded and a clearance field."""
         self._check_ccl("components", connectivity, min_voxels)
         mask = self._site_mask("components", iso, unknown, sites)
-        labels, kept, found, stats = self._label(mask, connectivity, min_voxels)
+        if links is not None:
+            links = self._check_links("components", links)
+        labels, kept, found, stats = self._label(mask, connectivity, min_voxels, links=links)
         return Components(self.origin, self.step, labels, kept, found, stats, mask, connectivity, min_voxels)
 
     # ---- pooling --------------------------------------------------------------------------------------------------------------

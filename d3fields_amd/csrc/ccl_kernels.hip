@@ -27,6 +27,8 @@
 // stale value -- a parent once stored is an ancestor for good (whoever lowers parent[a] from p to b goes on to unite p with b), and the
 // only decisive step is the atomic min, whose return value says whether `a` still was a root.  Flatten runs after the kernel boundary.
 // Integer min / max / add only: every output is a function of the input alone, two launches give identical bytes.
+// d3f_volume_components_linked (section 24) swaps the first two kernels for ccl_linked_init_kernel / ccl_linked_merge_kernel, which follow the bits of a
+// link volume instead of plain adjacency; everything from the flatten kernel on is shared.
 #include "d3f_internal.h"
 
 namespace d3f {
@@ -125,6 +127,65 @@ __global__ __launch_bounds__(kBlock) void ccl_merge_kernel(const uint8_t *__rest
             if (y > 0) ccl_line<CONN == 26>(site, parent, v, v - plane - nz, z, nz, down);
             if (y + 1 < ny) ccl_line<CONN == 26>(site, parent, v, v - plane + nz, z, nz, down);
         }
+    }
+}
+
+// ---- components over a link volume (d3f_volume_components_linked) ----
+// links: uint16 [nx, ny, nz] as d3f_volume_links writes it -- bit j of voxel v names the neighbour at offset j = 9*(dx+1) + 3*(dy+1) + (dz+1),
+// j = 0..12, all of lower flat index.  Two sites are united iff the higher one's bit is set, the connectivity allows the offset (conn_mask),
+// and the neighbour lies inside the volume and is a site: a bit that fails one of these is ignored and never followed, so a caller's own bits
+// cannot cause a read outside the volume.  Only the first two kernels differ from the site-only labelling; parents still never rise.
+
+// v is tied to v - 1 by bit 12: the same test in both kernels
+__device__ __forceinline__ bool ccl_link_down(const uint8_t *__restrict__ site, const uint16_t *__restrict__ links, int64_t v, int z, uint32_t conn_mask)
+{
+    return z > 0 && (links[v] & conn_mask & 0x1000u) != 0 && site[v - 1] != 0;
+}
+
+// ccl_init_kernel with runs of "bit 12 set" instead of runs of sites: a site's first parent is the lowest voxel it reaches through consecutive
+// bit-12 links INSIDE the wave (a link needs z > 0, so a run never crosses a line start).
+__global__ __launch_bounds__(kBlock) void ccl_linked_init_kernel(const uint8_t *__restrict__ site, const uint16_t *__restrict__ links, int32_t *__restrict__ parent,
+                                                                 int32_t *__restrict__ size, int32_t *__restrict__ count, int nz, uint32_t conn_mask, int64_t n)
+{
+    const int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const bool s = v < n && site[v] != 0;
+    const bool tied = s && ccl_link_down(site, links, v, (int)((uint32_t)v % (uint32_t)nz), conn_mask);
+    const unsigned long long word = __ballot(tied);
+    if (v == 0) count[0] = count[1] = 0;
+    if (v >= n) return;
+    size[v] = 0;
+    int p = -1;
+    if (s) {
+        const unsigned long long loose = ~word & ((2ull << lane) - 1ull);      // the lanes up to this one that are not tied to the lane below
+        const int start = loose ? 63 - __builtin_clzll(loose) : 0;            // the highest of them begins the run (none: the run enters from the wave below)
+        p = (int)v - (lane - start);
+    }
+    parent[v] = p;
+}
+
+__global__ __launch_bounds__(kBlock) void ccl_linked_merge_kernel(const uint8_t *__restrict__ site, const uint16_t *__restrict__ links, int32_t *parent, int ny,
+                                                                  int nz, uint32_t conn_mask, int64_t n)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n || site[i] == 0) return;
+    const int v = (int)i;
+    const uint32_t bits = links[v] & conn_mask;
+    if (bits == 0) return;
+    const uint32_t l = (uint32_t)v / (uint32_t)nz;
+    const int z = (int)((uint32_t)v - l * (uint32_t)nz);
+    const uint32_t x = l / (uint32_t)ny;
+    const int y = (int)(l - x * (uint32_t)ny);
+    if ((v & 63) == 0 && ccl_link_down(site, links, v, z, conn_mask)) ccl_unite(parent, v, v - 1);      // the run goes on across the wave boundary of the init kernel
+    const int plane = ny * nz;
+#pragma unroll
+    for (int j = 0; j < 12; ++j) {
+        const int dx = j / 9 - 1, dy = (j / 3) % 3 - 1, dz = j % 3 - 1;
+        if (!((bits >> j) & 1u)) continue;
+        if (dx < 0 && x == 0) continue;
+        if ((unsigned)(y + dy) >= (unsigned)ny || (unsigned)(z + dz) >= (unsigned)nz) continue;
+        const int u = v + dx * plane + dy * nz + dz;
+        if (site[u] != 0) ccl_unite(parent, v, u);
     }
 }
 
@@ -301,6 +362,25 @@ __global__ __launch_bounds__(kBlock) void ccl_box_kernel(const int32_t *__restri
 // parent, size, rank: int32 [n] each, then the scratch of the scan
 int64_t ccl_workspace_bytes(int64_t n) { return 12 * n + scan_scratch_bytes(n); }
 
+// flatten, count, number, label and box: everything after the merge kernel, the same for both labellings
+static hipError_t ccl_finish(int ny, int nz, int64_t n, int min_voxels, int32_t *parent, int32_t *size, uint32_t *rank, int32_t *out_label, int32_t *out_count,
+                             int32_t *out_stats, int capacity, hipStream_t s)
+{
+    const dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
+    // about 512 workgroups, at most 64 turns each: few enough adds on the word of a component that spans the volume, enough waves to hide the walks
+    const int iters = (int)std::min<int64_t>(64, (n + kCclFlattenSpan - 1) / kCclFlattenSpan);
+    const int64_t span = (int64_t)kBlock * iters;
+    hipLaunchKernelGGL(ccl_flatten_kernel, dim3((unsigned)((n + span - 1) / span)), block, 0, s, parent, size, out_count, iters, n);
+    hipLaunchKernelGGL(ccl_flag_kernel, grid, block, 0, s, parent, size, rank, min_voxels, n);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    e = launch_exclusive_scan_u32(rank, rank, n, rank + n, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(ccl_label_kernel, grid, block, 0, s, parent, size, rank, out_label, out_count, out_stats, capacity, min_voxels, n);
+    if (capacity > 0) hipLaunchKernelGGL(ccl_box_kernel, dim3((unsigned)((n + span - 1) / span)), block, 0, s, out_label, out_stats, capacity, ny, nz, iters, n);
+    return hipGetLastError();
+}
+
 hipError_t launch_volume_components(const uint8_t *site, int nx, int ny, int nz, int connectivity, int min_voxels, int32_t *out_label, int32_t *out_count,
                                     int32_t *out_stats, int capacity, void *workspace, hipStream_t s)
 {
@@ -316,18 +396,21 @@ hipError_t launch_volume_components(const uint8_t *site, int nx, int ny, int nz,
         hipLaunchKernelGGL(ccl_merge_kernel<18>, grid, block, 0, s, site, parent, ny, nz, n);
     else
         hipLaunchKernelGGL(ccl_merge_kernel<26>, grid, block, 0, s, site, parent, ny, nz, n);
-    // about 512 workgroups, at most 64 turns each: few enough adds on the word of a component that spans the volume, enough waves to hide the walks
-    const int iters = (int)std::min<int64_t>(64, (n + kCclFlattenSpan - 1) / kCclFlattenSpan);
-    const int64_t span = (int64_t)kBlock * iters;
-    hipLaunchKernelGGL(ccl_flatten_kernel, dim3((unsigned)((n + span - 1) / span)), block, 0, s, parent, size, out_count, iters, n);
-    hipLaunchKernelGGL(ccl_flag_kernel, grid, block, 0, s, parent, size, rank, min_voxels, n);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    e = launch_exclusive_scan_u32(rank, rank, n, rank + n, s);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(ccl_label_kernel, grid, block, 0, s, parent, size, rank, out_label, out_count, out_stats, capacity, min_voxels, n);
-    if (capacity > 0) hipLaunchKernelGGL(ccl_box_kernel, dim3((unsigned)((n + span - 1) / span)), block, 0, s, out_label, out_stats, capacity, ny, nz, iters, n);
-    return hipGetLastError();
+    return ccl_finish(ny, nz, n, min_voxels, parent, size, rank, out_label, out_count, out_stats, capacity, s);
+}
+
+hipError_t launch_volume_components_linked(const uint8_t *site, const uint16_t *links, int nx, int ny, int nz, int connectivity, int min_voxels,
+                                           int32_t *out_label, int32_t *out_count, int32_t *out_stats, int capacity, void *workspace, hipStream_t s)
+{
+    const int64_t n = (int64_t)nx * ny * nz;
+    int32_t *parent = static_cast<int32_t *>(workspace);
+    int32_t *size = parent + n;
+    uint32_t *rank = reinterpret_cast<uint32_t *>(size + n);
+    const dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
+    const uint32_t conn_mask = connectivity == 6 ? 0x1410u : connectivity == 18 ? 0x1ebau : 0x1fffu;      // bits by |dx|+|dy|+|dz| (parts_kernels.hip)
+    hipLaunchKernelGGL(ccl_linked_init_kernel, grid, block, 0, s, site, links, parent, size, out_count, nz, conn_mask, n);
+    hipLaunchKernelGGL(ccl_linked_merge_kernel, grid, block, 0, s, site, links, parent, ny, nz, conn_mask, n);
+    return ccl_finish(ny, nz, n, min_voxels, parent, size, rank, out_label, out_count, out_stats, capacity, s);
 }
 
 }  // namespace d3f

@@ -871,6 +871,57 @@ int d3f_volume_components(const uint8_t *site, int32_t nx, int32_t ny, int32_t n
     return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_components launch");
 }
 
+int d3f_volume_components_linked(const uint8_t *site, const uint16_t *links, int32_t nx, int32_t ny, int32_t nz, int32_t connectivity, int32_t min_voxels,
+                                 int32_t *out_label, int32_t *out_count, int32_t *out_stats, int32_t stats_capacity, void *workspace, int64_t workspace_bytes,
+                                 void *stream)
+{
+    if (!site || !links) return fail(D3F_ERR_INVALID_ARG, "volume_components_linked: site or links is NULL");
+    if (!out_label || !out_count) return fail(D3F_ERR_INVALID_ARG, "volume_components_linked: out_label or out_count is NULL");
+    if (connectivity != 6 && connectivity != 18 && connectivity != 26)
+        return fail(D3F_ERR_INVALID_ARG, "volume_components_linked: connectivity=%d, must be 6, 18 or 26", connectivity);
+    if (min_voxels < 1) return fail(D3F_ERR_INVALID_ARG, "volume_components_linked: min_voxels=%d, must be >= 1", min_voxels);
+    if (stats_capacity < 0) return fail(D3F_ERR_INVALID_ARG, "volume_components_linked: stats_capacity=%d is negative", stats_capacity);
+    if (stats_capacity > 0 && !out_stats)
+        return fail(D3F_ERR_INVALID_ARG, "volume_components_linked: out_stats is NULL with stats_capacity=%d", stats_capacity);
+    if (!edt_shape_ok(nx, ny, nz))
+        return fail(D3F_ERR_BAD_SHAPE, "volume_components_linked: nx=%d ny=%d nz=%d, every extent must be in [1, %d] and the volume at most 2^31 - 1 voxels",
+                    nx, ny, nz, D3F_EDT_MAX_EXTENT);
+    if (!aligned(links, 2)) return fail(D3F_ERR_BAD_LAYOUT, "volume_components_linked: links must be 2-byte aligned");
+    if (!aligned(out_label, 4) || !aligned(out_count, 4) || !aligned(out_stats, 4))
+        return fail(D3F_ERR_BAD_LAYOUT, "volume_components_linked: out_label / out_count / out_stats must be 4-byte aligned");
+    const int64_t need = d3f_volume_components_workspace_bytes(nx, ny, nz);
+    if (!workspace || workspace_bytes < need) return fail(D3F_ERR_WORKSPACE, "volume_components_linked: needs %lld workspace bytes", (long long)need);
+    if (!aligned(workspace, 4)) return fail(D3F_ERR_BAD_LAYOUT, "volume_components_linked: workspace must be 4-byte aligned");
+    hipError_t e = d3f::launch_volume_components_linked(site, links, nx, ny, nz, connectivity, min_voxels, out_label, out_count,
+                                                        stats_capacity > 0 ? out_stats : nullptr, stats_capacity, workspace, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_components_linked launch");
+}
+
+// ---- descriptor-gated links between neighbouring voxels (parts_kernels.hip) ----
+int d3f_volume_links(const uint8_t *site, const uint8_t *valid, const int32_t *slot, int32_t nx, int32_t ny, int32_t nz, const d3f_volume_set *set, int32_t rule,
+                     float threshold, int32_t connectivity, uint16_t *out_links, void *stream)
+{
+    if (!site || !set || !out_links) return fail(D3F_ERR_INVALID_ARG, "volume_links: site, set or out_links is NULL");
+    if (!set->data) return fail(D3F_ERR_INVALID_ARG, "volume_links: set->data is NULL");
+    if (rule != D3F_LINK_L2 && rule != D3F_LINK_COSINE && rule != D3F_LINK_ARGMAX) return fail(D3F_ERR_INVALID_ARG, "volume_links: unknown rule %d", rule);
+    if (connectivity != 6 && connectivity != 18 && connectivity != 26)
+        return fail(D3F_ERR_INVALID_ARG, "volume_links: connectivity=%d, must be 6, 18 or 26", connectivity);
+    if (threshold != threshold) return fail(D3F_ERR_INVALID_ARG, "volume_links: threshold is NaN (+Inf accepts every pair of finite rows under D3F_LINK_L2)");
+    if (rule == D3F_LINK_COSINE && !(threshold >= 0.0f && threshold <= 1.0f))
+        return fail(D3F_ERR_INVALID_ARG, "volume_links: threshold=%g, the cosine bound must lie in [0, 1]", (double)threshold);
+    if (!edt_shape_ok(nx, ny, nz))
+        return fail(D3F_ERR_BAD_SHAPE, "volume_links: nx=%d ny=%d nz=%d, every extent must be in [1, %d] and the volume at most 2^31 - 1 voxels", nx, ny, nz,
+                    D3F_EDT_MAX_EXTENT);
+    if (set->C < 1 || set->C > D3F_VOLUME_MAX_CHANNELS) return fail(D3F_ERR_BAD_SHAPE, "volume_links: C=%d outside [1,%d]", set->C, D3F_VOLUME_MAX_CHANNELS);
+    if (set->stride_voxel < set->C) return fail(D3F_ERR_BAD_LAYOUT, "volume_links: stride_voxel=%lld < C=%d", (long long)set->stride_voxel, set->C);
+    if (!aligned(slot, 4) || !aligned(set->data, 4) || !aligned(out_links, 2))
+        return fail(D3F_ERR_BAD_LAYOUT, "volume_links: slot / data must be 4-byte aligned, out_links 2-byte aligned");
+    const bool vec = set->C % 4 == 0 && set->stride_voxel % 4 == 0 && aligned(set->data, 16);
+    hipError_t e = d3f::launch_volume_links(site, valid, slot, nx, ny, nz, set->data, set->C, set->stride_voxel, vec, rule, threshold, connectivity, out_links,
+                                            static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_links launch");
+}
+
 // ---- mean rows, votes and moments per component (pool_kernels.hip) ----
 static bool pool_shape_ok(int32_t nx, int32_t ny, int32_t nz, int32_t K)
 {

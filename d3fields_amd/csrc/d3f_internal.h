@@ -249,6 +249,12 @@ hipError_t launch_volume_edt(const uint8_t *site, int nx, int ny, int nz, float 
 int64_t ccl_workspace_bytes(int64_t n);
 hipError_t launch_volume_components(const uint8_t *site, int nx, int ny, int nz, int connectivity, int min_voxels, int32_t *out_label, int32_t *out_count,
                                     int32_t *out_stats, int capacity, void *workspace, hipStream_t s);
+hipError_t launch_volume_components_linked(const uint8_t *site, const uint16_t *links, int nx, int ny, int nz, int connectivity, int min_voxels,
+                                           int32_t *out_label, int32_t *out_count, int32_t *out_stats, int capacity, void *workspace, hipStream_t s);
+
+// parts_kernels.hip: descriptor-gated links between neighbouring voxels; vec: rows may move as 16-byte vectors
+hipError_t launch_volume_links(const uint8_t *site, const uint8_t *valid, const int32_t *slot, int nx, int ny, int nz, const float *data, int C, int64_t stride,
+                               bool vec, int rule, float threshold, int connectivity, uint16_t *out, hipStream_t s);
 
 // pool_kernels.hip: mean rows, votes and moments of the baked field per component
 struct PoolArgs {

@@ -793,6 +793,59 @@ int d3f_pose_consensus_select(const float *model, const float *cand, int32_t M, 
 int d3f_pose_refit(const float *model, const float *cand, int32_t M, int32_t k, const int8_t *assign, int32_t n_poses, float tau2, float *pose_out,
                    double *rmse_out, int32_t *inliers_out, void *stream);
 
+/* (still ABI 16: symbols added -- two entry points and six constants; no struct or earlier entry point changes and D3F_ABI_VERSION stays 16; a
+ * client detects the feature by the symbols.)  Which part is this?  Descriptor-gated links between neighbouring voxels, and the connected
+ * components over such a link volume (csrc/parts_kernels.hip, csrc/ccl_kernels.hip).
+ *   volume       nx x ny x nz, z fastest, flat index v = (x*ny + y)*nz + z, extents in [1, D3F_EDT_MAX_EXTENT], at most 2^31 - 1 voxels;
+ *   site         uint8 [nx,ny,nz], non-zero = site;  valid: NULL or one byte per voxel;  slot: NULL or the int32 volume of a band, -1 = no row;
+ *   set          ONE set (HOST struct) as d3f_volume_pool takes it: the row of voxel v is data + v*stride_voxel, with `slot` it is
+ *                data + slot[v]*stride_voxel (slot values are trusted to address a row); `fill` is not read;
+ *   member       site[v] != 0, valid[v] != 0 (when given) and slot[v] >= 0 (when given);
+ *   offsets      (dx, dy, dz) over {-1,0,1}^3 in lexicographic order, the 13 that precede (0,0,0): j = 9*(dx+1) + 3*(dy+1) + (dz+1).  Bits 0..8 are
+ *                dx = -1, bits 9..11 are (0,-1,*), bit 12 is (0,0,-1): each names a neighbour of LOWER flat index.
+ * d3f_volume_links writes out_links uint16 [nx,ny,nz], every voxel: bit j of voxel v is set iff v is a member, u = v + offset j lies inside the
+ * volume (the rule is spatial: (x, y, 0) and (x, y-1, nz-1) are adjacent in memory and are no neighbours), |dx|+|dy|+|dz| <= 1 / 2 / 3 for
+ * connectivity 6 / 18 / 26, u is a member, and the rule accepts the rows a (of v) and b (of u).  Bits 13..15 are 0.  Every pair is evaluated
+ * once, by its higher voxel, so links are symmetric by construction.
+ *   D3F_LINK_L2      s <= threshold; the caller passes the SQUARED radius.  The comparison is false for a NaN s: a row with a NaN, or two rows
+ *                    with the same infinity in one channel, link to nothing, and a row with an infinity links to nothing under a finite
+ *                    threshold.  threshold = +Inf accepts every s that is not NaN, so every pair of finite rows;
+ *   D3F_LINK_COSINE  na > 0 && nb > 0 && dot >= 0 && (double)dot*dot >= ((double)t*t) * ((double)na*nb) with t = threshold in [0, 1]: float64
+ *                    products of the float32 sums, each rounded once; no square root, no division.  A zero row and a row with a NaN link to
+ *                    nothing; sums that overflow to infinity compare as IEEE has it (Inf >= Inf holds, 0 * Inf is NaN and does not);
+ *   D3F_LINK_ARGMAX  best(a) == best(b) with `best = 0; for c in 1..C-1: if row[c] > row[best]: best = c`: the vote rule of d3f_volume_pool
+ *                    (ties go to the lowest channel, a NaN never wins, a NaN at channel 0 stays).  Exact; meant for an instance-mask set.
+ *                    threshold is not used (it still must not be NaN).
+ * THE SUMMATION ORDER.  Every sum has one float32 accumulator that starts at +0.0f and takes the channels in ascending order c = 0 .. C-1:
+ *   s = fl(s + fl(d*d)) with d = fl(a_c - b_c);   dot = fl(dot + fl(a_c*b_c));   na = fl(na + fl(a_c*a_c));   nb = fl(nb + fl(b_c*b_c));
+ * each operation one IEEE float32 operation, nothing fused.  The vector and the scalar row path (the alignment rule of d3f_volume_sample) give
+ * the same bits; tests/parts_cases.py reproduces every sum bit for bit.
+ * One workgroup per tile of D3F_LINK_TILE_X x D3F_LINK_TILE_Y x D3F_LINK_TILE_Z voxels stages the rows of the tile and of its halo (x-1, y-1 .. y+1,
+ * z-1 .. z+1) through LDS in chunks of channels, so a row is loaded once per tile; a tile without a member writes zeros and loads no row.  No
+ * atomics, no workspace, nothing waits for another workgroup, the caller's stream, no allocation, no synchronisation; two runs give identical bytes.
+ * Status errors, nothing launched: NULL site / set / set->data / out_links, an unknown rule, connectivity not 6 / 18 / 26, a NaN threshold, a
+ * cosine threshold outside [0, 1] (D3F_ERR_INVALID_ARG); an extent outside [1, 16384], more than 2^31 - 1 voxels, C outside
+ * 1..D3F_VOLUME_MAX_CHANNELS (D3F_ERR_BAD_SHAPE); stride_voxel < C, slot or data not 4-byte aligned, out_links not 2-byte aligned
+ * (D3F_ERR_BAD_LAYOUT).
+ *
+ * d3f_volume_components_linked is d3f_volume_components with `links` after `site`: the same outputs, stats rows, numbering, workspace
+ * (d3f_volume_components_workspace_bytes) and status codes (links NULL: D3F_ERR_INVALID_ARG; not 2-byte aligned: D3F_ERR_BAD_LAYOUT).  Two sites are
+ * united iff the higher one's bit for that offset is set, the connectivity allows the offset, and the neighbour lies inside the volume and is
+ * a site; components are the classes of the transitive closure.  A bit that points outside the volume or at a non-site, and bits 13..15, are
+ * ignored and never followed: a caller may AND or OR criteria of its own into a link volume, and no bit pattern causes a read out of range.  An
+ * all-ones link volume gives exactly the labelling of d3f_volume_components. */
+#define D3F_LINK_L2 0
+#define D3F_LINK_COSINE 1
+#define D3F_LINK_ARGMAX 2
+#define D3F_LINK_TILE_X 4
+#define D3F_LINK_TILE_Y 4
+#define D3F_LINK_TILE_Z 16
+int d3f_volume_links(const uint8_t *site, const uint8_t *valid, const int32_t *slot, int32_t nx, int32_t ny, int32_t nz, const d3f_volume_set *set, int32_t rule,
+                     float threshold, int32_t connectivity, uint16_t *out_links, void *stream);
+int d3f_volume_components_linked(const uint8_t *site, const uint16_t *links, int32_t nx, int32_t ny, int32_t nz, int32_t connectivity, int32_t min_voxels,
+                                 int32_t *out_label, int32_t *out_count, int32_t *out_stats, int32_t stats_capacity, void *workspace, int64_t workspace_bytes,
+                                 void *stream);
+
 /* (ABI 12) The first surface a ray meets in a baked volume: a fixed-step march through `dist` with one linear interpolation at the
  * sign change.  Everything in fp32.  Ray i is p(t) = o + t*d; d need not be unit.
  *   once per ray: go_a = (o_a - origin_a) / h, gd_a = d_a / h (IEEE divisions), len = sqrtf(fma(d_z, d_z, fma(d_y, d_y, d_x*d_x)));
