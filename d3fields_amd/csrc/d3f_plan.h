@@ -160,11 +160,12 @@ struct Query {
         if ((flags & D3F_FLAG_LOCAL_POINTS) && n < kWindowCloudMin && map_bytes <= kInfinityCacheBytes) return false;
         return true;
     }
-    // (a flat lattice with more than 2^28 tiles per 16-tile slab would overflow the walk's 32-bit level arithmetic)
+    // (a flat lattice with more than 2^28 tiles per 16-tile slab would overflow the walk's 32-bit level arithmetic; a lattice below
+    // kSmallBatch is walked only when D3F_TUNE_FORCE_REORDER asks for it, as a small cloud is sorted only then: tests of the walk)
     bool walk_possible() const
     {
-        return lattice && 16.0 * ((lattice[1] + 1) / 2) * ((lattice[2] + 1) / 2) < 4294967296.0 && n_maps > 0 && n >= kSmallBatch &&
-               n <= 0x7fffffffLL && !(flags & D3F_TUNE_NO_REORDER) && tune.walk >= 0;
+        return lattice && 16.0 * ((lattice[1] + 1) / 2) * ((lattice[2] + 1) / 2) < 4294967296.0 && n_maps > 0 &&
+               (n >= kSmallBatch || (flags & D3F_TUNE_FORCE_REORDER)) && n <= 0x7fffffffLL && !(flags & D3F_TUNE_NO_REORDER) && tune.walk >= 0;
     }
 };
 

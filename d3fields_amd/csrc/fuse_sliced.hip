@@ -41,6 +41,7 @@ __device__ __forceinline__ void fused_eval_sliced_body(const EvalParams &P)
     float *krt = reinterpret_cast<float *>(idx_s + TP);
     CornerRec *crec_s = reinterpret_cast<CornerRec *>(smem + P.crec_offset);
     __shared__ TileBox tbs[4];
+    __shared__ uint32_t live_s;                // fp32 maps: some (point, view) pair of the workgroup passed the depth test
 
     // unit (chunk, slice) -> XCD blockIdx % 8; the unit's workgroups are consecutive in that XCD's stream
     const int xcd = (int)(blockIdx.x & 7u);
@@ -61,6 +62,7 @@ __device__ __forceinline__ void fused_eval_sliced_body(const EvalParams &P)
         if (t < P.sl_tiles) tb = walk_tile(P, t);
         tbs[threadIdx.x] = tb;
     }
+    if constexpr (!HALF) { if (threadIdx.x == 0) live_s = 0u; }
     compute_krt(P.K, P.pose, V, krt, kBlock);
     __syncthreads();
     int start[5];
@@ -80,6 +82,11 @@ __device__ __forceinline__ void fused_eval_sliced_body(const EvalParams &P)
     const float mu = P.mu;
     const float Wm1 = (float)(P.W - 1), Hm1 = (float)(P.H - 1);
     const MapDesc &m0 = P.maps[0];                                           // the sliced wide map
+    // fp32 maps: the bytes one view of it spans (below 4 GiB: d3f_api.hip, fill_map) -- the range of phase B's buffer loads -- and the
+    // offset a dead pair's corner record carries: the first byte past that range (0, i.e. texel 0 as on fp16 maps, if a lane's
+    // offset inside the texel could carry it past 32 bits)
+    const uint32_t view_bytes = (uint32_t)(((int64_t)(m0.fh - 1) * m0.sy + (int64_t)(m0.fw - 1) * m0.sx + m0.C) * ES);
+    const uint32_t dead_off = view_bytes <= 0xffff0000u ? view_bytes : 0u;
 
     // ---------------- phase A (as fused_eval_body: lane = (point, view), the views of a point adjacent) ----------------
     {
@@ -110,8 +117,8 @@ __device__ __forceinline__ void fused_eval_sliced_body(const EvalParams &P)
                 ViewRec r;
                 r.gx = o.gx; r.gy = o.gy; r.wgt = wgt; r.valid = o.valid;
                 rec[p * V + v] = r;
-                CornerRec cr;                           // invalid pair: texel 0 with zero weights (see phase B)
-                cr.o[0] = cr.o[1] = cr.o[2] = cr.o[3] = 0u;
+                CornerRec cr;                           // invalid pair: zero weights, and texel 0 or (fp32 maps) no texel (see phase B)
+                cr.o[0] = cr.o[1] = cr.o[2] = cr.o[3] = HALF ? 0u : dead_off;
                 cr.w[0] = cr.w[1] = cr.w[2] = cr.w[3] = 0.0f;
                 if (o.valid != 0.0f) {
                     const Corner c = corner_setup(m0, o.gx, o.gy);
@@ -121,6 +128,7 @@ __device__ __forceinline__ void fused_eval_sliced_body(const EvalParams &P)
                     cr.w[2] = (c.isw ? c.wsw : 0.0f) * sc; cr.w[3] = (c.ise ? c.wse : 0.0f) * sc;
                 }
                 crec_s[p * V + v] = cr;
+                if constexpr (!HALF) { if (o.valid != 0.0f) live_s = 1u; }
             }
             if (in && v == 0) {
                 const bool all_invalid = (cnt == 0.0f);
@@ -147,7 +155,16 @@ __device__ __forceinline__ void fused_eval_sliced_body(const EvalParams &P)
         const uint32_t co = (uint32_t)(slice * LP + lg) * 16u;               // byte offset of this lane's vector in a texel
         const char *__restrict__ data = reinterpret_cast<const char *>(m.data);
         auto raw = [&](const char *bv, uint32_t off) -> RT { return *reinterpret_cast<const RT *>(bv + (off + co)); };
-        for (int p = grp; p < tile_n; p += PTS) {
+        int p0 = grp;
+        if constexpr (!HALF) {
+            // no pair of the workgroup's points passed the depth test (the lattice overhangs the views): every fused row is zero,
+            // on the fast path as on the strict one (no valid view: fusion.py:386) -- straight to the stores
+            if (live_s == 0u) {
+                for (int p = grp; p < tile_n; p += PTS) store_out<VT>(m.out + (int64_t)idx_s[p] * m.C + (co >> 2), (VT)0.0f, P.store_policy);
+                p0 = tile_n;
+            }
+        }
+        for (int p = p0; p < tile_n; p += PTS) {
             const int64_t i = idx_s[p];
             const float cnt = cnt_s[p];
             const float denom = cnt + 1e-6f;
@@ -157,9 +174,63 @@ __device__ __forceinline__ void fused_eval_sliced_body(const EvalParams &P)
                 if constexpr (HALF) fma_mix8(acc, acc2, t, w);
                 else acc = v_fma<VT>(t, w, acc);
             };
-            if (!strict) {
-                // fast path, branch-free: phase A left an all-zero corner record for an invalid (point, view), so its
-                // loads hit texel 0 of the view and its term is +-0 -- adding it changes no bit.  The corner
+            if (!strict) { if constexpr (!HALF) {
+                // fast path on fp32 maps: phase A left a DEAD corner record for an invalid (point, view) -- zero weights, and offsets
+                // at the END of the view (dead_off).  The corners are fetched as raw buffer loads whose range is the view, so a dead
+                // pair's four loads are out of range: the lanes ask for no line and get zeros, the fma stay, and the term is +0 where
+                // a loaded texel gave +-0 -- acc + (+-0) has the bits of acc + (+0) unless acc is -0, equal under torch.equal.  A
+                // group of VC views whose weights are zero for both points of the wave is skipped with a scalar branch.  The corner
+                // loads of VC views are in flight together, then the views are consumed in view order with the folded weights: four
+                // fma per view straight into the sum.
+                auto all_zero = [](f32x4 w) -> bool {
+                    return ((__float_as_uint(w.x) | __float_as_uint(w.y) | __float_as_uint(w.z) | __float_as_uint(w.w)) << 1) == 0u;
+                };
+                auto view_rsrc = [&](int v) -> __amdgpu_buffer_rsrc_t {
+                    return __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(data) + (int64_t)v * m.sv * ES, 0, (int)view_bytes, 0x00020000);
+                };
+                auto fetch = [&](__amdgpu_buffer_rsrc_t r, uint32_t off) -> RT {
+                    return __builtin_bit_cast(RT, __builtin_amdgcn_raw_buffer_load_b128(r, (int)(off + co), 0, 0));
+                };
+                int v0 = 0;
+                for (; v0 + VC <= V; v0 += VC) {
+                    CornerRec cr[VC];
+                    f32x4 w[VC];
+                    bool any = false;
+#pragma unroll
+                    for (int q = 0; q < VC; ++q) {
+                        cr[q] = crec_s[p * V + v0 + q];
+                        w[q] = f32x4{cr[q].w[0], cr[q].w[1], cr[q].w[2], cr[q].w[3]};
+                        any = any || !all_zero(w[q]);
+                    }
+                    if (__builtin_amdgcn_ballot_w64(any) == 0ull) continue;      // (wave-uniform)
+                    RT a[VC], b[VC], d[VC], e[VC];
+#pragma unroll
+                    for (int q = 0; q < VC; ++q) {
+                        const __amdgpu_buffer_rsrc_t r = view_rsrc(v0 + q);
+                        a[q] = fetch(r, cr[q].o[0]); b[q] = fetch(r, cr[q].o[1]); d[q] = fetch(r, cr[q].o[2]); e[q] = fetch(r, cr[q].o[3]);
+                    }
+#pragma unroll
+                    for (int q = 0; q < VC; ++q) {
+                        accumulate(a[q], w[q].x);
+                        accumulate(b[q], w[q].y);
+                        accumulate(d[q], w[q].z);
+                        accumulate(e[q], w[q].w);
+                    }
+                }
+                for (; v0 < V; ++v0) {
+                    const CornerRec cr = crec_s[p * V + v0];
+                    const f32x4 w = f32x4{cr.w[0], cr.w[1], cr.w[2], cr.w[3]};
+                    if (__builtin_amdgcn_ballot_w64(!all_zero(w)) == 0ull) continue;     // (wave-uniform)
+                    const __amdgpu_buffer_rsrc_t r = view_rsrc(v0);
+                    const RT a = fetch(r, cr.o[0]), b = fetch(r, cr.o[1]), d = fetch(r, cr.o[2]), e = fetch(r, cr.o[3]);
+                    accumulate(a, w.x);
+                    accumulate(b, w.y);
+                    accumulate(d, w.z);
+                    accumulate(e, w.w);
+                }
+            } else {
+                // fast path on fp16-stored maps, branch-free: phase A left an all-zero corner record for an invalid (point, view), so
+                // its loads hit texel 0 of the view and its term is +-0 -- adding it changes no bit.  The corner
                 // loads of VC views are in flight together, then the views are consumed in view order with the folded
                 // weights: four fma per view straight into the sum.
                 int v0 = 0;
@@ -190,7 +261,7 @@ __device__ __forceinline__ void fused_eval_sliced_body(const EvalParams &P)
                     accumulate(d, cr.w[2]);
                     accumulate(e, cr.w[3]);
                 }
-            } else {
+            } } else {
                 for (int v = 0; v < V; ++v) {
                     const ViewRec r = rec[p * V + v];
                     const char *bv = data + (int64_t)v * m.sv * ES;

@@ -2,6 +2,7 @@
 the texels of a window of W consecutive points, for different processing orders of the 985 600-point grid.
 
     python scripts/sim_reuse.py            # prints the table that DESIGN.md section 5.3 quotes
+    python scripts/notebook/sim_reuse.py --walks   # only the orders of the walk's lower levels (profiles/sliced_walk/sim_reuse.txt)
 
 For every (point, valid view) the kernel requests the four bilinear corner texels (1536 B each at C = 384).  A texel is
 re-fetched from beyond the cache unless another point of the same window already touched it, so
@@ -103,6 +104,177 @@ def lattice_walk(t=(2, 2, 2), snake=False):
     return np.argsort(key * 64 + sub, kind="stable")
 
 
+def hit_rates(order, windows):
+    seq = ids[order]
+    out = []
+    for wnd in windows:
+        nch = N // wnd
+        blk = seq[:nch * wnd].reshape(nch, wnd * V * 4)
+        blk = np.sort(blk, axis=1)
+        valid = blk >= 0
+        uniq = ((blk[:, 1:] != blk[:, :-1]) & valid[:, 1:]).sum() + valid[:, 0].sum()
+        out.append(1.0 - uniq / valid.sum())
+    return out
+
+
+# ---- the levels BELOW the macro-bricks (python scripts/notebook/sim_reuse.py --walks; profiles/sliced_walk/sim_reuse.txt) -------------
+# The walk is generated block by block instead of through a sort key, so that a level's order may depend on where the walk
+# comes from and where it goes next.  A policy names, for the levels (16-tile macro-bricks, 8-tile sub-bricks, 4-tile mini-bricks,
+# tiles inside a mini-brick), how the blocks of that level are ordered inside their parent:
+#   "row"     row-major, x slowest (walk_level)
+#   "snake"   serpentine, x slowest: y backwards in odd x slabs, z backwards in odd rows (walk_level_snake); for a 2x2x2 parent this
+#             IS the reflected Gray code of the blocks
+#   "snake:zyx" the same with another axis order (slowest first)
+#   "hilbert" the serpentine whose axis order and mirroring (48 candidates) put its first block next to the tile the walk comes
+#             from and its last block next to the block it goes to: orientation carried from parent to parent, as a Hilbert curve
+#             does, generalised to clipped parents.  Not closed form: a bound on what carrying the orientation can give.
+WALK_LEVELS = (16, 8, 4, 1)
+
+
+def _children(n, perm, snake, mirror=(False, False, False)):
+    ns, nm, nf = int(n[perm[0]]), int(n[perm[1]]), int(n[perm[2]])
+    idx = np.arange(ns * nm * nf)
+    a = idx // (nm * nf)
+    r = idx - a * (nm * nf)
+    bw = r // nf
+    c = r - bw * nf
+    b = bw
+    if snake:
+        b = np.where(a % 2 == 1, nm - 1 - bw, bw)
+        c = np.where((a * nm + bw) % 2 == 1, nf - 1 - c, c)
+    out = np.zeros((len(idx), 3), np.int64)
+    out[:, perm[0]], out[:, perm[1]], out[:, perm[2]] = a, b, c
+    for ax in range(3):
+        if mirror[ax]:
+            out[:, ax] = int(n[ax]) - 1 - out[:, ax]
+    return out
+
+
+_PERMS = ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0))
+
+
+def _box_dist(p, o, e):
+    """L1 distance of point p to the box [o, o + e)"""
+    return int(np.maximum(0, np.maximum(o - p, p - (o + e - 1))).sum())
+
+
+def walk_tiles(e_tiles, policy):
+    """tile coordinates [n, 3] of the walk over a lattice of e_tiles tiles, the levels ordered as `policy` says"""
+    out = []
+    last = [None]
+
+    def gen(o, e, lvl, exit_):
+        b = WALK_LEVELS[lvl]
+        n = (e + b - 1) // b
+        pol = policy[lvl]
+        if pol == "hilbert":
+            best = None
+            for perm in _PERMS:
+                for m in range(8):
+                    mirror = (bool(m & 1), bool(m & 2), bool(m & 4))
+                    if any(mirror[ax] and n[ax] == 1 for ax in range(3)):
+                        continue
+                    ch = _children(n, perm, True, mirror)
+                    f, l = ch[0] * b, ch[-1] * b
+                    d_in = 0 if last[0] is None else _box_dist(last[0], o + f, np.minimum(b, e - f))
+                    d_out = 0 if exit_ is None else _box_dist(exit_, o + l, np.minimum(b, e - l))
+                    score = (d_in, d_out)
+                    if best is None or score < best[0]:
+                        best = (score, ch)
+            ch = best[1]
+        elif pol.startswith("snake"):
+            perm = tuple("xyz".index(c) for c in pol[6:]) if ":" in pol else (0, 1, 2)
+            ch = _children(n, perm, True)
+        else:
+            ch = _children(n, (0, 1, 2), False)
+        if b == 1:
+            out.append(o + ch)
+            last[0] = o + ch[-1]
+            return
+        for q in range(len(ch)):
+            co = o + ch[q] * b
+            if q + 1 < len(ch):                      # where the walk goes after this block: the nearest tile of the next one
+                no = o + ch[q + 1] * b
+                nxt = np.clip(co + np.minimum(b, e - ch[q] * b) // 2, no, no + np.minimum(b, e - ch[q + 1] * b) - 1)
+            else:
+                nxt = exit_
+            gen(co, np.minimum(b, e - ch[q] * b), lvl + 1, nxt)
+
+    gen(np.zeros(3, np.int64), np.asarray(e_tiles, np.int64), 0, None)
+    return np.concatenate(out)
+
+
+def lattice_walk_policy(t, policy):
+    """point order of the walk with tiles of t points (z fastest inside a tile, like walk_point)"""
+    e = [(nx + t[0] - 1) // t[0], (ny + t[1] - 1) // t[1], (nz + t[2] - 1) // t[2]]
+    tiles = walk_tiles(e, policy)
+    assert len(np.unique((tiles[:, 0] * e[1] + tiles[:, 1]) * e[2] + tiles[:, 2])) == e[0] * e[1] * e[2]
+    d = np.stack(np.meshgrid(np.arange(t[0]), np.arange(t[1]), np.arange(t[2]), indexing="ij"), -1).reshape(-1, 3)
+    p = tiles[:, None, :] * np.asarray(t) + d[None, :, :]
+    p = p.reshape(-1, 3)
+    p = p[(p[:, 0] < nx) & (p[:, 1] < ny) & (p[:, 2] < nz)]
+    return (p[:, 0] * ny + p[:, 1]) * nz + p[:, 2]
+
+
+def llc_hits(order, chunk=4096, cap=170000):
+    """Infinity-Cache model of DESIGN.md 5.5: the unique texels of each 4096-point chunk of the walk (what the L2s miss at least
+    once) go through an LRU of `cap` texels; the share of them found there"""
+    seq = ids[order]
+    resident = np.zeros(V * H * W_IMG, bool)
+    stamp = np.zeros(V * H * W_IMG, np.int64)
+    hits = tot = 0
+    for c in range(0, N, chunk):
+        u = np.unique(seq[c:c + chunk])
+        u = u[u >= 0]
+        hits += int(resident[u].sum())
+        tot += len(u)
+        resident[u] = True
+        stamp[u] = c
+        over = int(resident.sum()) - cap
+        if over > 0:
+            r = np.flatnonzero(resident)
+            resident[r[np.argpartition(stamp[r], over)[:over]]] = False
+    return hits / tot, tot
+
+
+def face_steps(order_tiles):
+    """share of the steps between consecutive tiles that go to a face neighbour"""
+    d = np.abs(np.diff(order_tiles, axis=0)).sum(axis=1)
+    return float((d == 1).mean())
+
+
+if "--walks" in sys.argv:
+    WALKS = [
+        ("row-major at every level (before the serpentine)", ("row", "row", "row", "row")),
+        ("today: macro-bricks serpentine", ("snake", "row", "row", "row")),
+        ("+ sub-bricks serpentine (= Gray)", ("snake", "snake", "row", "row")),
+        ("+ sub- and mini-bricks serpentine", ("snake", "snake", "snake", "row")),
+        ("+ sub-, mini-bricks and tiles serpentine", ("snake", "snake", "snake", "snake")),
+        ("today + boustrophedon tiles only", ("snake", "row", "row", "snake")),
+        ("today + mini-bricks and tiles serpentine", ("snake", "row", "snake", "snake")),
+        ("sub z-slowest serpentine, rest as today", ("snake", "snake:zyx", "row", "row")),
+        ("all lower levels z-slowest serpentine", ("snake", "snake:zyx", "snake:zyx", "snake:zyx")),
+        ("sub-bricks oriented (Hilbert-like)", ("snake", "hilbert", "row", "row")),
+        ("sub- and mini-bricks oriented", ("snake", "hilbert", "hilbert", "row")),
+        ("sub-, mini-bricks and tiles oriented", ("snake", "hilbert", "hilbert", "hilbert")),
+    ]
+    WIN = (1536, 2048, 3072, 4096)
+    for t in ((2, 2, 1), (2, 2, 2)):
+        print("\ntiles of %dx%dx%d points (%s): ideal hit rate [%%] of a window of W consecutive points; share [%%] of a 4096-point chunk's"
+              % (t + ("the channel-sliced family with a wide map alone: c2_dense" if t[2] == 1 else "with a thin map riding along: c3_dense",)))
+        print("unique texels found in an LRU of 170 k texels (the Infinity Cache); M texels the chunks touch (what the L2s fill at least once) and M texels they\nmiss in that LRU (what the fabric fetches from HBM); face steps between tiles [%]\n")
+        print("%-50s" % "order of the levels" + "".join("%8d" % w for w in WIN) + "%10s%10s%10s%8s" % ("LLC", "touched", "LLC miss", "face"))
+        e = [(nx + t[0] - 1) // t[0], (ny + t[1] - 1) // t[1], (nz + t[2] - 1) // t[2]]
+        for name, policy in WALKS:
+            order = lattice_walk_policy(t, policy)
+            assert len(np.unique(order)) == N
+            r = hit_rates(order, WIN)
+            llc, tot = llc_hits(order)
+            print("%-50s" % name + "".join("%8.2f" % (100 * x) for x in r) + "%10.2f%10.4f%10.4f%8.1f"
+                  % (100 * llc, tot / 1e6, tot * (1 - llc) / 1e6, 100 * face_steps(walk_tiles(e, policy))), flush=True)
+    sys.exit(0)
+
+
 def view_tile_major(v, tile, depth_minor=True):
     """points sorted by the pixel tile of view v they project to, then by depth along the ray"""
     tx_, ty_ = np.floor(pix[:, v, 0] / tile).astype(np.int64), np.floor(pix[:, v, 1] / tile).astype(np.int64)
@@ -128,19 +300,6 @@ def epipolar_slabs(thick=2):
     ang = np.arctan2(perp @ np.cross(base, [0, 0, 1.0]), perp[:, 2])
     slab = np.floor((ang - ang.min()) / (0.005 * thick / 1.0)).astype(np.int64)      # ~ thick grid steps at 1 m
     return np.lexsort((np.linalg.norm(perp, axis=1), rel @ base, slab))
-
-
-def hit_rates(order, windows):
-    seq = ids[order]
-    out = []
-    for wnd in windows:
-        nch = N // wnd
-        blk = seq[:nch * wnd].reshape(nch, wnd * V * 4)
-        blk = np.sort(blk, axis=1)
-        valid = blk >= 0
-        uniq = ((blk[:, 1:] != blk[:, :-1]) & valid[:, 1:]).sum() + valid[:, 0].sum()
-        out.append(1.0 - uniq / valid.sum())
-    return out
 
 
 WINDOWS = (64, 512, 1024, 2048, 4096, 32768)
