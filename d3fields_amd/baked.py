@@ -29,6 +29,10 @@ call for all components, the same bytes on every run.
 rows agree (d3f_volume_links, csrc/parts_kernels.hip; d3f_volume_components_linked) -- a `Components` in which touching
 objects with different descriptors are separate; `links()` gives the link volume alone and `components(links=)` labels over any such volume.
 
+`BakedField.flow(other, name, radius_voxels=)` answers "how did it move?": for every occupied voxel the voxel of a second field on the same
+grid, within a window, whose stored row is closest (d3f_volume_flow, csrc/flow_kernels.hip) -- a `Flow` with the
+target, the cost, a sub-voxel offset, world displacements and the forward-backward test `consistent(back)`.
+
 `BakedField.travel(goals, radius=)` answers "how do I get there, and how far is it along the way": the cost-to-go field of a goal set
 through the free voxels (d3f_volume_geodesic_*, csrc/geodesic_kernels.hip) -- exact shortest lattice paths with
 integer weights, as a new field whose `dist` is the travel distance and whose `next_voxel` names the voxel to step to; `path(starts)`
@@ -57,7 +61,7 @@ import torch
 
 from . import _lib
 
-__all__ = ["BakedField", "Components"]
+__all__ = ["BakedField", "Components", "Flow"]
 
 _RESERVED = ("dist", "valid_mask", "grid_shape")
 _POOL_KEYS = ("count", "moments", "centroid", "covariance")     # output keys of pool, next to one name + '_votes' per voted set
@@ -170,6 +174,72 @@ class Components:
         _check_points(pts, self.labels.device, "Components.label_at")
         inside, flat = _voxel_of(pts, self.origin, self.step, self.grid_shape)
         return torch.where(inside, self.labels.view(-1)[flat], torch.zeros_like(flat, dtype=torch.int32))
+
+
+def _voxel_coords(flat, grid_shape):
+    """int64 [..., 3]: (x, y, z) of flat voxel indices"""
+    ny, nz = grid_shape[1], grid_shape[2]
+    flat = flat.long()
+    return torch.stack((flat // (ny * nz), (flat // nz) % ny, flat % nz), dim=-1)
+
+
+class Flow:
+    """Dense descriptor flow from one baked field to another on the same grid (BakedField.flow).  Tensors only, on the fields' device.
+
+    target        int32 [nx, ny, nz]: the flat index (x*ny + y)*nz + z of the voxel of the other field whose row is closest, -1: unmatched
+    cost          float32 [nx, ny, nz]: the squared L2 distance of the two rows (the float32 chain of d3f_volume_flow), +Inf where unmatched
+    matched       bool [nx, ny, nz]: target >= 0
+    voxel_offset  int32 [nx, ny, nz, 3]: the target's (x, y, z) minus the voxel's, 0 where unmatched
+    axis_cost     float32 [nx, ny, nz, 6] or None (refine=False): the costs of the target's neighbours x-, x+, y-, y+, z-, z+, +Inf where one
+                  takes no part
+    offset        float64 [nx, ny, nz, 3] or None (refine=False): the sub-voxel correction in voxel units, per axis
+                  0.5 (f- - f+) / (f- - 2 f0 + f+) clamped to [-0.5, 0.5]; 0 where a side is +Inf or the denominator is not > 0; NaN where unmatched
+    origin, step, grid_shape   of the fields it came from; no reference to the fields themselves"""
+
+    def __init__(self, origin, step, target, cost, axis_cost=None):
+        self.origin, self.step, self.grid_shape = tuple(origin), float(step), torch.Size(target.shape)
+        self.target, self.cost, self.axis_cost = target, cost, axis_cost
+        self.matched = target >= 0
+        n = target.numel()
+        own = _voxel_coords(torch.arange(n, device=target.device).view(self.grid_shape), self.grid_shape)
+        to = _voxel_coords(torch.clamp(target, min=0), self.grid_shape)
+        self.voxel_offset = torch.where(self.matched[..., None], to - own, torch.zeros_like(own)).to(torch.int32)
+        self.offset = None
+        if axis_cost is not None:
+            inf = float("inf")
+            f0 = cost.double()
+            offs = []
+            for a in range(3):
+                fm, fp = axis_cost[..., 2 * a].double(), axis_cost[..., 2 * a + 1].double()
+                den = fm - 2.0 * f0 + fp
+                off = torch.clamp(0.5 * (fm - fp) / den, -0.5, 0.5)
+                offs.append(torch.where((fm < inf) & (fp < inf) & (den > 0), off, torch.zeros_like(off)))
+            out = torch.stack(offs, dim=-1)
+            self.offset = torch.where(self.matched[..., None], out, torch.full_like(out, float("nan")))
+
+    def displacement(self, refined=True):
+        """float64 [nx, ny, nz, 3]: the world vector from each voxel to its match, (voxel_offset [+ offset]) * step; NaN where unmatched"""
+        d = self.voxel_offset.double()
+        if refined:
+            if self.offset is None:
+                raise ValueError("Flow.displacement: this flow was computed with refine=False; pass refined=False")
+            return (d + self.offset) * self.step
+        return torch.where(self.matched[..., None], d * self.step, torch.full_like(d, float("nan")))
+
+    def consistent(self, back, tol_voxels=1):
+        """The forward-backward test -> bool [nx, ny, nz]: a voxel passes when it is matched, `back` (the flow of the other field to this one)
+        has a target at its target, and that voxel lies within Chebyshev distance tol_voxels of the voxel itself.  The ambiguity filter:
+        a match that the way back does not confirm is a repeated or featureless descriptor.  Integer torch indexing, no kernel."""
+        if not isinstance(back, Flow) or back.grid_shape != self.grid_shape:
+            raise ValueError("Flow.consistent: back must be a Flow on the same grid %s" % (tuple(self.grid_shape),))
+        if back.target.device != self.target.device:
+            raise ValueError("Flow.consistent: back is on %s, this flow on %s" % (back.target.device, self.target.device))
+        if isinstance(tol_voxels, bool) or not isinstance(tol_voxels, int) or tol_voxels < 0:
+            raise ValueError("Flow.consistent: tol_voxels must be an integer >= 0, got %r" % (tol_voxels,))
+        ret = back.target.view(-1)[torch.clamp(self.target, min=0).long()]
+        own = _voxel_coords(torch.arange(self.target.numel(), device=self.target.device).view(self.grid_shape), self.grid_shape)
+        near = ((_voxel_coords(torch.clamp(ret, min=0), self.grid_shape) - own).abs().amax(dim=-1) <= tol_voxels)
+        return self.matched & (ret >= 0) & near
 
 
 class BakedField:
@@ -658,6 +728,60 @@ class BakedField:
         links = self._links(name, code, threshold, members, connectivity)
         labels, kept, found, stats = self._label(members, connectivity, min_voxels, links=links)
         return Components(self.origin, self.step, labels, kept, found, stats, members, connectivity, min_voxels)
+
+    def flow(self, other, name, radius_voxels=2, max_cost=None, iso=0.0, sites=None, other_sites=None, refine=True):
+        """How did it move?  For every member voxel of this field the voxel of `other` -- a field on the same grid -- within Chebyshev distance
+        radius_voxels whose stored row of `name` is closest in L2 (d3f_volume_flow, csrc/flow_kernels.hip) -> Flow.
+
+        other          a BakedField with the same grid_shape, origin and step on the same device; either field may be dense or banded
+        radius_voxels  1..4: the half width of the search window in voxels
+        max_cost       None, or a distance between rows >= 0: a candidate takes part only if its squared distance is <= float32(max_cost)^2
+        iso, sites     this field's members, as links() takes them; other_sites: the other field's (None: its own valid & (dist <= iso))
+        refine         also the costs of the target's six axis neighbours, and from them the sub-voxel `offset`
+        Members are the sites that are valid and, on a banded field, stored.  The costs are float32 sums in ascending channel order; ties go
+        to the nearer candidate, then to the lower flat index: the same bytes on every run.  Not differentiable."""
+        if not isinstance(other, BakedField):
+            raise ValueError("flow: other must be a BakedField, got %r" % (type(other).__name__,))
+        if not self._sets or not other._sets:
+            raise ValueError("flow: a field without sets (a clearance or travel field) has no rows to compare; use the fields they came from")
+        for f, who in ((self, "this field"), (other, "the other field")):
+            if name not in f._sets:
+                raise ValueError("flow: %r was not baked in %s, which holds %s" % (name, who, f.names()))
+        if self._channels(name) != other._channels(name):
+            raise ValueError("flow: %r has %d channels here and %d in the other field" % (name, self._channels(name), other._channels(name)))
+        if tuple(self.grid_shape) != tuple(other.grid_shape) or self.origin != other.origin or self.step != other.step:
+            raise ValueError("flow: the fields must share one grid: %s at %s step %g here, %s at %s step %g there" % (
+                tuple(self.grid_shape), self.origin, self.step, tuple(other.grid_shape), other.origin, other.step))
+        if self.device != other.device:
+            raise ValueError("flow: the other field is on %s, this one on %s" % (other.device, self.device))
+        if isinstance(radius_voxels, bool) or not isinstance(radius_voxels, int) or not 1 <= radius_voxels <= _lib.FLOW_MAX_RADIUS:
+            raise ValueError("flow: radius_voxels must be an integer in 1..%d, got %r" % (_lib.FLOW_MAX_RADIUS, radius_voxels))
+        max_cost2 = math.inf
+        if max_cost is not None:
+            max_cost = float(max_cost)
+            if not max_cost >= 0.0:
+                raise ValueError("flow: max_cost must be a distance >= 0 (None: no threshold), got %r" % (max_cost,))
+            t = torch.tensor(max_cost, dtype=torch.float32)
+            max_cost2 = float(t * t)              # float32(max_cost)^2, squared in float32
+        members_a = self._members(self._site_mask("flow", iso, "free", sites))
+        members_b = other._members(other._site_mask("flow", iso if other_sites is None else 0.0, "free", other_sites))
+        dev = self.device
+        nx, ny, nz = self.grid_shape
+        empty = any(f.band is not None and f.band_voxels.shape[0] == 0 for f in (self, other))      # no row array to point at, and no member
+        if empty:
+            target = torch.full((nx, ny, nz), -1, dtype=torch.int32, device=dev)
+            cost = torch.full((nx, ny, nz), math.inf, dtype=torch.float32, device=dev)
+            axis = torch.full((nx, ny, nz, 6), math.inf, dtype=torch.float32, device=dev) if refine else None
+            return Flow(self.origin, self.step, target, cost, axis)
+        target = torch.empty((nx, ny, nz), dtype=torch.int32, device=dev)
+        cost = torch.empty((nx, ny, nz), dtype=torch.float32, device=dev)
+        axis = torch.empty((nx, ny, nz, 6), dtype=torch.float32, device=dev) if refine else None
+        site_a, site_b = members_a.contiguous().view(torch.uint8), members_b.contiguous().view(torch.uint8)
+        set_a, set_b = self._set_array([name]), other._set_array([name])
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.d3f_volume_flow(_lib.ptr(site_a), _lib.ptr(self.slot), set_a, _lib.ptr(site_b), _lib.ptr(other.slot), set_b, nx, ny, nz,
+                                                 radius_voxels, max_cost2, _lib.ptr(target), _lib.ptr(cost), _lib.ptr(axis), _lib.current_stream_handle(dev)))
+        return Flow(self.origin, self.step, target, cost, axis)
 
     def components(self, iso=0.0, unknown="free", connectivity=26, min_voxels=1, sites=None, links=None):
         """The connected components of the occupied voxels (d3f_volume_components) -> Components.

@@ -922,6 +922,32 @@ int d3f_volume_links(const uint8_t *site, const uint8_t *valid, const int32_t *s
     return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_links launch");
 }
 
+// ---- dense descriptor flow between two fields on one grid (flow_kernels.hip) ----
+int d3f_volume_flow(const uint8_t *site_a, const int32_t *slot_a, const d3f_volume_set *set_a, const uint8_t *site_b, const int32_t *slot_b,
+                    const d3f_volume_set *set_b, int32_t nx, int32_t ny, int32_t nz, int32_t radius, float max_cost2, int32_t *out_target, float *out_cost,
+                    float *out_axis_cost, void *stream)
+{
+    if (!site_a || !site_b || !set_a || !set_b) return fail(D3F_ERR_INVALID_ARG, "volume_flow: site_a, site_b, set_a or set_b is NULL");
+    if (!set_a->data || !set_b->data) return fail(D3F_ERR_INVALID_ARG, "volume_flow: set_a->data or set_b->data is NULL");
+    if (!out_target || !out_cost) return fail(D3F_ERR_INVALID_ARG, "volume_flow: out_target or out_cost is NULL");
+    if (radius < 1 || radius > D3F_FLOW_MAX_RADIUS) return fail(D3F_ERR_INVALID_ARG, "volume_flow: radius=%d outside [1,%d]", radius, D3F_FLOW_MAX_RADIUS);
+    if (max_cost2 != max_cost2) return fail(D3F_ERR_INVALID_ARG, "volume_flow: max_cost2 is NaN (+Inf means no threshold)");
+    if (!edt_shape_ok(nx, ny, nz))
+        return fail(D3F_ERR_BAD_SHAPE, "volume_flow: nx=%d ny=%d nz=%d, every extent must be in [1, %d] and the volume at most 2^31 - 1 voxels", nx, ny, nz,
+                    D3F_EDT_MAX_EXTENT);
+    if (set_a->C < 1 || set_a->C > D3F_VOLUME_MAX_CHANNELS) return fail(D3F_ERR_BAD_SHAPE, "volume_flow: C=%d outside [1,%d]", set_a->C, D3F_VOLUME_MAX_CHANNELS);
+    if (set_b->C != set_a->C) return fail(D3F_ERR_BAD_SHAPE, "volume_flow: C=%d of set_a, C=%d of set_b: the sets must have the same width", set_a->C, set_b->C);
+    if (set_a->stride_voxel < set_a->C || set_b->stride_voxel < set_b->C)
+        return fail(D3F_ERR_BAD_LAYOUT, "volume_flow: stride_voxel=%lld / %lld < C=%d", (long long)set_a->stride_voxel, (long long)set_b->stride_voxel, set_a->C);
+    if (!aligned(slot_a, 4) || !aligned(slot_b, 4) || !aligned(set_a->data, 4) || !aligned(set_b->data, 4) || !aligned(out_target, 4) || !aligned(out_cost, 4) ||
+        !aligned(out_axis_cost, 4))
+        return fail(D3F_ERR_BAD_LAYOUT, "volume_flow: slots, data and outputs must be 4-byte aligned");
+    const bool vec = set_a->C % 4 == 0 && set_a->stride_voxel % 4 == 0 && set_b->stride_voxel % 4 == 0 && aligned(set_a->data, 16) && aligned(set_b->data, 16);
+    hipError_t e = d3f::launch_volume_flow(site_a, slot_a, set_a->data, set_a->stride_voxel, site_b, slot_b, set_b->data, set_b->stride_voxel, set_a->C, vec, nx,
+                                           ny, nz, radius, max_cost2, out_target, out_cost, out_axis_cost, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_flow launch");
+}
+
 // ---- mean rows, votes and moments per component (pool_kernels.hip) ----
 static bool pool_shape_ok(int32_t nx, int32_t ny, int32_t nz, int32_t K)
 {

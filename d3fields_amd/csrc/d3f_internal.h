@@ -256,6 +256,11 @@ hipError_t launch_volume_components_linked(const uint8_t *site, const uint16_t *
 hipError_t launch_volume_links(const uint8_t *site, const uint8_t *valid, const int32_t *slot, int nx, int ny, int nz, const float *data, int C, int64_t stride,
                                bool vec, int rule, float threshold, int connectivity, uint16_t *out, hipStream_t s);
 
+// flow_kernels.hip: dense descriptor flow between two fields on one grid; vec: the rows of BOTH sets may move as 16-byte vectors
+hipError_t launch_volume_flow(const uint8_t *site_a, const int32_t *slot_a, const float *data_a, int64_t stride_a, const uint8_t *site_b, const int32_t *slot_b,
+                              const float *data_b, int64_t stride_b, int C, bool vec, int nx, int ny, int nz, int radius, float max_cost2, int32_t *out_target,
+                              float *out_cost, float *out_axis_cost, hipStream_t s);
+
 // pool_kernels.hip: mean rows, votes and moments of the baked field per component
 struct PoolArgs {
     const int32_t *label;

@@ -36,8 +36,9 @@ _SPHERES = [(-0.15, -0.10, -0.06, 0.06), (0.12, 0.05, -0.05, 0.05), (0.02, -0.22
             (0.25, -0.15, -0.04, 0.04)]
 
 
-def raycast_depth(K, Rt, H, W):
-    """Depth (camera z) of the plane z=0 and a few spheres, [V,H,W] float32."""
+def raycast_depth(K, Rt, H, W, spheres=None):
+    """Depth (camera z) of the plane z=0 and a few spheres (None: _SPHERES; else a list of (x, y, z, radius)), [V,H,W] float32."""
+    spheres = _SPHERES if spheres is None else spheres
     V = K.shape[0]
     out = np.zeros((V, H, W), np.float32)
     uu, vv = np.meshgrid(np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64))
@@ -51,7 +52,7 @@ def raycast_depth(K, Rt, H, W):
             tp = -c[2] / dw[..., 2]
         tp[~(tp > 0)] = np.inf
         best = np.minimum(best, tp)
-        for (sx, sy, sz, r) in _SPHERES:
+        for (sx, sy, sz, r) in spheres:
             oc = c - np.array([sx, sy, sz])
             a = (dw * dw).sum(-1)
             b = 2.0 * (dw * oc).sum(-1)
@@ -111,8 +112,9 @@ def make_scene(V=4, H=480, W=640, depth_kind="smooth", seed=0):
 _SPHERE_NAMES = ["mug", "mug", "box", "pen"]
 
 
-def sphere_label_images(K, Rt, depth):
+def sphere_label_images(K, Rt, depth, spheres=None):
     """[V,H,W] int64: 0 = table plane / nothing, s + 1 = the pixel's surface point lies on sphere s of the ray-cast scene."""
+    spheres = _SPHERES if spheres is None else spheres
     V, H, W = depth.shape
     out = np.zeros((V, H, W), np.int64)
     uu, vv = np.meshgrid(np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64))
@@ -121,7 +123,7 @@ def sphere_label_images(K, Rt, depth):
         d = depth[v].astype(np.float64)
         cam = np.stack([(uu - Kv[0, 2]) / Kv[0, 0] * d, (vv - Kv[1, 2]) / Kv[1, 1] * d, d], -1)
         world = (cam - t) @ R
-        for s, (sx, sy, sz, r) in enumerate(_SPHERES):
+        for s, (sx, sy, sz, r) in enumerate(spheres):
             hit = (np.linalg.norm(world - np.array([sx, sy, sz]), axis=-1) < r + 2e-3) & (d > 0)
             out[v][hit] = s + 1
     return out

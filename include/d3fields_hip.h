@@ -846,6 +846,40 @@ int d3f_volume_components_linked(const uint8_t *site, const uint16_t *links, int
                                  int32_t *out_label, int32_t *out_count, int32_t *out_stats, int32_t stats_capacity, void *workspace, int64_t workspace_bytes,
                                  void *stream);
 
+/* (still ABI 16: symbols added -- one entry point and one constant; no struct or earlier entry point changes and D3F_ABI_VERSION stays 16; a
+ * client detects the feature by the symbol.)  How did it move?  Dense descriptor flow between two baked fields on the SAME grid (DESIGN.md
+ * section 25; csrc/flow_kernels.hip): for every member voxel of field A the voxel of field B within Chebyshev distance `radius` whose stored
+ * row is closest in L2.
+ *   volume       nx x ny x nz, z fastest, flat index v = (x*ny + y)*nz + z, extents in [1, D3F_EDT_MAX_EXTENT], at most 2^31 - 1 voxels;
+ *   site_a/_b    uint8 [nx,ny,nz], non-zero = site;  slot_a/_b: NULL (dense) or the int32 volume of a band, -1 = no row; either field may be
+ *                dense or banded, independently of the other;
+ *   set_a/_b     ONE set each (HOST structs) as d3f_volume_links takes it, both with the same C in 1..D3F_VOLUME_MAX_CHANNELS; `fill` is not read;
+ *   member       of A: site_a[v] != 0 and slot_a[v] >= 0 (when given); of B likewise (a caller folds `valid` into the site byte);
+ *   candidates   of v: u = v + (dx, dy, dz) with |dx|, |dy|, |dz| <= radius, radius in 1..D3F_FLOW_MAX_RADIUS, u inside the volume (spatially:
+ *                nothing wraps through memory) and a member of B;
+ *   cost         s(v, u): one float32 accumulator that starts at +0.0f and takes the channels in ascending order, s = fl(s + fl(d*d)) with
+ *                d = fl(a_c - b_c), each operation one IEEE float32 operation, nothing fused: the L2 chain of d3f_volume_links word for word;
+ *   takes part   iff s is finite (not NaN, not +Inf) and s <= max_cost2; the caller passes the SQUARED radius, +Inf means no threshold;
+ *   winner       the candidate with the lexicographically smallest key (s, d2, j), d2 = dx^2 + dy^2 + dz^2,
+ *                j = ((dx + r)*(2r + 1) + (dy + r))*(2r + 1) + (dz + r); for a fixed v ascending j is ascending flat index of u.  With s >= +0,
+ *                d2 <= 48 and j < 729 the key packs exactly into 64 bits: bits(s) << 16 | d2 << 10 | j.
+ * Outputs, every voxel of the volume written: out_target int32 [nx,ny,nz] the flat index of the winner or -1; out_cost float32 [nx,ny,nz] the
+ * winner's s or +Inf.  -1 and +Inf go together: a non-member of A, or a member with no candidate that takes part.  out_axis_cost (NULL to
+ * skip) float32 [n, 6]: for a voxel with target t the costs s(v, t -+ e) in the order x-, x+, y-, y+, z-, z+, +Inf where the neighbour lies
+ * outside the volume, is no member of B or has a non-finite s (neither the window nor max_cost2 applies here); six +Inf for a voxel without
+ * a target.  The same chain.
+ * One workgroup per tile of D3F_LINK_TILE_X x _Y x _Z voxels of A; the window is cut into sub-windows of at most 5 x 5 x 5 offsets, one pass
+ * each over the B rows of a shifted box staged through LDS, and the running best 64-bit key makes the merge exact.  No atomics, no workspace,
+ * nothing waits for another workgroup, the caller's stream, no allocation, no synchronisation; two runs give identical bytes.
+ * Status errors, nothing launched: NULL site_a / site_b / set_a / set_b / a set's data / out_target / out_cost, radius outside
+ * 1..D3F_FLOW_MAX_RADIUS, a NaN max_cost2 (D3F_ERR_INVALID_ARG); an extent outside [1, 16384], more than 2^31 - 1 voxels, C outside
+ * 1..D3F_VOLUME_MAX_CHANNELS or different in the two sets (D3F_ERR_BAD_SHAPE); a stride_voxel < C, a slot, data or output not 4-byte aligned
+ * (D3F_ERR_BAD_LAYOUT). */
+#define D3F_FLOW_MAX_RADIUS 4
+int d3f_volume_flow(const uint8_t *site_a, const int32_t *slot_a, const d3f_volume_set *set_a, const uint8_t *site_b, const int32_t *slot_b,
+                    const d3f_volume_set *set_b, int32_t nx, int32_t ny, int32_t nz, int32_t radius, float max_cost2, int32_t *out_target, float *out_cost,
+                    float *out_axis_cost, void *stream);
+
 /* (ABI 12) The first surface a ray meets in a baked volume: a fixed-step march through `dist` with one linear interpolation at the
  * sign change.  Everything in fp32.  Ray i is p(t) = o + t*d; d need not be unit.
  *   once per ray: go_a = (o_a - origin_a) / h, gd_a = d_a / h (IEEE divisions), len = sqrtf(fma(d_z, d_z, fma(d_y, d_y, d_x*d_x)));
