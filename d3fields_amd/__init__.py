@@ -8,7 +8,7 @@ this package is the host-side mirror of the reference's Python interface.
 """
 from .fusion import Fusion, create_init_grid, fps, instance2onehot, onehot2instance  # noqa: F401
 from . import baked  # noqa: F401
-from .baked import BakedField, Components, Flow  # noqa: F401
+from .baked import BakedField, Components, Flow, PartMotions  # noqa: F401
 from . import consensus  # noqa: F401
 from .consensus import consensus_poses  # noqa: F401
 from . import corr_utils  # noqa: F401

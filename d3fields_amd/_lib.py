@@ -45,6 +45,9 @@ POOL_MAX_VOTE_CHANNELS = 256
 LINK_L2, LINK_COSINE, LINK_ARGMAX = 0, 1, 2
 LINK_TILE = (4, 4, 16)
 FLOW_MAX_RADIUS = 4
+MOTION_OK, MOTION_THINNED, MOTION_TOO_FEW = 0, 1, 2
+MOTION_MAX_FITS = 8
+MOTION_SUM_DOUBLES, MOTION_POSE_DOUBLES = 16, 15
 KERNEL_NAME_MAX = 80
 GAUSSIAN_MAX_RADIUS = 64
 DTYPE_F32 = 0
@@ -163,6 +166,9 @@ SIGNATURES = {
     "d3f_volume_links": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, ctypes.POINTER(VolumeSet), _i32, _f32, _i32, _vp, _vp]),
     "d3f_volume_flow": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(VolumeSet), _vp, _vp, ctypes.POINTER(VolumeSet), _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp,
                                        _vp]),
+    "d3f_part_motion_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32, _i64]),
+    "d3f_part_motion": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _f64, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                       _vp, _i64, _vp]),
     "d3f_volume_pool_workspace_bytes":(_i64, [_i32, _i32, _i32, _i32, _i64, _i64]),
     "d3f_volume_pool": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, ctypes.POINTER(VolumeSet), _i32, ctypes.POINTER(_i32), _i64, _vp, _vp, _vp,
                                        ctypes.POINTER(_vp), _vp, _i64, _vp]),

@@ -33,6 +33,10 @@ objects with different descriptors are separate; `links()` gives the link volume
 grid, within a window, whose stored row is closest (d3f_volume_flow, csrc/flow_kernels.hip) -- a `Flow` with the
 target, the cost, a sub-voxel offset, world displacements and the forward-backward test `consistent(back)`.
 
+`Flow.motions(parts, keep=)` answers "how did each part move?": one rigid motion per part from the flow's dense correspondences, by a
+trim-and-refit loop on the device (d3f_part_motion, csrc/motion_kernels.hip) -- a `PartMotions` with a rotation, a
+translation, an inlier count, an rmse and a verdict per part, and the residual and inlier volumes; the same bytes on every run.
+
 `BakedField.travel(goals, radius=)` answers "how do I get there, and how far is it along the way": the cost-to-go field of a goal set
 through the free voxels (d3f_volume_geodesic_*, csrc/geodesic_kernels.hip) -- exact shortest lattice paths with
 integer weights, as a new field whose `dist` is the travel distance and whose `next_voxel` names the voxel to step to; `path(starts)`
@@ -61,7 +65,7 @@ import torch
 
 from . import _lib
 
-__all__ = ["BakedField", "Components", "Flow"]
+__all__ = ["BakedField", "Components", "Flow", "PartMotions"]
 
 _RESERVED = ("dist", "valid_mask", "grid_shape")
 _POOL_KEYS = ("count", "moments", "centroid", "covariance")     # output keys of pool, next to one name + '_votes' per voted set
@@ -240,6 +244,145 @@ class Flow:
         own = _voxel_coords(torch.arange(self.target.numel(), device=self.target.device).view(self.grid_shape), self.grid_shape)
         near = ((_voxel_coords(torch.clamp(ret, min=0), self.grid_shape) - own).abs().amax(dim=-1) <= tol_voxels)
         return self.matched & (ret >= 0) & near
+
+    def motions(self, parts, keep=None, tau_voxels=1.0, fits=3, min_pairs=8, refined=True, count=None):
+        """How did each part move?  One rigid motion per part from this flow's matches, by a trim-and-refit loop (d3f_part_motion,
+        csrc/motion_kernels.hip) -> PartMotions.
+
+        parts       a Components on this flow's grid (components() / parts() of the field the flow starts from), or an int32 [nx, ny, nz] label
+                    volume on this device together with count=K, as pool takes it.  With a Components the moments are taken about each part's
+                    box_lo; with a label volume about voxel (0, 0, 0)
+        keep        None, or a bool [nx, ny, nz] volume: only these voxels are pairs -- typically consistent(back)
+        tau_voxels  the inlier radius in voxels: a pair is an inlier of a pose when its residual is <= tau_voxels
+        fits        1..8: fit 0 takes every pair, fit f the inliers under the pose of fit f-1
+        min_pairs   >= 3: a part with fewer pairs gets no pose (TOO_FEW); one that falls below it later keeps its last pose (THINNED)
+        refined     the match is target + offset (the flow must have been computed with refine=True); False: the target voxel alone
+        A pair is a voxel with a label in 1..K that `keep` passes and that has a target (and a finite offset).  Sums are float64 in a fixed
+        order: the same bytes on every run.  One host read (the member capacity).  Not differentiable."""
+        dev = self.target.device
+        nx, ny, nz = self.grid_shape
+        ref = None
+        if isinstance(parts, Components):
+            if count is not None:
+                raise ValueError("motions: count comes with a label tensor; a Components knows its own")
+            if tuple(parts.grid_shape) != tuple(self.grid_shape) or tuple(parts.origin) != self.origin or float(parts.step) != self.step:
+                raise ValueError("motions: the parts are of a grid %s at %s step %g, the flow of %s at %s step %g" % (
+                    tuple(parts.grid_shape), tuple(parts.origin), parts.step, tuple(self.grid_shape), self.origin, self.step))
+            labels, K, ref = parts.labels, parts.count, parts.box_lo
+        elif isinstance(parts, torch.Tensor):
+            if count is None or isinstance(count, bool) or not isinstance(count, int) or count < 0:
+                raise ValueError("motions: a label tensor needs count=K, an integer >= 0, got %r" % (count,))
+            if parts.dtype != torch.int32 or tuple(parts.shape) != tuple(self.grid_shape):
+                raise ValueError("motions: labels must be an int32 tensor of shape %s, got %s %s" % (tuple(self.grid_shape), parts.dtype, tuple(parts.shape)))
+            labels, K = parts.detach(), count
+        else:
+            raise ValueError("motions: parts must be a Components or an int32 label tensor, got %r" % type(parts).__name__)
+        if labels.device != dev:
+            raise ValueError("motions: the labels are on %s, this flow on %s" % (labels.device, dev))
+        if K > nx * ny * nz:
+            raise ValueError("motions: count = %d exceeds the %d voxels" % (K, nx * ny * nz))
+        if keep is not None:
+            if not isinstance(keep, torch.Tensor) or keep.dtype != torch.bool or tuple(keep.shape) != tuple(self.grid_shape):
+                raise ValueError("motions: keep must be a bool tensor of shape %s" % (tuple(self.grid_shape),))
+            if keep.device != dev:
+                raise ValueError("motions: keep is on %s, this flow on %s" % (keep.device, dev))
+        if isinstance(tau_voxels, bool) or not isinstance(tau_voxels, (int, float)) or not (0.0 < float(tau_voxels) < math.inf):
+            raise ValueError("motions: tau_voxels must be a finite number > 0, got %r" % (tau_voxels,))
+        if isinstance(fits, bool) or not isinstance(fits, int) or not 1 <= fits <= _lib.MOTION_MAX_FITS:
+            raise ValueError("motions: fits must be an integer in 1..%d, got %r" % (_lib.MOTION_MAX_FITS, fits))
+        if isinstance(min_pairs, bool) or not isinstance(min_pairs, int) or min_pairs < 3:
+            raise ValueError("motions: min_pairs must be an integer >= 3, got %r" % (min_pairs,))
+        if refined and self.offset is None:
+            raise ValueError("motions: this flow was computed with refine=False; pass refined=False")
+        if not dev.type == "cuda":
+            raise RuntimeError("motions: the flow must live on the ROCm device; there is no CPU path")
+        lib = _lib.load()
+        labels = labels.contiguous()
+        target = self.target.contiguous()
+        offset = self.offset.contiguous() if refined else None
+        keep8 = None if keep is None else keep.contiguous().view(torch.uint8)
+        ref = None if ref is None else ref.to(torch.int32).contiguous()
+        n = nx * ny * nz
+        tau2 = float(tau_voxels) * float(tau_voxels)
+        pose = torch.full((K, _lib.MOTION_POSE_DOUBLES), math.nan, dtype=torch.float64, device=dev)
+        pairs, inliers = torch.zeros(K, dtype=torch.int32, device=dev), torch.zeros(K, dtype=torch.int32, device=dev)
+        done = torch.zeros(K, dtype=torch.int32, device=dev)
+        status = torch.full((K,), _lib.MOTION_TOO_FEW, dtype=torch.int32, device=dev)
+        rmse = torch.full((K,), math.nan, dtype=torch.float64, device=dev)
+        res2 = torch.full((nx, ny, nz), math.nan, dtype=torch.float64, device=dev)
+        inlier = torch.zeros((nx, ny, nz), dtype=torch.uint8, device=dev)
+        if K > 0:                                                        # (no part: every output is empty, there is nothing to point at)
+            passes = (labels > 0) & (target >= 0)
+            capacity = int((passes if keep is None else passes & keep).sum())
+            members = torch.empty(1, dtype=torch.int64, device=dev)
+            ws_bytes = int(lib.d3f_part_motion_workspace_bytes(nx, ny, nz, K, capacity))
+            ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+            with torch.cuda.device(dev):
+                _lib.check(lib.d3f_part_motion(_lib.ptr(labels), K, nx, ny, nz, _lib.ptr(keep8), _lib.ptr(target), _lib.ptr(offset), _lib.ptr(ref), fits, tau2,
+                                               min_pairs, capacity, _lib.ptr(members), _lib.ptr(pairs), _lib.ptr(pose), _lib.ptr(inliers), _lib.ptr(rmse),
+                                               _lib.ptr(status), _lib.ptr(done), _lib.ptr(res2), _lib.ptr(inlier), None, _lib.ptr(ws), ws_bytes,
+                                               _lib.current_stream_handle(dev)))
+        return PartMotions(self.origin, self.step, pose, pairs, inliers, done, rmse, status, res2, inlier.view(torch.bool))
+
+
+class PartMotions:
+    """One rigid motion per part (Flow.motions).  Tensors only, on the flow's device; K parts, part k is row k - 1.
+
+    pose        float64 [K, 15] in voxel index units, as d3f_part_motion writes it: R row-major, src, dst with q = R (p - src) + dst; src is
+                the centroid of the part's final inlier sources, dst of their matches.  NaN for a part without a pose
+    rot, trans  float64 [K, 3, 3], [K, 3] in world coordinates: x' = rot x + trans, trans = (origin + step dst) - rot (origin + step src)
+    angle       float64 [K]: the rotation angle in radians;  shift float64 [K, 3]: the world displacement of the part's source centroid
+    pairs, inliers, fits   int32 [K]: the pairs, the inliers under the final pose, the fits done
+    rmse        float64 [K]: root mean square residual of the inliers in world units, NaN without inliers
+    status      int32 [K]: OK (0), THINNED (1: the inliers fell below min_pairs, the pose of the last fit stays), TOO_FEW (2: no pose)
+    residual    float64 [nx, ny, nz]: the distance between a pair's match and its part's motion of it, world units, NaN where there is no pair
+                or no pose;  inlier bool [nx, ny, nz]
+    Collinear or coincident pairs leave the rotation about their axis undetermined; the pose is then whatever the solver leaves, the same on
+    every run."""
+    OK, THINNED, TOO_FEW = _lib.MOTION_OK, _lib.MOTION_THINNED, _lib.MOTION_TOO_FEW
+
+    def __init__(self, origin, step, pose, pairs, inliers, fits, rmse_voxels, status, residual2_voxels, inlier):
+        self.origin, self.step = tuple(origin), float(step)
+        self.pose, self.pairs, self.inliers, self.fits, self.status, self.inlier = pose, pairs, inliers, fits, status, inlier
+        self.count = pose.shape[0]
+        self.grid_shape = torch.Size(inlier.shape)
+        o = torch.tensor(self.origin, dtype=torch.float64, device=pose.device)
+        self.rot = pose[:, 0:9].reshape(-1, 3, 3)
+        src, dst = o + self.step * pose[:, 9:12], o + self.step * pose[:, 12:15]
+        self.trans = dst - (self.rot @ src[:, :, None])[:, :, 0]
+        self.shift = dst - src
+        r = self.rot
+        skew = torch.stack((r[:, 2, 1] - r[:, 1, 2], r[:, 0, 2] - r[:, 2, 0], r[:, 1, 0] - r[:, 0, 1]), dim=-1)
+        self.angle = torch.atan2((skew * skew).sum(dim=-1).sqrt(), r[:, 0, 0] + r[:, 1, 1] + r[:, 2, 2] - 1.0)
+        self.rmse = rmse_voxels * self.step
+        self.residual = residual2_voxels.sqrt() * self.step
+
+    def apply(self, points, ids):
+        """float64 [N, 3]: world points moved by the poses of the parts `ids` (one label id in 1..K, or an integer tensor [N] of them); NaN
+        rows for a part without a pose"""
+        if not isinstance(points, torch.Tensor) or points.dtype != torch.float64 or points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError("PartMotions.apply: points must be a float64 [N, 3] tensor")
+        if points.device != self.pose.device:
+            raise ValueError("PartMotions.apply: points are on %s, the motions on %s" % (points.device, self.pose.device))
+        ids = torch.as_tensor(ids, device=points.device)
+        if ids.dtype not in (torch.int32, torch.int64) or ids.dim() > 1 or (ids.dim() == 1 and ids.shape[0] != points.shape[0]):
+            raise ValueError("PartMotions.apply: ids must be one integer or an integer tensor [N]")
+        ids = ids.long().expand(points.shape[0]) if ids.dim() == 0 else ids.long()
+        if ids.numel() and (int(ids.min()) < 1 or int(ids.max()) > self.count):
+            raise ValueError("PartMotions.apply: ids must lie in 1..%d" % self.count)
+        return (self.rot[ids - 1] @ points[:, :, None])[:, :, 0] + self.trans[ids - 1]
+
+    def moved(self, min_shift=None, min_angle=None):
+        """bool [K]: the parts that have a pose whose shift is at least min_shift (a world length) or whose angle is at least min_angle
+        (radians); a bound that is None does not count"""
+        if min_shift is None and min_angle is None:
+            raise ValueError("PartMotions.moved: give min_shift, min_angle or both")
+        out = torch.zeros(self.count, dtype=torch.bool, device=self.pose.device)
+        if min_shift is not None:
+            out |= self.shift.norm(dim=-1) >= float(min_shift)
+        if min_angle is not None:
+            out |= self.angle >= float(min_angle)
+        return out & (self.status != self.TOO_FEW)
 
 
 class BakedField:

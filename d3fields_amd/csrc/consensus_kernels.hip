@@ -32,6 +32,7 @@
 // consensus_select_kernel: ONE workgroup runs the rounds over the list: an arg-best over unique keys, then a compare pass.
 // pose_refit_kernel: one wave per pose; lane q re-scores point q, lane 0 runs Horn.
 // No float atomic, no scratch, nothing waits for another workgroup or polls memory.
+#include "d3f_horn.h"
 #include "d3f_internal.h"
 
 namespace d3f {
@@ -42,7 +43,8 @@ constexpr int kConsPasses = 8;
 constexpr int kConsTile = kConsPasses * kBlock;       // hypotheses per workgroup of the score kernel
 constexpr int kConsQueue = 2 * kBlock;                // the ring: fewer than 256 left over + at most 256 new
 constexpr int kSelectBlock = 1024;
-constexpr int kRefitSweeps = 12;
+constexpr int kRefitSweeps = kHornSweeps;
+static_assert(kRefitSweeps == 12, "the sweeps of the contract (tests/consensus_cases.py)");
 
 __device__ __forceinline__ double norm2(const double (&x)[3]) { return (x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]; }
 
@@ -430,53 +432,8 @@ __global__ __launch_bounds__(64) void pose_refit_kernel(const float *__restrict_
 #pragma unroll
                     for (int b = 0; b < 3; ++b) S[a][b] += ((double)p[a] - pm[a]) * ((double)c[b] - cm[b]);
             }
-            A[0][0] = (S[0][0] + S[1][1]) + S[2][2];
-            A[1][1] = (S[0][0] - S[1][1]) - S[2][2];
-            A[2][2] = (S[1][1] - S[0][0]) - S[2][2];
-            A[3][3] = (S[2][2] - S[0][0]) - S[1][1];
-            A[0][1] = A[1][0] = S[1][2] - S[2][1];
-            A[0][2] = A[2][0] = S[2][0] - S[0][2];
-            A[0][3] = A[3][0] = S[0][1] - S[1][0];
-            A[1][2] = A[2][1] = S[0][1] + S[1][0];
-            A[1][3] = A[3][1] = S[2][0] + S[0][2];
-            A[2][3] = A[3][2] = S[1][2] + S[2][1];
-            for (int i = 0; i < 4; ++i)
-                for (int j = 0; j < 4; ++j) V[i][j] = i == j ? 1.0 : 0.0;
-#pragma unroll 1
-            for (int sweep = 0; sweep < kRefitSweeps; ++sweep) {
-#pragma unroll 1
-                for (int i = 0; i < 3; ++i) {
-#pragma unroll 1
-                    for (int j = i + 1; j < 4; ++j) {
-                        const double apq = A[i][j];
-                        if (apq == 0.0) continue;
-                        const double theta = (A[j][j] - A[i][i]) / (2.0 * apq);
-                        const double t = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-                        A[i][i] -= t * apq;
-                        A[j][j] += t * apq;
-                        A[i][j] = A[j][i] = 0.0;
-                        for (int m = 0; m < 4; ++m) {
-                            if (m != i && m != j) {
-                                const double ami = A[m][i], amj = A[m][j];
-                                A[m][i] = A[i][m] = c * ami - s * amj;
-                                A[m][j] = A[j][m] = s * ami + c * amj;
-                            }
-                            const double vmi = V[m][i], vmj = V[m][j];
-                            V[m][i] = c * vmi - s * vmj;
-                            V[m][j] = s * vmi + c * vmj;
-                        }
-                    }
-                }
-            }
-            int top = 0;
-            for (int i = 1; i < 4; ++i)
-                if (A[i][i] > A[top][top]) top = i;
-            const double q0 = V[0][top], q1 = V[1][top], q2 = V[2][top], q3 = V[3][top];
-            const double a0 = q0 * q0, a1 = q1 * q1, a2 = q2 * q2, a3 = q3 * q3, n2 = ((a0 + a1) + a2) + a3;
-            const double R[3][3] = {{(((a0 + a1) - a2) - a3) / n2, (2.0 * (q1 * q2 - q0 * q3)) / n2, (2.0 * (q1 * q3 + q0 * q2)) / n2},
-                                    {(2.0 * (q1 * q2 + q0 * q3)) / n2, (((a0 - a1) + a2) - a3) / n2, (2.0 * (q2 * q3 - q0 * q1)) / n2},
-                                    {(2.0 * (q1 * q3 - q0 * q2)) / n2, (2.0 * (q2 * q3 + q0 * q1)) / n2, (((a0 - a1) - a2) + a3) / n2}};
+            double R[3][3];
+            horn_rotation<1>(S, &A[0][0], &V[0][0], R);       // d3f_horn.h: the block motion_fit_kernel shares
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
 #pragma unroll

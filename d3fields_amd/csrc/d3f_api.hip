@@ -1020,6 +1020,68 @@ int d3f_volume_pool(const int32_t *label, int32_t nx, int32_t ny, int32_t nz, in
     return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_pool launch");
 }
 
+// ---- one rigid motion per part from dense correspondences (motion_kernels.hip) ----
+int64_t d3f_part_motion_workspace_bytes(int32_t nx, int32_t ny, int32_t nz, int32_t K, int64_t member_capacity)
+{
+    if (K < 0 || member_capacity < 0 || !pool_shape_ok(nx, ny, nz, K)) return 0;
+    return d3f::motion_workspace_bytes((int64_t)nx * ny * nz, K, member_capacity);
+}
+
+int d3f_part_motion(const int32_t *label, int32_t K, int32_t nx, int32_t ny, int32_t nz, const uint8_t *keep, const int32_t *target, const double *offset,
+                    const int32_t *ref, int32_t fits, double tau2, int32_t min_pairs, int64_t member_capacity, int64_t *out_members, int32_t *out_pairs,
+                    double *out_pose, int32_t *out_inliers, double *out_rmse, int32_t *out_status, int32_t *out_fits, double *out_residual2, uint8_t *out_inlier,
+                    double *out_sums, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (!label || !target) return fail(D3F_ERR_INVALID_ARG, "part_motion: label or target is NULL");
+    if (!out_members || !out_pairs || !out_pose || !out_inliers || !out_rmse || !out_status || !out_fits)
+        return fail(D3F_ERR_INVALID_ARG, "part_motion: out_members, out_pairs, out_pose, out_inliers, out_rmse, out_status or out_fits is NULL");
+    if (K < 0) return fail(D3F_ERR_INVALID_ARG, "part_motion: K=%d is negative", K);
+    if (fits < 1 || fits > D3F_MOTION_MAX_FITS) return fail(D3F_ERR_INVALID_ARG, "part_motion: fits=%d outside [1,%d]", fits, D3F_MOTION_MAX_FITS);
+    if (!(tau2 > 0.0 && tau2 < __builtin_huge_val())) return fail(D3F_ERR_INVALID_ARG, "part_motion: tau2=%g, the squared inlier radius must be finite and > 0", tau2);
+    if (min_pairs < 3) return fail(D3F_ERR_INVALID_ARG, "part_motion: min_pairs=%d, a rigid motion needs at least 3 pairs", min_pairs);
+    if (member_capacity < 0) return fail(D3F_ERR_INVALID_ARG, "part_motion: member_capacity=%lld is negative", (long long)member_capacity);
+    if (!edt_shape_ok(nx, ny, nz))
+        return fail(D3F_ERR_BAD_SHAPE, "part_motion: nx=%d ny=%d nz=%d, every extent must be in [1, %d] and the volume at most 2^31 - 1 voxels", nx, ny, nz,
+                    D3F_EDT_MAX_EXTENT);
+    if (!pool_shape_ok(nx, ny, nz, K)) return fail(D3F_ERR_BAD_SHAPE, "part_motion: K=%d exceeds the %lld voxels", K, (long long)nx * ny * nz);
+    if (!aligned(label, 4) || !aligned(target, 4) || !aligned(offset, 8) || !aligned(ref, 4) || !aligned(out_members, 8) || !aligned(out_pairs, 4) ||
+        !aligned(out_pose, 8) || !aligned(out_inliers, 4) || !aligned(out_rmse, 8) || !aligned(out_status, 4) || !aligned(out_fits, 4) ||
+        !aligned(out_residual2, 8) || !aligned(out_sums, 8))
+        return fail(D3F_ERR_BAD_LAYOUT, "part_motion: every pointer must be aligned to its element size");
+    const int64_t need = d3f_part_motion_workspace_bytes(nx, ny, nz, K, member_capacity);
+    if (!workspace || workspace_bytes < need) return fail(D3F_ERR_WORKSPACE, "part_motion: needs %lld workspace bytes", (long long)need);
+    if (!aligned(workspace, 8)) return fail(D3F_ERR_BAD_LAYOUT, "part_motion: workspace must be 8-byte aligned");
+    hipError_t e;
+    if (K == 0) {
+        e = d3f::launch_pool_nothing(out_members, static_cast<hipStream_t>(stream));
+    } else {
+        d3f::MotionArgs A;
+        A.label = label;
+        A.K = K; A.nx = nx; A.ny = ny; A.nz = nz;
+        A.keep = keep;
+        A.target = target;
+        A.offset = offset;
+        A.ref = ref;
+        A.fits = fits;
+        A.min_pairs = min_pairs;
+        A.tau2 = tau2;
+        A.member_capacity = member_capacity;
+        A.out_members = out_members;
+        A.out_pairs = out_pairs;
+        A.out_pose = out_pose;
+        A.out_inliers = out_inliers;
+        A.out_rmse = out_rmse;
+        A.out_status = out_status;
+        A.out_fits = out_fits;
+        A.out_residual2 = out_residual2;
+        A.out_inlier = out_inlier;
+        A.out_sums = out_sums;
+        A.workspace = workspace;
+        e = d3f::launch_part_motion(A, static_cast<hipStream_t>(stream));
+    }
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "part_motion launch");
+}
+
 // ---- cost-to-go through free space (geodesic_kernels.hip) ----
 static const char *geo_weights_bad(int32_t connectivity, const int32_t *w)
 {

@@ -281,6 +281,61 @@ int64_t pool_workspace_bytes(int64_t n, int64_t K, int64_t cap, int64_t mean_cha
 int pool_levels(int64_t cap);                                       // fold levels a member capacity needs: 1..4
 hipError_t launch_volume_pool(const PoolArgs &A, hipStream_t s);
 hipError_t launch_pool_nothing(int64_t *out_members, hipStream_t s);   // K == 0: out_members = 0
+// The label-sorted member list on its own (motion_kernels.hip folds float64 rows over it).
+// The arrays the scans turn into offsets, K + 1 entries each (the last one 0, so that entry K of a scan is the total):
+//   first[k]      count_k: where the component's members start in the sorted list
+//   work[l][k]    the chunks component k folds at level l: ceil(count / 256^(l+1)) while it still has more than one row there (any at l = 0)
+//   part[l][k]    the partial rows it writes at level l: the same number where that is more than one
+struct PoolPlan {
+    uint32_t *first;
+    uint32_t *work[4];
+    uint32_t *part[3];
+};
+// what the workspace holds, in this order (every piece padded to 256 bytes); pitch: the 4-byte words of a partial row
+struct PoolLayout {
+    int64_t flag, flag_scan, keys[2], vals[2], counters, counters_scan, plan, plan_scan, rows[2], total;
+    int64_t waves_total, rows_a, rows_b;
+};
+PoolLayout pool_layout(int64_t n, int64_t K, int64_t cap, int64_t pitch);
+struct PoolList {
+    const uint32_t *vals;        // the members' flat indices grouped by label, ascending inside a label; valid where *out_members <= cap
+    PoolPlan plan;               // scanned
+    int levels;                  // 0 with cap == 0
+};
+// out_count is zeroed and counted, out_members written, the list sorted and the plan scanned: everything of launch_volume_pool before its folds.
+// cap = min(member_capacity, n); workspace laid out by L = pool_layout(n, K, cap, pitch).
+hipError_t launch_pool_members(const int32_t *label, const uint8_t *valid, const int32_t *slot, int64_t n, int K, int64_t cap, int64_t *out_members,
+                               int32_t *out_count, void *workspace, const PoolLayout &L, PoolList *list, hipStream_t s);
+inline int64_t pool_level_chunks(int64_t cap, int K, int l)   // an upper bound of the chunks folded at level l
+{
+    // capacity / 256^(l+1) plus one ragged chunk per component that takes part (every non-empty one at level 0, those with more than 256^l members later)
+    return l == 0 ? (cap >> 8) + (K < cap ? K : cap) : (cap >> (8 * l + 8)) + (cap >> (8 * l)) + 1;
+}
+
+// motion_kernels.hip: one rigid motion per part from dense correspondences
+struct MotionArgs {
+    const int32_t *label;
+    int32_t K, nx, ny, nz;
+    const uint8_t *keep;         // or nullptr
+    const int32_t *target;
+    const double *offset;        // or nullptr
+    const int32_t *ref;          // or nullptr
+    int32_t fits, min_pairs;
+    double tau2;
+    int64_t member_capacity;
+    int64_t *out_members;
+    int32_t *out_pairs;
+    double *out_pose;
+    int32_t *out_inliers;
+    double *out_rmse;
+    int32_t *out_status, *out_fits;
+    double *out_residual2;       // or nullptr
+    uint8_t *out_inlier;         // or nullptr
+    double *out_sums;            // or nullptr
+    void *workspace;
+};
+int64_t motion_workspace_bytes(int64_t n, int64_t K, int64_t cap);
+hipError_t launch_part_motion(const MotionArgs &A, hipStream_t s);
 
 // geodesic_kernels.hip: cost-to-go through free space, exact shortest paths on the lattice; w: host int32[3]
 int64_t geodesic_workspace_bytes(int nx, int ny, int nz);

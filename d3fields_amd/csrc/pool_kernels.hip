@@ -183,16 +183,6 @@ __global__ __launch_bounds__(kBlock) void pool_sort_scatter_kernel(const uint32_
     }
 }
 
-// The arrays the scans turn into offsets, K + 1 entries each (the last one 0, so that entry K of a scan is the total):
-//   first[k]      count_k: where the component's members start in the sorted list
-//   work[l][k]    the chunks component k folds at level l: ceil(count / 256^(l+1)) while it still has more than one row there (any at l = 0)
-//   part[l][k]    the partial rows it writes at level l: the same number where that is more than one
-struct PoolPlan {
-    uint32_t *first;
-    uint32_t *work[4];
-    uint32_t *part[3];
-};
-
 __global__ __launch_bounds__(kBlock) void pool_prep_kernel(const int32_t *__restrict__ count, const int64_t *__restrict__ members, int64_t cap, int K, int levels, PoolPlan A)
 {
     const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -456,13 +446,7 @@ int pool_levels(int64_t cap)
     return levels;
 }
 
-// what the workspace holds, in this order (every piece padded to 256 bytes)
-struct PoolLayout {
-    int64_t flag, flag_scan, keys[2], vals[2], counters, counters_scan, plan, plan_scan, rows[2], total;
-    int64_t waves_total, rows_a, rows_b;
-};
-
-static PoolLayout pool_layout(int64_t n, int64_t K, int64_t cap, int64_t pitch)
+PoolLayout pool_layout(int64_t n, int64_t K, int64_t cap, int64_t pitch)
 {
     PoolLayout L;
     int64_t at = 0;
@@ -497,6 +481,72 @@ int64_t pool_workspace_bytes(int64_t n, int64_t K, int64_t cap, int64_t mean_cha
     return pool_layout(n, K, cap, mean_channels > 0 ? mean_channels + 3 * D3F_MAX_MAPS : 0).total;
 }
 
+// Everything before the folds: the zeroed counts, flags and counts, ranks, the list in flat order, the stable sort by label, the plan and its scans.
+hipError_t launch_pool_members(const int32_t *label, const uint8_t *valid, const int32_t *slot, int64_t n, int K, int64_t cap, int64_t *out_members,
+                               int32_t *out_count, void *workspace, const PoolLayout &L, PoolList *list, hipStream_t s)
+{
+    const dim3 block(kBlock);
+    unsigned char *ws = static_cast<unsigned char *>(workspace);
+    uint32_t *flag = reinterpret_cast<uint32_t *>(ws + L.flag);
+    uint32_t *keys[2] = {reinterpret_cast<uint32_t *>(ws + L.keys[0]), reinterpret_cast<uint32_t *>(ws + L.keys[1])};
+    uint32_t *vals[2] = {reinterpret_cast<uint32_t *>(ws + L.vals[0]), reinterpret_cast<uint32_t *>(ws + L.vals[1])};
+    uint32_t *counters = reinterpret_cast<uint32_t *>(ws + L.counters);
+
+    hipLaunchKernelGGL(pool_zero_kernel, dim3(pool_grid(K)), block, 0, s, reinterpret_cast<uint32_t *>(out_count), (int64_t)K);
+
+    // members: flags and counts, ranks, the list in flat order
+    const int iters = (int)std::min<int64_t>(64, (n + kPoolFlagSpan - 1) / kPoolFlagSpan);
+    const int64_t span = (int64_t)kBlock * iters;
+    const dim3 grid_n((unsigned)((n + kBlock - 1) / kBlock));
+    hipLaunchKernelGGL(pool_flag_kernel, dim3((unsigned)((n + span - 1) / span)), block, 0, s, label, valid, slot, flag, out_count, K, iters, n);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    e = launch_exclusive_scan_u32(flag, flag, n, ws + L.flag_scan, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(pool_compact_kernel, grid_n, block, 0, s, label, valid, slot, flag, keys[0], vals[0], out_members, K, cap, n);
+
+    // the list grouped by label: a stable sort, least significant digit first
+    int sorted = 0;
+    if (cap > 0) {
+        const int passes = K < 256 ? 1 : K < 65536 ? 2 : K < (1 << 24) ? 3 : 4;
+        const dim3 grid_sort((unsigned)(L.waves_total / 4));
+        for (int p = 0; p < passes; ++p) {
+            hipLaunchKernelGGL(pool_sort_count_kernel, grid_sort, block, 0, s, keys[sorted], counters, out_members, cap, 8 * p, L.waves_total);
+            e = hipGetLastError();
+            if (e != hipSuccess) return e;
+            e = launch_exclusive_scan_u32(counters, counters, 256 * L.waves_total, ws + L.counters_scan, s);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL(pool_sort_scatter_kernel, grid_sort, block, 0, s, keys[sorted], vals[sorted], keys[sorted ^ 1], vals[sorted ^ 1], counters, out_members,
+                               cap, 8 * p, L.waves_total);
+            sorted ^= 1;
+        }
+    }
+
+    // where every component's members, chunks and partial rows start
+    const int levels = cap > 0 ? pool_levels(cap) : 0;
+    const int64_t plan_pitch = pool_pad(4 * ((int64_t)K + 1));
+    PoolPlan plan;
+    plan.first = reinterpret_cast<uint32_t *>(ws + L.plan);
+    for (int l = 0; l < 4; ++l) plan.work[l] = reinterpret_cast<uint32_t *>(ws + L.plan + (1 + l) * plan_pitch);
+    for (int l = 0; l < 3; ++l) plan.part[l] = reinterpret_cast<uint32_t *>(ws + L.plan + (5 + l) * plan_pitch);
+    hipLaunchKernelGGL(pool_prep_kernel, dim3((unsigned)(((int64_t)K + 1 + kBlock - 1) / kBlock)), block, 0, s, out_count, out_members, cap, K, levels, plan);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (levels > 0) {
+        e = launch_exclusive_scan_u32(plan.first, plan.first, (int64_t)K + 1, ws + L.plan_scan, s);
+        for (int l = 0; l < levels && e == hipSuccess; ++l) {
+            e = launch_exclusive_scan_u32(plan.work[l], plan.work[l], (int64_t)K + 1, ws + L.plan_scan, s);
+            if (e == hipSuccess && l + 1 < levels) e = launch_exclusive_scan_u32(plan.part[l], plan.part[l], (int64_t)K + 1, ws + L.plan_scan, s);
+        }
+        if (e != hipSuccess) return e;
+    }
+
+    list->vals = vals[sorted];
+    list->plan = plan;
+    list->levels = levels;
+    return hipGetLastError();
+}
+
 hipError_t launch_volume_pool(const PoolArgs &A, hipStream_t s)
 {
     const int64_t n = (int64_t)A.nx * A.ny * A.nz;
@@ -520,70 +570,24 @@ hipError_t launch_volume_pool(const PoolArgs &A, hipStream_t s)
     }
     const PoolLayout L = pool_layout(n, K, cap, pitch);
     unsigned char *ws = static_cast<unsigned char *>(A.workspace);
-    uint32_t *flag = reinterpret_cast<uint32_t *>(ws + L.flag);
-    uint32_t *keys[2] = {reinterpret_cast<uint32_t *>(ws + L.keys[0]), reinterpret_cast<uint32_t *>(ws + L.keys[1])};
-    uint32_t *vals[2] = {reinterpret_cast<uint32_t *>(ws + L.vals[0]), reinterpret_cast<uint32_t *>(ws + L.vals[1])};
-    uint32_t *counters = reinterpret_cast<uint32_t *>(ws + L.counters);
 
-    // the zeroed integer outputs
-    hipLaunchKernelGGL(pool_zero_kernel, dim3(pool_grid(K)), block, 0, s, reinterpret_cast<uint32_t *>(A.out_count), (int64_t)K);
+    // the zeroed integer outputs (out_count: launch_pool_members)
     if (A.out_moments) hipLaunchKernelGGL(pool_zero_kernel, dim3(pool_grid((int64_t)K * 18)), block, 0, s, reinterpret_cast<uint32_t *>(A.out_moments), (int64_t)K * 18);
     for (int i = 0; i < A.n_sets; ++i)
         if (P.sets[i].mode == D3F_POOL_VOTES)
             hipLaunchKernelGGL(pool_zero_kernel, dim3(pool_grid((int64_t)K * P.sets[i].C)), block, 0, s, static_cast<uint32_t *>(P.sets[i].out), (int64_t)K * P.sets[i].C);
 
-    // members: flags and counts, ranks, the list in flat order
-    const int iters = (int)std::min<int64_t>(64, (n + kPoolFlagSpan - 1) / kPoolFlagSpan);
-    const int64_t span = (int64_t)kBlock * iters;
-    const dim3 grid_n((unsigned)((n + kBlock - 1) / kBlock));
-    hipLaunchKernelGGL(pool_flag_kernel, dim3((unsigned)((n + span - 1) / span)), block, 0, s, A.label, A.valid, A.slot, flag, A.out_count, K, iters, n);
-    hipError_t e = hipGetLastError();
+    PoolList list;
+    hipError_t e = launch_pool_members(A.label, A.valid, A.slot, n, K, cap, A.out_members, A.out_count, A.workspace, L, &list, s);
     if (e != hipSuccess) return e;
-    e = launch_exclusive_scan_u32(flag, flag, n, ws + L.flag_scan, s);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(pool_compact_kernel, grid_n, block, 0, s, A.label, A.valid, A.slot, flag, keys[0], vals[0], A.out_members, K, cap, n);
-
-    // the list grouped by label: a stable sort, least significant digit first
-    int sorted = 0;
-    if (cap > 0) {
-        const int passes = K < 256 ? 1 : K < 65536 ? 2 : K < (1 << 24) ? 3 : 4;
-        const dim3 grid_sort((unsigned)(L.waves_total / 4));
-        for (int p = 0; p < passes; ++p) {
-            hipLaunchKernelGGL(pool_sort_count_kernel, grid_sort, block, 0, s, keys[sorted], counters, A.out_members, cap, 8 * p, L.waves_total);
-            e = hipGetLastError();
-            if (e != hipSuccess) return e;
-            e = launch_exclusive_scan_u32(counters, counters, 256 * L.waves_total, ws + L.counters_scan, s);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(pool_sort_scatter_kernel, grid_sort, block, 0, s, keys[sorted], vals[sorted], keys[sorted ^ 1], vals[sorted ^ 1], counters, A.out_members,
-                               cap, 8 * p, L.waves_total);
-            sorted ^= 1;
-        }
-    }
-
-    // where every component's members, chunks and partial rows start
-    const int levels = cap > 0 ? pool_levels(cap) : 0;
-    const int64_t plan_pitch = pool_pad(4 * ((int64_t)K + 1));
-    PoolPlan plan;
-    plan.first = reinterpret_cast<uint32_t *>(ws + L.plan);
-    for (int l = 0; l < 4; ++l) plan.work[l] = reinterpret_cast<uint32_t *>(ws + L.plan + (1 + l) * plan_pitch);
-    for (int l = 0; l < 3; ++l) plan.part[l] = reinterpret_cast<uint32_t *>(ws + L.plan + (5 + l) * plan_pitch);
-    hipLaunchKernelGGL(pool_prep_kernel, dim3((unsigned)(((int64_t)K + 1 + kBlock - 1) / kBlock)), block, 0, s, A.out_count, A.out_members, cap, K, levels, plan);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    if (levels > 0) {
-        e = launch_exclusive_scan_u32(plan.first, plan.first, (int64_t)K + 1, ws + L.plan_scan, s);
-        for (int l = 0; l < levels && e == hipSuccess; ++l) {
-            e = launch_exclusive_scan_u32(plan.work[l], plan.work[l], (int64_t)K + 1, ws + L.plan_scan, s);
-            if (e == hipSuccess && l + 1 < levels) e = launch_exclusive_scan_u32(plan.part[l], plan.part[l], (int64_t)K + 1, ws + L.plan_scan, s);
-        }
-        if (e != hipSuccess) return e;
-    }
+    const int levels = list.levels;
+    const PoolPlan &plan = list.plan;
 
     // the folds
     P.count = A.out_count;
     P.members = A.out_members;
     P.cap = cap;
-    P.vals = vals[sorted];
+    P.vals = list.vals;
     P.slot = A.slot;
     P.first = plan.first;
     P.moments = A.out_moments;
@@ -601,9 +605,7 @@ hipError_t launch_volume_pool(const PoolArgs &A, hipStream_t s)
         P.part_out = l + 1 < levels ? plan.part[l] : nullptr;
         P.rows_in = l > 0 ? rows[(l - 1) & 1] : nullptr;
         P.rows_out = rows[l & 1];
-        // chunks: capacity / 256^(l+1) plus one ragged chunk per component that takes part (every non-empty one at level 0, those with more
-        // than 256^l members later)
-        const int64_t chunks = l == 0 ? (cap >> 8) + std::min<int64_t>(K, cap) : (cap >> (8 * l + 8)) + (cap >> (8 * l)) + 1;
+        const int64_t chunks = pool_level_chunks(cap, K, l);
         const dim3 grid((unsigned)((chunks + 3) / 4));
         if (l == 0)
             hipLaunchKernelGGL(pool_level_kernel<true>, grid, block, 0, s, P);

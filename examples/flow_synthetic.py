@@ -5,11 +5,16 @@
                                            surface point in the object's own frame), so they move with the object
     a.flow(b, 'feat', radius_voxels=3)     for every occupied voxel of the first bake the voxel of the second with the closest row
     b.flow(a, ...), consistent(back)       the forward-backward test drops matches the way back does not confirm
-    parts('mask', rule='argmax')           the parts of the first bake; the median displacement of each part's consistent voxels
+    parts('mask', rule='argmax')           the parts of the first bake
+    fwd.motions(parts, keep=consistent)    one rigid motion per part from its consistent matches, by a trim-and-refit loop on the device: the
+                                           rotation angle, the shift, the inliers among the pairs and their rmse
 
-    python examples/flow_synthetic.py [--step 0.004] [--band 0.008] [--move 2,-1,0]
+    python examples/flow_synthetic.py [--step 0.004] [--band 0.008] [--move 2,-1,0] [--turn 10]
+
+--turn DEG also turns the moved sphere, and with it its painted code, about its own vertical axis.
 """
 import argparse
+import math
 import os
 import sys
 
@@ -23,8 +28,9 @@ NAMES = ["table"] + ["%s %d" % (n, i) for i, n in enumerate(synth._SPHERE_NAMES)
 C = 32
 
 
-def observe(spheres, K, Rt, H, W, proto, dev):
-    """one observation of the scene with these spheres -> a Fusion holding depth, a one-hot mask and the painted descriptors"""
+def observe(spheres, K, Rt, H, W, proto, dev, turn=0.0):
+    """one observation of the scene with these spheres -> a Fusion holding depth, a one-hot mask and the painted descriptors; sphere 1 is
+    turned by `turn` radians about the vertical through its centre (its shape stays, its painted code turns with it)"""
     V = K.shape[0]
     depth = synth.raycast_depth(K, Rt, H, W, spheres)
     labels = synth.sphere_label_images(K, Rt, depth, spheres)
@@ -37,6 +43,11 @@ def observe(spheres, K, Rt, H, W, proto, dev):
         d = depth[v].astype(np.float64)
         cam = np.stack([(uu - Kv[0, 2]) / Kv[0, 0] * d, (vv - Kv[1, 2]) / Kv[1, 1] * d, d], -1)
         local = (cam - t) @ R - centres[labels[v]]                             # the surface point in its object's frame
+        if turn != 0.0:
+            c, sn = math.cos(turn), math.sin(turn)
+            Rz = np.array([[c, -sn, 0.0], [sn, c, 0.0], [0.0, 0.0, 1.0]])
+            on = labels[v] == 2
+            local[on] = local[on] @ Rz                                         # Rz^T (p - centre): where the point was before the turn
         phase = local[..., None, :] * freqs[:, None]                           # [H, W, 4, 3]
         code = np.concatenate([np.sin(phase), np.cos(phase)], -1).reshape(H, W, 24)
         feat[v] = np.concatenate([proto[labels[v]], 0.5 * code], -1)
@@ -53,6 +64,7 @@ def main():
     ap.add_argument("--step", type=float, default=0.004)
     ap.add_argument("--band", type=float, default=None, help="bake channel rows only within this distance (m) of the surface, e.g. 0.008")
     ap.add_argument("--move", default="2,-1,0", help="how far sphere 1 moves between the observations, in voxels")
+    ap.add_argument("--turn", type=float, default=0.0, help="degrees sphere 1 also turns about its own vertical axis")
     ap.add_argument("--radius", type=int, default=3)
     ap.add_argument("--min-voxels", type=int, default=30)
     args = ap.parse_args()
@@ -65,7 +77,7 @@ def main():
     after = list(before)
     after[1] = tuple(c + m * args.step for c, m in zip(before[1][:3], move)) + (before[1][3],)
     a = observe(before, K, Rt, H, W, proto, dev).bake(synth.WORK_BOX, args.step, return_names=["mask", "feat"], band=args.band)
-    b = observe(after, K, Rt, H, W, proto, dev).bake(synth.WORK_BOX, args.step, return_names=["mask", "feat"], band=args.band)
+    b = observe(after, K, Rt, H, W, proto, dev, turn=math.radians(args.turn)).bake(synth.WORK_BOX, args.step, return_names=["mask", "feat"], band=args.band)
     iso = args.step                                                           # a shell one step thick round the observed surfaces
     fwd = a.flow(b, "feat", radius_voxels=args.radius, iso=iso)
     back = b.flow(a, "feat", radius_voxels=args.radius, iso=iso)
@@ -76,12 +88,13 @@ def main():
           % (tuple(a.grid_shape), args.step, NAMES[2], tuple(move), m, 100.0 * int(fwd.matched.sum()) / m, 100.0 * int(ok.sum()) / m))
     parts = a.parts("mask", rule="argmax", iso=iso, min_voxels=args.min_voxels)
     votes = a.pool(parts, return_names=[], votes=["mask"])["mask_votes"]
-    disp = fwd.displacement() / args.step                                     # in voxels, refined
+    pm = fwd.motions(parts, keep=ok)                                          # one call: every part's rigid motion from its consistent matches
+    verdict = {pm.OK: "ok", pm.THINNED: "thinned", pm.TOO_FEW: "too few"}
     for k in parts.largest(8).tolist():
-        sel = (parts.labels == k) & ok
-        med = disp[sel].median(dim=0).values.tolist() if bool(sel.any()) else [float("nan")] * 3
-        print("    part %3d ('%s'): %6d voxels, %6d consistent, median displacement (%+.2f, %+.2f, %+.2f) voxels"
-              % (k, NAMES[int(votes[k - 1].argmax())], int(parts.sizes[k - 1]), int(sel.sum()), med[0], med[1], med[2]))
+        sh = (pm.shift[k - 1] / args.step).tolist()
+        print("    part %3d ('%s'): %6d voxels, %6d consistent, turned %5.2f deg, shift (%+.2f, %+.2f, %+.2f) voxels, %d / %d inliers, rmse %.3f voxels, %s"
+              % (k, NAMES[int(votes[k - 1].argmax())], int(parts.sizes[k - 1]), int(pm.pairs[k - 1]), math.degrees(float(pm.angle[k - 1])), sh[0], sh[1], sh[2],
+                 int(pm.inliers[k - 1]), int(pm.pairs[k - 1]), float(pm.rmse[k - 1]) / args.step, verdict[int(pm.status[k - 1])]))
 
 
 if __name__ == "__main__":

@@ -880,6 +880,62 @@ int d3f_volume_flow(const uint8_t *site_a, const int32_t *slot_a, const d3f_volu
                     const d3f_volume_set *set_b, int32_t nx, int32_t ny, int32_t nz, int32_t radius, float max_cost2, int32_t *out_target, float *out_cost,
                     float *out_axis_cost, void *stream);
 
+/* (still ABI 16: symbols added -- two entry points and their constants; no struct or earlier entry point changes and D3F_ABI_VERSION stays 16; a
+ * client detects the feature by the symbols.)  How did each part move?  One rigid motion per part from the dense correspondences of a flow, with
+ * a trim-and-refit loop and the verdict per voxel (csrc/motion_kernels.hip).
+ *   volume       nx x ny x nz, z fastest, flat index v = (x*ny + y)*nz + z, n voxels; extents in [1, D3F_EDT_MAX_EXTENT], n <= 2^31 - 1;
+ *   label        int32 [nx,ny,nz] as d3f_volume_components writes it, K >= 0 parts;  keep: NULL (every voxel) or one byte per voxel;
+ *   target       int32 [nx,ny,nz] as d3f_volume_flow writes it;  offset: NULL (zeros) or float64 [n,3], the sub-voxel correction in voxels;
+ *   ref          NULL (zeros) or int32 [K,3]: an integer reference corner per part (the lower corner of its box), which keeps the moments small.
+ * PAIR: voxel v is a pair of part k when label[v] == k with 1 <= k <= K, keep is NULL or keep[v] != 0, 0 <= target[v] < n and, with offset
+ * given, its three components at v are finite.  Any other label or target indexes nothing.  In voxel units relative to ref_k:
+ *   a = (x,y,z)(v) - ref_k (exact integers held as float64);  b = ((x,y,z)(target[v]) - ref_k) + offset[v]: the integer difference first, then
+ *   one float64 add per axis (none with offset NULL).
+ * MOMENTS: a member's row is the D3F_MOTION_SUM_DOUBLES = 16 float64 {1, a0,a1,a2, b0,b1,b2, a_i*b_j (i major, 9)}; a member that is no inlier
+ * of the current fit contributes a row of +0.0.  The rows of a part are folded in ascending flat index in chunks of D3F_POOL_CHUNK = 256
+ * consecutive members of that part with a ragged last chunk, and the next level folds the part's partial rows in chunk order, 256 at a time
+ * (the chunk and level structure of d3f_volume_pool).  Inside a chunk: pad to 256 rows with +0.0; lane l of 64 holds
+ * (((0.0 + m_l) + m_{l+64}) + m_{l+128}) + m_{l+192}; then for s = 32, 16, 8, 4, 2, 1: v[l] = v[l] + v[l+s] for l < s; v[0] is the fold.  Every +
+ * is one IEEE float64 add, the 16 columns are independent, nothing is fused.  A part without pairs has a row of +0.0.
+ * FIT (float64): with n and the sums A, B, M of the row: pm = A / n, cm = B / n, S_ij = M_ij - (A_i * B_j) / n; then Horn's closed form exactly as
+ * d3f_pose_refit does it: the symmetric 4 x 4 matrix of S, 12 cyclic Jacobi sweeps that skip zero entries, the first largest diagonal entry,
+ * R = the quaternion's matrix / |q|^2.  The pose row is D3F_MOTION_POSE_DOUBLES = 15 float64: R row-major, src = ref + pm, dst = ref + cm, and
+ * means q = R (p - src) + dst in voxel index units.
+ * RESIDUAL of a pair: u = a - pm, w = b - cm, e_i = ((R_i0 u0 + R_i1 u1) + R_i2 u2) - w_i, r2 = (e0 e0 + e1 e1) + e2 e2.  It is an inlier when
+ * r2 <= tau2 (a NaN compares false).
+ * LOOP, fits in 1..D3F_MOTION_MAX_FITS: fit 0 uses every pair, fit f >= 1 the inliers under the pose of fit f-1.  A part with fewer than min_pairs
+ * (>= 3) pairs at fit 0: a NaN pose row, D3F_MOTION_TOO_FEW, out_fits 0.  A part whose inliers fall below min_pairs at a later fit keeps the pose of
+ * its last fit: D3F_MOTION_THINNED, out_fits the number of fits done.  Else D3F_MOTION_OK, out_fits = fits.
+ * Always written: out_members ONE device int64, the total pair count; out_pairs int32 [K].  Written when out_members <= member_capacity:
+ *   out_pose [K,15], out_status, out_fits [K];  under the final pose: out_residual2 float64 [n] (may be NULL; NaN where v is no pair or its part
+ *   has no pose), out_inlier uint8 [n] (may be NULL), out_inliers int32 [K], out_rmse float64 [K] = sqrt(fold(r2 of the final inliers, +0.0 for
+ *   the others) / inliers) by the same tree, NaN without inliers;  out_sums (may be NULL; for tests) float64 [K,16]: the sums of the LAST fold a
+ *   part took part in (the fold that thinned it, for a thinned part).
+ * Over capacity (out_members > member_capacity): only out_members and out_pairs are defined, the status is D3F_OK, the caller runs again with
+ * room (the protocol of d3f_volume_pool).  K == 0: D3F_OK, only out_members = 0 is written.
+ * Collinear or coincident pairs leave the rotation about their axis undetermined; the pose is then still a deterministic function of the input
+ * (whatever the Jacobi sweeps leave).  It is not detected.
+ * The member list is built once by d3f_volume_pool's flag, scan, compaction and stable label sort on "label where pair, else 0"; one wave folds one
+ * chunk; the whole loop is enqueued on the caller's stream, as many fold levels per fit as member_capacity allows; a part whose loop has ended
+ * takes no further part.  No allocation, no synchronisation, no float atomic, nothing waits for another workgroup; two runs give identical bytes.
+ * workspace: d3f_part_motion_workspace_bytes(nx, ny, nz, K, member_capacity), 8-byte aligned, contents irrelevant; the function returns 0 exactly
+ * for arguments d3f_part_motion rejects.
+ * Status errors, nothing launched: NULL label / target / out_members / out_pairs / out_pose / out_inliers / out_rmse / out_status / out_fits, K < 0,
+ * fits outside 1..8, tau2 not finite or <= 0, min_pairs < 3, member_capacity < 0 (D3F_ERR_INVALID_ARG); an extent outside
+ * [1, D3F_EDT_MAX_EXTENT], more than 2^31 - 1 voxels, K above the voxel count (D3F_ERR_BAD_SHAPE); a pointer not aligned to its element
+ * (D3F_ERR_BAD_LAYOUT); the workspace NULL or short (D3F_ERR_WORKSPACE). */
+#define D3F_MOTION_OK 0
+#define D3F_MOTION_THINNED 1
+#define D3F_MOTION_TOO_FEW 2
+#define D3F_MOTION_MAX_FITS 8
+#define D3F_MOTION_SUM_DOUBLES 16
+#define D3F_MOTION_POSE_DOUBLES 15
+int64_t d3f_part_motion_workspace_bytes(int32_t nx, int32_t ny, int32_t nz, int32_t K, int64_t member_capacity);
+int d3f_part_motion(const int32_t *label, int32_t K, int32_t nx, int32_t ny, int32_t nz, const uint8_t *keep, const int32_t *target, const double *offset,
+                    const int32_t *ref, int32_t fits, double tau2, int32_t min_pairs, int64_t member_capacity, int64_t *out_members, int32_t *out_pairs,
+                    double *out_pose, int32_t *out_inliers, double *out_rmse, int32_t *out_status, int32_t *out_fits, double *out_residual2,
+                    uint8_t *out_inlier, double *out_sums, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* (ABI 12) The first surface a ray meets in a baked volume: a fixed-step march through `dist` with one linear interpolation at the
  * sign change.  Everything in fp32.  Ray i is p(t) = o + t*d; d need not be unit.
  *   once per ray: go_a = (o_a - origin_a) / h, gd_a = d_a / h (IEEE divisions), len = sqrtf(fma(d_z, d_z, fma(d_y, d_y, d_x*d_x)));
