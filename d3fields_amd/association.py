@@ -137,7 +137,7 @@ def paint_label_images(fusion, instances):
     lib = _lib.load()
     dev = torch.device(fusion.device)
     obs = fusion.curr_obs_torch
-    out = torch.zeros((fusion.num_cam, fusion.H, fusion.W), dtype=torch.uint8, device=dev)
+    out = torch.empty((fusion.num_cam, fusion.H, fusion.W), dtype=torch.uint8, device=dev)      # (d3f_compose_labels writes every pixel of every view)
     for view in range(fusion.num_cam):
         dets = _device_tensor(obs["mask_gs"][view], dev)        # numpy, CPU or device tensor (a GPU SAM producer's natural output)
         dets = (dets != 0).to(torch.uint8).reshape(dets.shape[0], -1).contiguous()

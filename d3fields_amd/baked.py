@@ -304,14 +304,18 @@ class Flow:
         ref = None if ref is None else ref.to(torch.int32).contiguous()
         n = nx * ny * nz
         tau2 = float(tau_voxels) * float(tau_voxels)
-        pose = torch.full((K, _lib.MOTION_POSE_DOUBLES), math.nan, dtype=torch.float64, device=dev)
-        pairs, inliers = torch.zeros(K, dtype=torch.int32, device=dev), torch.zeros(K, dtype=torch.int32, device=dev)
-        done = torch.zeros(K, dtype=torch.int32, device=dev)
-        status = torch.full((K,), _lib.MOTION_TOO_FEW, dtype=torch.int32, device=dev)
-        rmse = torch.full((K,), math.nan, dtype=torch.float64, device=dev)
-        res2 = torch.full((nx, ny, nz), math.nan, dtype=torch.float64, device=dev)
-        inlier = torch.zeros((nx, ny, nz), dtype=torch.uint8, device=dev)
-        if K > 0:                                                        # (no part: every output is empty, there is nothing to point at)
+        # the call writes every output: the capacity below counts a superset of the pairs, so the list always fits, and under the final poses
+        # motion_fill_kernel puts NaN / 0 into the two volumes before the pairs' own values land there
+        pose = torch.empty((K, _lib.MOTION_POSE_DOUBLES), dtype=torch.float64, device=dev)
+        pairs, inliers = torch.empty(K, dtype=torch.int32, device=dev), torch.empty(K, dtype=torch.int32, device=dev)
+        done, status = torch.empty(K, dtype=torch.int32, device=dev), torch.empty(K, dtype=torch.int32, device=dev)
+        rmse = torch.empty(K, dtype=torch.float64, device=dev)
+        if K == 0:                                                       # (no part: nothing is launched, the per-part outputs are empty and the volumes are filled here)
+            res2 = torch.full((nx, ny, nz), math.nan, dtype=torch.float64, device=dev)
+            inlier = torch.zeros((nx, ny, nz), dtype=torch.uint8, device=dev)
+        else:
+            res2 = torch.empty((nx, ny, nz), dtype=torch.float64, device=dev)
+            inlier = torch.empty((nx, ny, nz), dtype=torch.uint8, device=dev)
             passes = (labels > 0) & (target >= 0)
             capacity = int((passes if keep is None else passes & keep).sum())
             members = torch.empty(1, dtype=torch.int64, device=dev)
@@ -524,7 +528,7 @@ class BakedField:
         n = nx * ny * nz
         cell_band = torch.empty((nx - 1, ny - 1, nz - 1), dtype=torch.uint8, device=dev)
         slot = torch.empty((nx, ny, nz), dtype=torch.int32, device=dev)
-        count = torch.zeros(1, dtype=torch.int64, device=dev)
+        count = torch.empty(1, dtype=torch.int64, device=dev)        # (d3f_band_mark always writes it)
         ws_bytes = int(self._lib.d3f_band_workspace_bytes(nx, ny, nz))
         ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
         vol = self._volume()
@@ -1415,9 +1419,13 @@ class BakedField:
                     torch.empty(0, dtype=torch.int32, device=dev), torch.empty((0, k, 3), dtype=torch.float64, device=dev) if refine else None)
         slot = self.slot if rows_banded else None
         sup = torch.empty((M, K), dtype=torch.float32, device=dev)
-        count = torch.zeros(K, dtype=torch.int32, device=dev)
-        idx = torch.full((k, K), -1, dtype=torch.int64, device=dev)
-        val = torch.full((k, K), float("inf"), dtype=torch.float32, device=dev)
+        # (d3f_volume_peaks zeroes the counts itself before it adds to them; without rows it is not called)
+        count = torch.empty(K, dtype=torch.int32, device=dev) if M > 0 else torch.zeros(K, dtype=torch.int32, device=dev)
+        if M > 0:                                      # (d3f_topk_smallest writes every entry: -1 / NaN where there are fewer than k rows)
+            idx, val = torch.empty((k, K), dtype=torch.int64, device=dev), torch.empty((k, K), dtype=torch.float32, device=dev)
+        else:
+            idx = torch.full((k, K), -1, dtype=torch.int64, device=dev)
+            val = torch.full((k, K), float("inf"), dtype=torch.float32, device=dev)
         if M > 0:                                      # (an empty tensor has no address: nothing to ask)
             ws_bytes = int(self._lib.d3f_pairwise_topk_workspace_bytes(M, K))
             ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
@@ -1599,7 +1607,8 @@ class BakedField:
         for k, v in terms.items():
             if not (v >= 0.0 and math.isfinite(v)):
                 raise ValueError("%s: %s must be finite and >= 0, got %r" % (who, k, v))
-        centroid = torch.zeros((I, 3), dtype=torch.float32, device=self.device)
+        # (d3f_volume_align_centroid writes every row, zeros where an instance has no weighted finite point; it is not called without points)
+        centroid = (torch.empty if I > 0 and n > 0 else torch.zeros)((I, 3), dtype=torch.float32, device=self.device)
         if I > 0 and n > 0:
             with torch.cuda.device(self.device):
                 _lib.check(self._lib.d3f_volume_align_centroid(_lib.ptr(pts), _lib.ptr(wt), I, n, _lib.ptr(centroid), _lib.current_stream_handle(self.device)))
@@ -1648,9 +1657,11 @@ class BakedField:
         prob = self._align_problem(who, points, name, targets, dist_targets, weights, dist_weight, feat_weight, outside)
         I, dev = prob["I"], self.device
         pose = self._align_pose(who, I, rot, trans)
-        out = torch.zeros((I, _lib.ALIGN_ROW_DOUBLES), dtype=torch.float64, device=dev)
         if I > 0 and prob["n"] > 0:
+            out = torch.empty((I, _lib.ALIGN_ROW_DOUBLES), dtype=torch.float64, device=dev)      # (without skip the fold writes every row)
             self._align_accumulate(prob, pose, None, out)
+        else:
+            out = torch.zeros((I, _lib.ALIGN_ROW_DOUBLES), dtype=torch.float64, device=dev)
         iu = torch.triu_indices(6, 6, device=dev)
         H = torch.zeros((I, 6, 6), dtype=torch.float64, device=dev)
         H[:, iu[0], iu[1]] = out[:, :21]
@@ -1700,16 +1711,19 @@ class BakedField:
         state[:, 12:24] = pose
         state[:, 24:27] = prob["centroid"]
         state[:, 27] = 1e-3
-        history = torch.zeros((I, iters + 1), dtype=torch.float64, device=dev)
         if I > 0 and n > 0:
+            # state (beyond [0, 28)) and skip must be zero, as the header says; step `it` writes history[:, it] of every instance and step 0
+            # writes every row of out (every instance is RUNNING then)
+            history = torch.empty((I, iters + 1), dtype=torch.float64, device=dev)
             skip = torch.zeros(I, dtype=torch.int32, device=dev)
-            out = torch.zeros((I, _lib.ALIGN_ROW_DOUBLES), dtype=torch.float64, device=dev)
+            out = torch.empty((I, _lib.ALIGN_ROW_DOUBLES), dtype=torch.float64, device=dev)
             for it in range(iters + 1):
                 self._align_accumulate(prob, pose, skip, None)
                 with torch.cuda.device(dev):
                     _lib.check(self._lib.d3f_volume_align_step(_lib.ptr(state), _lib.ptr(prob["ws"]), prob["ws_bytes"], I, n, _lib.ptr(out), it, iters, rot_tol,
                                                                trans_tol, _lib.ptr(pose), _lib.ptr(skip), _lib.ptr(history), _lib.current_stream_handle(dev)))
         else:
+            history = torch.zeros((I, iters + 1), dtype=torch.float64, device=dev)
             state[:, 29] = _lib.ALIGN_NO_GRADIENT          # no point at all: nothing to align to
         R = state[:, 0:9].to(torch.float32).reshape(I, 3, 3)
         t = state[:, 9:12].to(torch.float32)

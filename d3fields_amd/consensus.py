@@ -148,11 +148,16 @@ def consensus_poses(model_pts, candidates, tau, n_poses=8, min_inliers=4, shared
         raise ValueError("%s: tau = %r squares to zero in float32" % (who, tau))
 
     lib = _lib.load()
-    hyp = torch.full((H,), -1, dtype=torch.int32, device=dev)
-    inl = torch.full((H,), -1, dtype=torch.int32, device=dev)
-    asg = torch.full((H, _lib.CONSENSUS_MAX_POINTS), -1, dtype=torch.int8, device=dev)
-    pose = torch.full((H, 12), float("nan"), dtype=torch.float32, device=dev)
-    stats = torch.zeros(4, dtype=torch.int32, device=dev)
+    if n_trip > 0:                                  # (the select kernel writes every rank, the ones that do not exist as -1 / NaN)
+        hyp, inl = torch.empty(H, dtype=torch.int32, device=dev), torch.empty(H, dtype=torch.int32, device=dev)
+        asg = torch.empty((H, _lib.CONSENSUS_MAX_POINTS), dtype=torch.int8, device=dev)
+        pose = torch.empty((H, 12), dtype=torch.float32, device=dev)
+    else:
+        hyp = torch.full((H,), -1, dtype=torch.int32, device=dev)
+        inl = torch.full((H,), -1, dtype=torch.int32, device=dev)
+        asg = torch.full((H, _lib.CONSENSUS_MAX_POINTS), -1, dtype=torch.int8, device=dev)
+        pose = torch.full((H, 12), float("nan"), dtype=torch.float32, device=dev)
+    stats = torch.empty(4, dtype=torch.int32, device=dev) if n_trip > 0 else torch.zeros(4, dtype=torch.int32, device=dev)      # (select writes all four)
     terms = (tau2, side_tol, min_side, min_sin)
     with torch.cuda.device(dev):
         stream = _lib.current_stream_handle(dev)
@@ -167,9 +172,9 @@ def consensus_poses(model_pts, candidates, tau, n_poses=8, min_inliers=4, shared
                                                      ws_bytes, stream))
         out = _result(hyp, inl, asg, pose, stats, trip_dev, M, k)
         if refit:
-            rpose = torch.full((H, 12), float("nan"), dtype=torch.float32, device=dev)
-            rmse = torch.full((H,), float("nan"), dtype=torch.float64, device=dev)
-            rinl = torch.full((H,), -1, dtype=torch.int32, device=dev)
+            rpose = torch.empty((H, 12), dtype=torch.float32, device=dev)          # (one wave per rank writes all three, NaN / -1 without three pairs)
+            rmse = torch.empty(H, dtype=torch.float64, device=dev)
+            rinl = torch.empty(H, dtype=torch.int32, device=dev)
             _lib.check(lib.d3f_pose_refit(_lib.ptr(p), _lib.ptr(c), M, k, _lib.ptr(asg), H, tau2, _lib.ptr(rpose), _lib.ptr(rmse), _lib.ptr(rinl), stream))
             out.update({"refit_rot": rpose[:, :9].reshape(H, 3, 3).transpose(1, 2).contiguous(), "refit_trans": rpose[:, 9:].contiguous(), "rmse": rmse,
                         "refit_inliers": rinl})

@@ -429,7 +429,8 @@ __global__ __launch_bounds__(kBlock) void lattice_probe_kernel(const float *__re
 // locality probe (256 samples each), and every output word is WRITTEN by exactly one workgroup, so the buffer needs no clearing:
 //   out[0..2] lattice dims (zeros: not a lattice)      out[8 + b], b < 16: 1 if workgroup b's samples contradict the dims
 //   out[24 + 3 q .. +2], q < 4: sum of near steps, sum of far distances, number of finite samples (floats) of locality workgroup q
-static_assert(D3F_PROBE_WORDS == 40, "points_probe_kernel writes words 0..3, 8..23 and 24..35");
+//   out[4..7], out[36..39]: unused, zeroed by workgroup 0
+static_assert(D3F_PROBE_WORDS == 40, "points_probe_kernel writes words 0..3, 8..23 and 24..35, and zeroes 4..7 and 36..39");
 constexpr int kLocalityBlocks = 4;
 __global__ __launch_bounds__(kBlock) void points_probe_kernel(const float *__restrict__ pts, int64_t n, int32_t *__restrict__ out)
 {
@@ -474,6 +475,8 @@ __global__ __launch_bounds__(kBlock) void points_probe_kernel(const float *__res
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         out[0] = ok ? (int32_t)nx : 0; out[1] = ok ? ny : 0; out[2] = ok ? nz : 0; out[3] = 0;
     }
+    // the words no probe reports in (4..7 and 36..39) are zeroed, so that EVERY word of `out` is written, as the header says
+    if (blockIdx.x == 0 && ((threadIdx.x >= 4 && threadIdx.x < 8) || (threadIdx.x >= 36 && threadIdx.x < D3F_PROBE_WORDS))) out[threadIdx.x] = 0;
     int bad = 0;
     if (ok) {
         const int64_t samples = min((int64_t)kProbeBlocks * kBlock, n);

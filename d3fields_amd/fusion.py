@@ -972,7 +972,7 @@ class Fusion:
         grid, axes = self._grid(boundaries, step_size)
         n = grid.nx * grid.ny * grid.nz
         views, keep, V = self._views(dev)
-        count = torch.zeros(1, dtype=torch.int64, device=dev)
+        count = torch.empty(1, dtype=torch.int64, device=dev)    # (d3f_grid_shell clears it itself, then writes the total)
         capacity = max(1 << 16, n // 16)
         ws_bytes = self._lib.d3f_grid_shell_workspace_bytes(ctypes.byref(grid))
         # (+ room for the tiled copy of the depth maps a big grid's lookups go to: include/d3fields_hip.h, d3f_grid_shell)

@@ -56,7 +56,7 @@ def marching_cubes(vol, shape, iso=0.0, valid=None, count_first=False, capacitie
         valid = valid.contiguous().view(-1)
     ws_bytes = int(lib.d3f_mesh_workspace_bytes(nx, ny, nz))
     ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-    counts = torch.zeros(2, dtype=torch.int64, device=dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)       # (both calls write both counts)
     stream = _lib.current_stream_handle(dev)
     with torch.cuda.device(dev):
         if count_first:

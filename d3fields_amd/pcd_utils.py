@@ -46,7 +46,7 @@ def _backproject(depth, mask, cam_params, cam_to_world, bounds, dev):
     cap = H * W
     pts = torch.empty((cap, 3), dtype=torch.float64, device=dev)
     pix = torch.empty(cap, dtype=torch.int32, device=dev)
-    cnt = torch.zeros(1, dtype=torch.int64, device=dev)
+    cnt = torch.empty(1, dtype=torch.int64, device=dev)          # (written by the call: H, W >= 1)
     ws = torch.empty(lib.d3f_backproject_workspace_bytes(H, W), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         _lib.check(lib.d3f_backproject_view(_lib.ptr(d), _lib.ptr(m), H, W, _dbl(cam_params), _dbl(np.asarray(cam_to_world).reshape(-1)),
@@ -110,7 +110,7 @@ def voxel_downsample(pcd, voxel_size, pcd_color=None):
     col = torch.from_numpy(np.ascontiguousarray(pcd_color, dtype=np.float64).reshape(-1, 3)).to(dev) if pcd_color is not None else None
     out_p = torch.empty((n, 3), dtype=torch.float64, device=dev)
     out_c = torch.empty((n, 3), dtype=torch.float64, device=dev) if col is not None else None
-    cnt = torch.zeros(1, dtype=torch.int64, device=dev)
+    cnt = torch.empty(1, dtype=torch.int64, device=dev)          # (written by the call, also for n == 0)
     ws_bytes = lib.d3f_voxel_downsample_workspace_bytes(n)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):

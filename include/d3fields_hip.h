@@ -14,6 +14,12 @@
  *     d3f_last_error() and the one-shot event pair armed by d3f_profile_next_eval() (a measurement
  *     hook, consumed by the same thread's next query); work is enqueued on `stream` (a
  *     hipStream_t, NULL = default stream) and NOT synchronised;
+ *   - a workspace or an output may hold ANYTHING when it is handed over (a fresh hipMalloc, the leftovers of another
+ *     call): every call clears or writes what it reads, on `stream`.  The exceptions are stated where they apply and are
+ *     these: the point order and gate words under D3F_FLAG_REUSE_POINT_ORDER, the words of D3F_CHECK_WORDS_ARE_ZERO,
+ *     out_dims[3] of d3f_lattice_probe, the state block and skip words of d3f_volume_align_step, the workspace
+ *     d3f_pose_consensus_select and d3f_volume_geodesic_relax take over from the call before them, the Adam state of
+ *     d3f_rigid_update and the scratch of d3f_track_step (tests/test_gpu_dirty_buffers.py);
  *   - all tensors fp32, C-contiguous unless strides are part of the signature;
  *   - return value: D3F_OK or a negative D3F_ERR_* code; d3f_last_error() gives the text of
  *     the calling thread's last failure.  Nothing aborts.
@@ -715,7 +721,9 @@ int d3f_volume_peaks(const int32_t *slot, const uint8_t *mask, int32_t nx, int32
  *   solved at a pose accepted in this very call also ends the instance as CONVERGED, without being taken: it would lower the cost by less
  *   than the fp32 sums resolve, so it could never be accepted.  Otherwise the candidate R = Exp(w) R, t = c + Exp(w)(t - c) + v with
  *   Rodrigues in float64, rounded to float32, goes to the state and to pose_out[i].
- *   A final instance, and every instance at it == iters, gets pose_out[i] = its accepted pose; a final one also skip_out[i] = 1.
+ *   An instance that ends in this call, and every instance at it == iters, gets pose_out[i] = its accepted pose; one that ends also skip_out[i] = 1.
+ *   skip_out (the `skip` of the accumulate) must be ZERO before step 0: the step only ever stores 1 there.  pose_out, out and history may hold anything
+ *   before step 0, which writes out[i] and pose_out[i] of every instance; an instance that was final at entry keeps what an earlier step wrote there.
  * A solve is accumulate(pose, skip), step(0), accumulate, step(1), ... step(iters) on one stream: 2 iters + 2 launches, no allocation, no
  * synchronisation, no atomics, and no kernel waits for another workgroup.
  * Status errors, on the host before any HIP call: NULL vol / points / pose / centroids / workspace / state / outputs, negative I or n, a weight

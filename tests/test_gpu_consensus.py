@@ -136,11 +136,8 @@ def test_refit_is_exact_on_a_quarter_turn(dev, axis):
     assert np.isnan(pose[1]).all() and np.isnan(rmse[1]) and inl[1] == -1
 
 
-@pytest.mark.parametrize("name", CC.REFIT_CASES)
-def test_refit_against_the_horn_restatement(dev, name):
-    cs, params = CC.case(name)
-    ref = CC.reference(name)
-    pose, rmse, inl = run_refit(dev, cs["p"], cs["c"], ref["sel_assign"], ref["tau2"])
+def check_refit(cs, params, ref, pose, rmse, inl):
+    """the refit outputs of ref['sel_assign'] against the Horn restatement -> the worst error / bound (shared with tests/dirty_cases.py)"""
     worst = 0.0
     for r in range(params["n_poses"]):
         if r >= ref["found"]:
@@ -159,7 +156,15 @@ def test_refit_against_the_horn_restatement(dev, name):
         assert abs(rmse[r] - want_rmse) <= 1e-12 * max(1.0, want_rmse) + 8 * CC.EPS * np.abs(cc).max()
         n, _ = CC.score(pose[r:r + 1], cs["p"], cs["c"], ref["tau2"])       # the count at the DEVICE's refit pose, by the restatement: exact
         assert inl[r] == n[0]
-    print(name, "refit: worst error / bound", worst)
+    return worst
+
+
+@pytest.mark.parametrize("name", CC.REFIT_CASES)
+def test_refit_against_the_horn_restatement(dev, name):
+    cs, params = CC.case(name)
+    ref = CC.reference(name)
+    pose, rmse, inl = run_refit(dev, cs["p"], cs["c"], ref["sel_assign"], ref["tau2"])
+    print(name, "refit: worst error / bound", check_refit(cs, params, ref, pose, rmse, inl))
 
 
 # ---- the public layer ---------------------------------------------------------------------------------------------------------------------
