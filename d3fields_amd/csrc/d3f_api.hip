@@ -39,6 +39,86 @@ int check_views(const d3f_views *v)
     return D3F_OK;
 }
 
+// ---- the argument rules the kernels rely on, each stated once: an entry point calls these and restates none of them (which status wins when
+// two arguments are bad is pinned row by row, tests/test_api_status_host.py).  who: the entry point's short name, the first word of every message ----
+bool finite_nonneg(double v) { return v >= 0.0 && v * 0.0 == 0.0; }
+bool positive_finite(float x) { return x > 0.0f && x * 0.0f == 0.0f; }
+
+// a site volume: 32-bit voxel indices, and the extents the distance transform's rows can take.  The predicate of the *_workspace_bytes functions.
+bool edt_shape_ok(int32_t nx, int32_t ny, int32_t nz)
+{
+    return nx >= 1 && ny >= 1 && nz >= 1 && nx <= D3F_EDT_MAX_EXTENT && ny <= D3F_EDT_MAX_EXTENT && nz <= D3F_EDT_MAX_EXTENT &&
+           (int64_t)nx * ny * nz <= 0x7fffffffLL;
+}
+
+int check_extents(const char *who, int32_t nx, int32_t ny, int32_t nz)
+{
+    if (edt_shape_ok(nx, ny, nz)) return D3F_OK;
+    return fail(D3F_ERR_BAD_SHAPE, "%s: nx=%d ny=%d nz=%d, every extent must be in [1, %d] and the volume at most 2^31 - 1 voxels", who, nx, ny, nz,
+                D3F_EDT_MAX_EXTENT);
+}
+
+int check_connectivity(const char *who, int32_t c)
+{
+    if (c == 6 || c == 18 || c == 26) return D3F_OK;
+    return fail(D3F_ERR_INVALID_ARG, "%s: connectivity=%d, must be 6, 18 or 26", who, c);
+}
+
+// the workspace protocol: absent or short is D3F_ERR_WORKSPACE (with the size to bring), only then misaligned is D3F_ERR_BAD_LAYOUT
+int check_workspace(const char *who, const void *workspace, int64_t bytes, int64_t need, int alignment)
+{
+    if (!workspace || bytes < need) return fail(D3F_ERR_WORKSPACE, "%s: needs %lld workspace bytes", who, (long long)need);
+    if (!aligned(workspace, alignment)) return fail(D3F_ERR_BAD_LAYOUT, "%s: workspace must be %d-byte aligned", who, alignment);
+    return D3F_OK;
+}
+
+// a stored set, by status: its width (the kernels' row loops), then its rows (stride_voxel and the 4-byte loads).  fill is read by the lookups and
+// the pooling only, and checked there.
+int check_set_shape(const char *who, int s, const d3f_volume_set &set)
+{
+    if (set.C >= 1 && set.C <= D3F_VOLUME_MAX_CHANNELS) return D3F_OK;
+    return fail(D3F_ERR_BAD_SHAPE, "%s: set %d: C=%d outside [1,%d]", who, s, set.C, D3F_VOLUME_MAX_CHANNELS);
+}
+
+int check_set_layout(const char *who, int s, const d3f_volume_set &set)
+{
+    if (set.stride_voxel < set.C) return fail(D3F_ERR_BAD_LAYOUT, "%s: set %d: stride_voxel=%lld < C=%d", who, s, (long long)set.stride_voxel, set.C);
+    if (!aligned(set.data, 4)) return fail(D3F_ERR_BAD_LAYOUT, "%s: set %d: data must be 4-byte aligned", who, s);
+    return D3F_OK;
+}
+
+// may the rows of a set move as 16-byte vectors?  (and-ed with the alignment of what is written or read beside them by the caller)
+bool set_reads_vectors(const d3f_volume_set &set) { return set.C % 4 == 0 && set.stride_voxel % 4 == 0 && aligned(set.data, 16); }
+
+// one thread per item, per_block items to a workgroup: the grid's x has 31 bits
+int check_launch_blocks(const char *who, int64_t n, int64_t per_block)
+{
+    if ((n + per_block - 1) / per_block > 0x7fffffffLL) return fail(D3F_ERR_BAD_SHAPE, "%s: n=%lld too large for one launch", who, (long long)n);
+    return D3F_OK;
+}
+
+// the per-set outputs of a lookup / the per-set gradients of its backward; a set keeps its vectors only if these are 16-byte aligned too
+int attach_outputs(const char *who, d3f::VolParams &P, int32_t n_sets, void *const *out_sets)
+{
+    for (int s = 0; s < n_sets; ++s) {
+        if (!out_sets[s]) return fail(D3F_ERR_INVALID_ARG, "%s: out_sets[%d] is NULL", who, s);
+        if (!aligned(out_sets[s], 4)) return fail(D3F_ERR_BAD_LAYOUT, "%s: out_sets[%d] must be 4-byte aligned", who, s);
+        P.sets[s].out = static_cast<float *>(out_sets[s]);
+        if (!aligned(out_sets[s], 16)) P.sets[s].vec = 0;
+    }
+    return D3F_OK;
+}
+
+int attach_grads(const char *who, d3f::VolParams &P, int32_t n_sets, const void *const *grad_sets)
+{
+    for (int s = 0; s < n_sets && grad_sets; ++s) {
+        if (!aligned(grad_sets[s], 4)) return fail(D3F_ERR_BAD_LAYOUT, "%s: grad_sets[%d] must be 4-byte aligned", who, s);
+        P.sets[s].grad = static_cast<const float *>(grad_sets[s]);
+        if (!aligned(grad_sets[s], 16)) P.sets[s].vec = 0;
+    }
+    return D3F_OK;
+}
+
 #ifdef D3F_EXPERIMENTS
 // phase stamps of the window kernel (Tune::stamps): 32 x uint64 per sampled workgroup, read back with d3f_exp_read_stamps
 constexpr int64_t kStampBytes = 8LL * 32 * 65536;
@@ -387,7 +467,7 @@ int d3f_pcd_to_index(const double *pts, int64_t n, const double *lower, double v
     if (!(voxel_size != 0.0)) return fail(D3F_ERR_INVALID_ARG, "pcd_to_index: voxel_size must be non-zero");
     if (n == 0) return D3F_OK;
     if (!pts || !out_index) return fail(D3F_ERR_INVALID_ARG, "pcd_to_index: NULL pointer");
-    if ((n + d3f::kBlock - 1) / d3f::kBlock > 0x7fffffffLL) return fail(D3F_ERR_BAD_SHAPE, "pcd_to_index: n=%lld too large for one launch", (long long)n);
+    if (const int rc = check_launch_blocks("pcd_to_index", n, d3f::kBlock)) return rc;
     hipError_t e = d3f::launch_pcd_to_index(pts, n, lower, voxel_size, voxel_num, out_index, out_voxel, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? D3F_OK : hip_fail(e, "pcd_to_index launch");
 }
@@ -403,9 +483,8 @@ int d3f_vox_idx_iou(const int32_t *idx1, int64_t n1, const int32_t *idx2, int64_
 {
     if (n1 < 0 || n2 < 0 || n1 + n2 > 0x3fffffffLL) return fail(D3F_ERR_BAD_SHAPE, "vox_idx_iou: n1=%lld n2=%lld", (long long)n1, (long long)n2);
     if (!out_counts || (n1 > 0 && !idx1) || (n2 > 0 && !idx2)) return fail(D3F_ERR_INVALID_ARG, "vox_idx_iou: NULL pointer");
-    if (!workspace || workspace_bytes < d3f_vox_iou_workspace_bytes(n1, n2))
-        return fail(D3F_ERR_WORKSPACE, "vox_idx_iou: needs %lld workspace bytes", (long long)d3f_vox_iou_workspace_bytes(n1, n2));
-    if (!aligned(workspace, 8) || !aligned(out_counts, 8)) return fail(D3F_ERR_BAD_LAYOUT, "vox_idx_iou: workspace / out_counts must be 8-byte aligned");
+    if (const int rc = check_workspace("vox_idx_iou", workspace, workspace_bytes, d3f_vox_iou_workspace_bytes(n1, n2), 8)) return rc;
+    if (!aligned(out_counts, 8)) return fail(D3F_ERR_BAD_LAYOUT, "vox_idx_iou: out_counts must be 8-byte aligned");
     hipError_t e = d3f::launch_voxset_iou(idx1, n1, idx2, n2, out_counts, workspace, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? D3F_OK : hip_fail(e, "vox_idx_iou launch");
 }
@@ -440,9 +519,7 @@ int d3f_voxel_downsample(const double *pts, const double *colors, int64_t n, dou
     if (!count_out) return fail(D3F_ERR_INVALID_ARG, "voxel_downsample: count_out is NULL");
     if (n == 0) return hipMemsetAsync(count_out, 0, sizeof(int64_t), static_cast<hipStream_t>(stream)) == hipSuccess ? D3F_OK : D3F_ERR_HIP;
     if (!pts || !out_pts || (colors && !out_colors)) return fail(D3F_ERR_INVALID_ARG, "voxel_downsample: NULL pointer");
-    if (!workspace || workspace_bytes < d3f_voxel_downsample_workspace_bytes(n))
-        return fail(D3F_ERR_WORKSPACE, "voxel_downsample: needs %lld workspace bytes", (long long)d3f_voxel_downsample_workspace_bytes(n));
-    if (!aligned(workspace, 16)) return fail(D3F_ERR_BAD_LAYOUT, "voxel_downsample: workspace must be 16-byte aligned");
+    if (const int rc = check_workspace("voxel_downsample", workspace, workspace_bytes, d3f_voxel_downsample_workspace_bytes(n), 16)) return rc;
     hipError_t e = d3f::launch_voxel_mean(pts, colors, n, voxel_size, out_pts, colors ? out_colors : nullptr, count_out, workspace,
                                           static_cast<hipStream_t>(stream));
     return e == hipSuccess ? D3F_OK : hip_fail(e, "voxel_downsample launch");
@@ -548,10 +625,7 @@ static int check_mesh(const char *who, const float *volume, int32_t nx, int32_t 
         return fail(D3F_ERR_BAD_SHAPE, "%s: %lld points exceed (2^31 - 1) / 3 (32-bit vertex and triangle indices)", who, (long long)nx * ny * nz);
     if (!volume || !counts_out) return fail(D3F_ERR_INVALID_ARG, "%s: volume / counts_out must be non-NULL", who);
     if (!aligned(volume, 4) || !aligned(counts_out, 8)) return fail(D3F_ERR_BAD_LAYOUT, "%s: volume / counts_out must be aligned to their element size", who);
-    if (!workspace || workspace_bytes < d3f_mesh_workspace_bytes(nx, ny, nz))
-        return fail(D3F_ERR_WORKSPACE, "%s: needs %lld workspace bytes", who, (long long)d3f_mesh_workspace_bytes(nx, ny, nz));
-    if (!aligned(workspace, 4)) return fail(D3F_ERR_BAD_LAYOUT, "%s: workspace must be 4-byte aligned", who);
-    return D3F_OK;
+    return check_workspace(who, workspace, workspace_bytes, d3f_mesh_workspace_bytes(nx, ny, nz), 4);
 }
 
 int64_t d3f_mesh_workspace_bytes(int32_t nx, int32_t ny, int32_t nz)
@@ -605,9 +679,8 @@ int d3f_volume_gaussian(const float *src, float *dst, int32_t nx, int32_t ny, in
     if (radius > D3F_GAUSSIAN_MAX_RADIUS)
         return fail(D3F_ERR_BAD_SHAPE, "volume_gaussian: radius %d exceeds D3F_GAUSSIAN_MAX_RADIUS = %d", radius, D3F_GAUSSIAN_MAX_RADIUS);
     if (!src || !dst || src == dst) return fail(D3F_ERR_INVALID_ARG, "volume_gaussian: src / dst must be distinct non-NULL volumes");
-    if (!workspace || workspace_bytes < d3f_volume_gaussian_workspace_bytes(nx, ny, nz))
-        return fail(D3F_ERR_WORKSPACE, "volume_gaussian: needs %lld workspace bytes", (long long)d3f_volume_gaussian_workspace_bytes(nx, ny, nz));
-    if (!aligned(src, 4) || !aligned(dst, 4) || !aligned(workspace, 4)) return fail(D3F_ERR_BAD_LAYOUT, "volume_gaussian: pointers must be 4-byte aligned");
+    if (const int rc = check_workspace("volume_gaussian", workspace, workspace_bytes, d3f_volume_gaussian_workspace_bytes(nx, ny, nz), 4)) return rc;
+    if (!aligned(src, 4) || !aligned(dst, 4)) return fail(D3F_ERR_BAD_LAYOUT, "volume_gaussian: src / dst must be 4-byte aligned");
     // scipy _gaussian_kernel1d: phi = exp(-0.5 / sigma^2 * x^2), phi / phi.sum(), float64
     double w[D3F_GAUSSIAN_MAX_RADIUS + 1], sum = 0.0;
     const double sd = (double)sigma;
@@ -645,22 +718,21 @@ int d3f_volume_cell_valid(const d3f_volume *vol, uint8_t *cell_valid_out, void *
 static int volume_common(const char *who, const d3f_volume *vol, const float *pts, int64_t n, const d3f_volume_set *sets, int32_t n_sets,
                          d3f::VolParams &P, bool null_data_ok = false)
 {
-    int rc = check_volume(who, vol);
+    const int rc = check_volume(who, vol);
     if (rc != D3F_OK) return rc;
-    if (!(vol->step > 0.0f) || vol->step * 0.0f != 0.0f) return fail(D3F_ERR_INVALID_ARG, "%s: vol->step must be > 0 and finite", who);
+    if (!positive_finite(vol->step)) return fail(D3F_ERR_INVALID_ARG, "%s: vol->step must be > 0 and finite", who);
     if (n < 0) return fail(D3F_ERR_INVALID_ARG, "%s: n=%lld is negative", who, (long long)n);
     if (n_sets < 0 || n_sets > D3F_MAX_MAPS) return fail(D3F_ERR_BAD_SHAPE, "%s: n_sets=%d outside [0,%d]", who, n_sets, D3F_MAX_MAPS);
     if (n_sets > 0 && !sets) return fail(D3F_ERR_INVALID_ARG, "%s: sets is NULL with n_sets=%d", who, n_sets);
     for (int s = 0; s < n_sets; ++s)
-        if (sets[s].C < 1 || sets[s].C > D3F_VOLUME_MAX_CHANNELS)
-            return fail(D3F_ERR_BAD_SHAPE, "%s: set %d: C=%d outside [1,%d]", who, s, sets[s].C, D3F_VOLUME_MAX_CHANNELS);
+        if (const int rc = check_set_shape(who, s, sets[s])) return rc;
     if (n == 0) return 1;
     if (!vol->dist || !vol->cell_valid || !pts) return fail(D3F_ERR_INVALID_ARG, "%s: vol->dist / vol->cell_valid / pts must be non-NULL", who);
     if (!aligned(vol->dist, 4) || !aligned(pts, 4)) return fail(D3F_ERR_BAD_LAYOUT, "%s: vol->dist / pts must be 4-byte aligned", who);
     for (int s = 0; s < n_sets; ++s) {
         if (!sets[s].data && !null_data_ok) return fail(D3F_ERR_INVALID_ARG, "%s: set %d: data is NULL", who, s);
-        if (sets[s].stride_voxel < sets[s].C) return fail(D3F_ERR_BAD_LAYOUT, "%s: set %d: stride_voxel=%lld < C=%d", who, s, (long long)sets[s].stride_voxel, sets[s].C);
-        if (!aligned(sets[s].data, 4) || !aligned(sets[s].fill, 4)) return fail(D3F_ERR_BAD_LAYOUT, "%s: set %d: data / fill must be 4-byte aligned", who, s);
+        if (const int rc = check_set_layout(who, s, sets[s])) return rc;
+        if (!aligned(sets[s].fill, 4)) return fail(D3F_ERR_BAD_LAYOUT, "%s: set %d: fill must be 4-byte aligned", who, s);
         d3f::VolSet &S = P.sets[s];
         S.data = sets[s].data;
         S.fill = sets[s].fill;
@@ -668,7 +740,7 @@ static int volume_common(const char *who, const d3f_volume *vol, const float *pt
         S.grad = nullptr;
         S.stride = sets[s].stride_voxel;
         S.C = sets[s].C;
-        S.vec = (S.C % 4 == 0 && S.stride % 4 == 0 && aligned(S.data, 16)) ? 1 : 0;      // and-ed with the alignment of out / grad by the caller
+        S.vec = set_reads_vectors(sets[s]) ? 1 : 0;      // and-ed with the alignment of out / grad by the caller
     }
     P.dist = vol->dist;
     P.cell = vol->cell_valid;
@@ -694,12 +766,7 @@ int d3f_volume_sample(const d3f_volume *vol, const float *pts, int64_t n, const 
     if (rc != D3F_OK) return rc == 1 ? D3F_OK : rc;
     if (!out_dist || !out_valid || (n_sets > 0 && !out_sets)) return fail(D3F_ERR_INVALID_ARG, "volume_sample: out_dist / out_valid / out_sets must be non-NULL");
     if (!aligned(out_dist, 4)) return fail(D3F_ERR_BAD_LAYOUT, "volume_sample: out_dist must be 4-byte aligned");
-    for (int s = 0; s < n_sets; ++s) {
-        if (!out_sets[s]) return fail(D3F_ERR_INVALID_ARG, "volume_sample: out_sets[%d] is NULL", s);
-        if (!aligned(out_sets[s], 4)) return fail(D3F_ERR_BAD_LAYOUT, "volume_sample: out_sets[%d] must be 4-byte aligned", s);
-        P.sets[s].out = static_cast<float *>(out_sets[s]);
-        if (!aligned(out_sets[s], 16)) P.sets[s].vec = 0;
-    }
+    if (const int rc = attach_outputs("volume_sample", P, n_sets, out_sets)) return rc;
     P.out_dist = out_dist;
     P.out_valid = out_valid;
     hipError_t e = d3f::launch_volume_sample(P, static_cast<hipStream_t>(stream));
@@ -714,11 +781,7 @@ int d3f_volume_sample_backward(const d3f_volume *vol, const float *pts, int64_t 
     if (rc != D3F_OK) return rc == 1 ? D3F_OK : rc;
     if (!grad_pts) return fail(D3F_ERR_INVALID_ARG, "volume_sample_backward: grad_pts is NULL");
     if (!aligned(grad_pts, 4) || !aligned(grad_dist, 4)) return fail(D3F_ERR_BAD_LAYOUT, "volume_sample_backward: grad_pts / grad_dist must be 4-byte aligned");
-    for (int s = 0; s < n_sets && grad_sets; ++s) {
-        if (!aligned(grad_sets[s], 4)) return fail(D3F_ERR_BAD_LAYOUT, "volume_sample_backward: grad_sets[%d] must be 4-byte aligned", s);
-        P.sets[s].grad = static_cast<const float *>(grad_sets[s]);
-        if (!aligned(grad_sets[s], 16)) P.sets[s].vec = 0;
-    }
+    if (const int rc = attach_grads("volume_sample_backward", P, n_sets, grad_sets)) return rc;
     P.grad_dist = grad_dist;
     P.grad_pts = grad_pts;
     hipError_t e = d3f::launch_volume_backward(P, static_cast<hipStream_t>(stream));
@@ -737,16 +800,14 @@ int d3f_band_mark(const d3f_volume *vol, float band, uint8_t *cell_band_out, int
 {
     const int rc = check_volume("band_mark", vol);
     if (rc != D3F_OK) return rc;
-    if (!(band > 0.0f) || band * 0.0f != 0.0f) return fail(D3F_ERR_INVALID_ARG, "band_mark: band must be > 0 and finite");
+    if (!positive_finite(band)) return fail(D3F_ERR_INVALID_ARG, "band_mark: band must be > 0 and finite");
     if (capacity < 0) return fail(D3F_ERR_INVALID_ARG, "band_mark: capacity=%lld is negative", (long long)capacity);
     if (!vol->dist || !vol->cell_valid) return fail(D3F_ERR_INVALID_ARG, "band_mark: vol->dist / vol->cell_valid must be non-NULL");
     if (!cell_band_out || !slot_out || !count_out || (capacity > 0 && !voxels_out))
         return fail(D3F_ERR_INVALID_ARG, "band_mark: cell_band_out / slot_out / count_out (and voxels_out for a positive capacity) must be non-NULL");
     if (!aligned(vol->dist, 4) || !aligned(slot_out, 4) || !aligned(voxels_out, 4) || !aligned(count_out, 8))
         return fail(D3F_ERR_BAD_LAYOUT, "band_mark: vol->dist / slot_out / voxels_out / count_out must be aligned to their element size");
-    if (!workspace || workspace_bytes < d3f_band_workspace_bytes(vol->nx, vol->ny, vol->nz))
-        return fail(D3F_ERR_WORKSPACE, "band_mark: needs %lld workspace bytes", (long long)d3f_band_workspace_bytes(vol->nx, vol->ny, vol->nz));
-    if (!aligned(workspace, 4)) return fail(D3F_ERR_BAD_LAYOUT, "band_mark: workspace must be 4-byte aligned");
+    if (const int rc = check_workspace("band_mark", workspace, workspace_bytes, d3f_band_workspace_bytes(vol->nx, vol->ny, vol->nz), 4)) return rc;
     hipError_t e = d3f::launch_band_mark(vol->dist, vol->cell_valid, vol->nx, vol->ny, vol->nz, band, cell_band_out, slot_out, voxels_out, capacity,
                                          count_out, workspace, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? D3F_OK : hip_fail(e, "band_mark launch");
@@ -778,12 +839,7 @@ int d3f_band_sample(const d3f_volume *vol, const d3f_band *band, const float *pt
     if (!out_dist || !out_valid || !out_in_band || (n_sets > 0 && !out_sets))
         return fail(D3F_ERR_INVALID_ARG, "band_sample: out_dist / out_valid / out_in_band / out_sets must be non-NULL");
     if (!aligned(out_dist, 4)) return fail(D3F_ERR_BAD_LAYOUT, "band_sample: out_dist must be 4-byte aligned");
-    for (int s = 0; s < n_sets; ++s) {
-        if (!out_sets[s]) return fail(D3F_ERR_INVALID_ARG, "band_sample: out_sets[%d] is NULL", s);
-        if (!aligned(out_sets[s], 4)) return fail(D3F_ERR_BAD_LAYOUT, "band_sample: out_sets[%d] must be 4-byte aligned", s);
-        B.V.sets[s].out = static_cast<float *>(out_sets[s]);
-        if (!aligned(out_sets[s], 16)) B.V.sets[s].vec = 0;
-    }
+    if (const int rc = attach_outputs("band_sample", B.V, n_sets, out_sets)) return rc;
     B.V.out_dist = out_dist;
     B.V.out_valid = out_valid;
     B.out_in_band = out_in_band;
@@ -799,11 +855,7 @@ int d3f_band_sample_backward(const d3f_volume *vol, const d3f_band *band, const 
     if (rc != D3F_OK) return rc == 1 ? D3F_OK : rc;
     if (!grad_pts) return fail(D3F_ERR_INVALID_ARG, "band_sample_backward: grad_pts is NULL");
     if (!aligned(grad_pts, 4) || !aligned(grad_dist, 4)) return fail(D3F_ERR_BAD_LAYOUT, "band_sample_backward: grad_pts / grad_dist must be 4-byte aligned");
-    for (int s = 0; s < n_sets && grad_sets; ++s) {
-        if (!aligned(grad_sets[s], 4)) return fail(D3F_ERR_BAD_LAYOUT, "band_sample_backward: grad_sets[%d] must be 4-byte aligned", s);
-        B.V.sets[s].grad = static_cast<const float *>(grad_sets[s]);
-        if (!aligned(grad_sets[s], 16)) B.V.sets[s].vec = 0;
-    }
+    if (const int rc = attach_grads("band_sample_backward", B.V, n_sets, grad_sets)) return rc;
     B.V.grad_dist = grad_dist;
     B.V.grad_pts = grad_pts;
     hipError_t e = d3f::launch_band_backward(B, static_cast<hipStream_t>(stream));
@@ -811,12 +863,6 @@ int d3f_band_sample_backward(const d3f_volume *vol, const d3f_band *band, const 
 }
 
 // ---- the exact Euclidean distance transform of a site volume (edt_kernels.hip) ----
-static bool edt_shape_ok(int32_t nx, int32_t ny, int32_t nz)
-{
-    return nx >= 1 && ny >= 1 && nz >= 1 && nx <= D3F_EDT_MAX_EXTENT && ny <= D3F_EDT_MAX_EXTENT && nz <= D3F_EDT_MAX_EXTENT &&
-           (int64_t)nx * ny * nz <= 0x7fffffffLL;
-}
-
 int64_t d3f_volume_edt_workspace_bytes(int32_t nx, int32_t ny, int32_t nz)
 {
     return edt_shape_ok(nx, ny, nz) ? d3f::edt_workspace_bytes((int64_t)nx * ny * nz) : 0;
@@ -827,16 +873,12 @@ int d3f_volume_edt(const uint8_t *site, int32_t nx, int32_t ny, int32_t nz, floa
 {
     if (!site) return fail(D3F_ERR_INVALID_ARG, "volume_edt: site is NULL");
     if (!out_d2 && !out_nearest && !out_dist) return fail(D3F_ERR_INVALID_ARG, "volume_edt: out_d2, out_nearest and out_dist are all NULL");
-    if (!edt_shape_ok(nx, ny, nz))
-        return fail(D3F_ERR_BAD_SHAPE, "volume_edt: nx=%d ny=%d nz=%d, every extent must be in [1, %d] and the volume at most 2^31 - 1 voxels", nx, ny, nz,
-                    D3F_EDT_MAX_EXTENT);
+    if (const int rc = check_extents("volume_edt", nx, ny, nz)) return rc;
     if (max_d2 < 0) return fail(D3F_ERR_INVALID_ARG, "volume_edt: max_d2=%d is negative (0: no cap)", max_d2);
-    if (out_dist && (!(step > 0.0f) || step * 0.0f != 0.0f)) return fail(D3F_ERR_INVALID_ARG, "volume_edt: step must be > 0 and finite with out_dist");
+    if (out_dist && !positive_finite(step)) return fail(D3F_ERR_INVALID_ARG, "volume_edt: step must be > 0 and finite with out_dist");
     if (!aligned(out_d2, 4) || !aligned(out_nearest, 4) || !aligned(out_dist, 4))
         return fail(D3F_ERR_BAD_LAYOUT, "volume_edt: out_d2 / out_nearest / out_dist must be 4-byte aligned");
-    const int64_t need = d3f_volume_edt_workspace_bytes(nx, ny, nz);
-    if (!workspace || workspace_bytes < need) return fail(D3F_ERR_WORKSPACE, "volume_edt: needs %lld workspace bytes", (long long)need);
-    if (!aligned(workspace, 4)) return fail(D3F_ERR_BAD_LAYOUT, "volume_edt: workspace must be 4-byte aligned");
+    if (const int rc = check_workspace("volume_edt", workspace, workspace_bytes, d3f_volume_edt_workspace_bytes(nx, ny, nz), 4)) return rc;
     hipError_t e = d3f::launch_volume_edt(site, nx, ny, nz, step, max_d2 > 0 ? max_d2 : 0x7fffffff, out_d2, out_nearest, out_dist, workspace,
                                           static_cast<hipStream_t>(stream));
     return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_edt launch");
@@ -848,53 +890,43 @@ int64_t d3f_volume_components_workspace_bytes(int32_t nx, int32_t ny, int32_t nz
     return edt_shape_ok(nx, ny, nz) ? d3f::ccl_workspace_bytes((int64_t)nx * ny * nz) : 0;
 }
 
+// both forms: every pair of neighbouring sites is joined, or (linked) only the pairs whose bit of links is set (d3f_volume_links)
+static int components_impl(const char *who, bool linked, const uint8_t *site, const uint16_t *links, int32_t nx, int32_t ny, int32_t nz, int32_t connectivity,
+                           int32_t min_voxels, int32_t *out_label, int32_t *out_count, int32_t *out_stats, int32_t stats_capacity, void *workspace,
+                           int64_t workspace_bytes, void *stream)
+{
+    if (!site) return fail(D3F_ERR_INVALID_ARG, "%s: site is NULL", who);
+    if (linked && !links) return fail(D3F_ERR_INVALID_ARG, "%s: links is NULL", who);
+    if (!out_label || !out_count) return fail(D3F_ERR_INVALID_ARG, "%s: out_label or out_count is NULL", who);
+    if (const int rc = check_connectivity(who, connectivity)) return rc;
+    if (min_voxels < 1) return fail(D3F_ERR_INVALID_ARG, "%s: min_voxels=%d, must be >= 1", who, min_voxels);
+    if (stats_capacity < 0) return fail(D3F_ERR_INVALID_ARG, "%s: stats_capacity=%d is negative", who, stats_capacity);
+    if (stats_capacity > 0 && !out_stats) return fail(D3F_ERR_INVALID_ARG, "%s: out_stats is NULL with stats_capacity=%d", who, stats_capacity);
+    if (const int rc = check_extents(who, nx, ny, nz)) return rc;
+    if (!aligned(links, 2)) return fail(D3F_ERR_BAD_LAYOUT, "%s: links must be 2-byte aligned", who);
+    if (!aligned(out_label, 4) || !aligned(out_count, 4) || !aligned(out_stats, 4))
+        return fail(D3F_ERR_BAD_LAYOUT, "%s: out_label / out_count / out_stats must be 4-byte aligned", who);
+    if (const int rc = check_workspace(who, workspace, workspace_bytes, d3f_volume_components_workspace_bytes(nx, ny, nz), 4)) return rc;
+    int32_t *stats = stats_capacity > 0 ? out_stats : nullptr;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = linked ? d3f::launch_volume_components_linked(site, links, nx, ny, nz, connectivity, min_voxels, out_label, out_count, stats, stats_capacity, workspace, s)
+                          : d3f::launch_volume_components(site, nx, ny, nz, connectivity, min_voxels, out_label, out_count, stats, stats_capacity, workspace, s);
+    return e == hipSuccess ? D3F_OK : fail(D3F_ERR_HIP, "%s launch: %s", who, hipGetErrorString(e));
+}
+
 int d3f_volume_components(const uint8_t *site, int32_t nx, int32_t ny, int32_t nz, int32_t connectivity, int32_t min_voxels, int32_t *out_label,
                           int32_t *out_count, int32_t *out_stats, int32_t stats_capacity, void *workspace, int64_t workspace_bytes, void *stream)
 {
-    if (!site) return fail(D3F_ERR_INVALID_ARG, "volume_components: site is NULL");
-    if (!out_label || !out_count) return fail(D3F_ERR_INVALID_ARG, "volume_components: out_label or out_count is NULL");
-    if (connectivity != 6 && connectivity != 18 && connectivity != 26)
-        return fail(D3F_ERR_INVALID_ARG, "volume_components: connectivity=%d, must be 6, 18 or 26", connectivity);
-    if (min_voxels < 1) return fail(D3F_ERR_INVALID_ARG, "volume_components: min_voxels=%d, must be >= 1", min_voxels);
-    if (stats_capacity < 0) return fail(D3F_ERR_INVALID_ARG, "volume_components: stats_capacity=%d is negative", stats_capacity);
-    if (stats_capacity > 0 && !out_stats) return fail(D3F_ERR_INVALID_ARG, "volume_components: out_stats is NULL with stats_capacity=%d", stats_capacity);
-    if (!edt_shape_ok(nx, ny, nz))
-        return fail(D3F_ERR_BAD_SHAPE, "volume_components: nx=%d ny=%d nz=%d, every extent must be in [1, %d] and the volume at most 2^31 - 1 voxels", nx,
-                    ny, nz, D3F_EDT_MAX_EXTENT);
-    if (!aligned(out_label, 4) || !aligned(out_count, 4) || !aligned(out_stats, 4))
-        return fail(D3F_ERR_BAD_LAYOUT, "volume_components: out_label / out_count / out_stats must be 4-byte aligned");
-    const int64_t need = d3f_volume_components_workspace_bytes(nx, ny, nz);
-    if (!workspace || workspace_bytes < need) return fail(D3F_ERR_WORKSPACE, "volume_components: needs %lld workspace bytes", (long long)need);
-    if (!aligned(workspace, 4)) return fail(D3F_ERR_BAD_LAYOUT, "volume_components: workspace must be 4-byte aligned");
-    hipError_t e = d3f::launch_volume_components(site, nx, ny, nz, connectivity, min_voxels, out_label, out_count, stats_capacity > 0 ? out_stats : nullptr,
-                                                 stats_capacity, workspace, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_components launch");
+    return components_impl("volume_components", false, site, nullptr, nx, ny, nz, connectivity, min_voxels, out_label, out_count, out_stats, stats_capacity,
+                           workspace, workspace_bytes, stream);
 }
 
 int d3f_volume_components_linked(const uint8_t *site, const uint16_t *links, int32_t nx, int32_t ny, int32_t nz, int32_t connectivity, int32_t min_voxels,
                                  int32_t *out_label, int32_t *out_count, int32_t *out_stats, int32_t stats_capacity, void *workspace, int64_t workspace_bytes,
                                  void *stream)
 {
-    if (!site || !links) return fail(D3F_ERR_INVALID_ARG, "volume_components_linked: site or links is NULL");
-    if (!out_label || !out_count) return fail(D3F_ERR_INVALID_ARG, "volume_components_linked: out_label or out_count is NULL");
-    if (connectivity != 6 && connectivity != 18 && connectivity != 26)
-        return fail(D3F_ERR_INVALID_ARG, "volume_components_linked: connectivity=%d, must be 6, 18 or 26", connectivity);
-    if (min_voxels < 1) return fail(D3F_ERR_INVALID_ARG, "volume_components_linked: min_voxels=%d, must be >= 1", min_voxels);
-    if (stats_capacity < 0) return fail(D3F_ERR_INVALID_ARG, "volume_components_linked: stats_capacity=%d is negative", stats_capacity);
-    if (stats_capacity > 0 && !out_stats)
-        return fail(D3F_ERR_INVALID_ARG, "volume_components_linked: out_stats is NULL with stats_capacity=%d", stats_capacity);
-    if (!edt_shape_ok(nx, ny, nz))
-        return fail(D3F_ERR_BAD_SHAPE, "volume_components_linked: nx=%d ny=%d nz=%d, every extent must be in [1, %d] and the volume at most 2^31 - 1 voxels",
-                    nx, ny, nz, D3F_EDT_MAX_EXTENT);
-    if (!aligned(links, 2)) return fail(D3F_ERR_BAD_LAYOUT, "volume_components_linked: links must be 2-byte aligned");
-    if (!aligned(out_label, 4) || !aligned(out_count, 4) || !aligned(out_stats, 4))
-        return fail(D3F_ERR_BAD_LAYOUT, "volume_components_linked: out_label / out_count / out_stats must be 4-byte aligned");
-    const int64_t need = d3f_volume_components_workspace_bytes(nx, ny, nz);
-    if (!workspace || workspace_bytes < need) return fail(D3F_ERR_WORKSPACE, "volume_components_linked: needs %lld workspace bytes", (long long)need);
-    if (!aligned(workspace, 4)) return fail(D3F_ERR_BAD_LAYOUT, "volume_components_linked: workspace must be 4-byte aligned");
-    hipError_t e = d3f::launch_volume_components_linked(site, links, nx, ny, nz, connectivity, min_voxels, out_label, out_count,
-                                                        stats_capacity > 0 ? out_stats : nullptr, stats_capacity, workspace, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_components_linked launch");
+    return components_impl("volume_components_linked", true, site, links, nx, ny, nz, connectivity, min_voxels, out_label, out_count, out_stats, stats_capacity,
+                           workspace, workspace_bytes, stream);
 }
 
 // ---- descriptor-gated links between neighbouring voxels (parts_kernels.hip) ----
@@ -904,21 +936,16 @@ int d3f_volume_links(const uint8_t *site, const uint8_t *valid, const int32_t *s
     if (!site || !set || !out_links) return fail(D3F_ERR_INVALID_ARG, "volume_links: site, set or out_links is NULL");
     if (!set->data) return fail(D3F_ERR_INVALID_ARG, "volume_links: set->data is NULL");
     if (rule != D3F_LINK_L2 && rule != D3F_LINK_COSINE && rule != D3F_LINK_ARGMAX) return fail(D3F_ERR_INVALID_ARG, "volume_links: unknown rule %d", rule);
-    if (connectivity != 6 && connectivity != 18 && connectivity != 26)
-        return fail(D3F_ERR_INVALID_ARG, "volume_links: connectivity=%d, must be 6, 18 or 26", connectivity);
+    if (const int rc = check_connectivity("volume_links", connectivity)) return rc;
     if (threshold != threshold) return fail(D3F_ERR_INVALID_ARG, "volume_links: threshold is NaN (+Inf accepts every pair of finite rows under D3F_LINK_L2)");
     if (rule == D3F_LINK_COSINE && !(threshold >= 0.0f && threshold <= 1.0f))
         return fail(D3F_ERR_INVALID_ARG, "volume_links: threshold=%g, the cosine bound must lie in [0, 1]", (double)threshold);
-    if (!edt_shape_ok(nx, ny, nz))
-        return fail(D3F_ERR_BAD_SHAPE, "volume_links: nx=%d ny=%d nz=%d, every extent must be in [1, %d] and the volume at most 2^31 - 1 voxels", nx, ny, nz,
-                    D3F_EDT_MAX_EXTENT);
-    if (set->C < 1 || set->C > D3F_VOLUME_MAX_CHANNELS) return fail(D3F_ERR_BAD_SHAPE, "volume_links: C=%d outside [1,%d]", set->C, D3F_VOLUME_MAX_CHANNELS);
-    if (set->stride_voxel < set->C) return fail(D3F_ERR_BAD_LAYOUT, "volume_links: stride_voxel=%lld < C=%d", (long long)set->stride_voxel, set->C);
-    if (!aligned(slot, 4) || !aligned(set->data, 4) || !aligned(out_links, 2))
-        return fail(D3F_ERR_BAD_LAYOUT, "volume_links: slot / data must be 4-byte aligned, out_links 2-byte aligned");
-    const bool vec = set->C % 4 == 0 && set->stride_voxel % 4 == 0 && aligned(set->data, 16);
-    hipError_t e = d3f::launch_volume_links(site, valid, slot, nx, ny, nz, set->data, set->C, set->stride_voxel, vec, rule, threshold, connectivity, out_links,
-                                            static_cast<hipStream_t>(stream));
+    if (const int rc = check_extents("volume_links", nx, ny, nz)) return rc;
+    if (const int rc = check_set_shape("volume_links", 0, *set)) return rc;
+    if (const int rc = check_set_layout("volume_links", 0, *set)) return rc;
+    if (!aligned(slot, 4) || !aligned(out_links, 2)) return fail(D3F_ERR_BAD_LAYOUT, "volume_links: slot must be 4-byte aligned, out_links 2-byte aligned");
+    hipError_t e = d3f::launch_volume_links(site, valid, slot, nx, ny, nz, set->data, set->C, set->stride_voxel, set_reads_vectors(*set), rule, threshold,
+                                            connectivity, out_links, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_links launch");
 }
 
@@ -932,17 +959,14 @@ int d3f_volume_flow(const uint8_t *site_a, const int32_t *slot_a, const d3f_volu
     if (!out_target || !out_cost) return fail(D3F_ERR_INVALID_ARG, "volume_flow: out_target or out_cost is NULL");
     if (radius < 1 || radius > D3F_FLOW_MAX_RADIUS) return fail(D3F_ERR_INVALID_ARG, "volume_flow: radius=%d outside [1,%d]", radius, D3F_FLOW_MAX_RADIUS);
     if (max_cost2 != max_cost2) return fail(D3F_ERR_INVALID_ARG, "volume_flow: max_cost2 is NaN (+Inf means no threshold)");
-    if (!edt_shape_ok(nx, ny, nz))
-        return fail(D3F_ERR_BAD_SHAPE, "volume_flow: nx=%d ny=%d nz=%d, every extent must be in [1, %d] and the volume at most 2^31 - 1 voxels", nx, ny, nz,
-                    D3F_EDT_MAX_EXTENT);
-    if (set_a->C < 1 || set_a->C > D3F_VOLUME_MAX_CHANNELS) return fail(D3F_ERR_BAD_SHAPE, "volume_flow: C=%d outside [1,%d]", set_a->C, D3F_VOLUME_MAX_CHANNELS);
+    if (const int rc = check_extents("volume_flow", nx, ny, nz)) return rc;
+    if (const int rc = check_set_shape("volume_flow", 0, *set_a)) return rc;             // set 0: set_a, set 1: set_b
     if (set_b->C != set_a->C) return fail(D3F_ERR_BAD_SHAPE, "volume_flow: C=%d of set_a, C=%d of set_b: the sets must have the same width", set_a->C, set_b->C);
-    if (set_a->stride_voxel < set_a->C || set_b->stride_voxel < set_b->C)
-        return fail(D3F_ERR_BAD_LAYOUT, "volume_flow: stride_voxel=%lld / %lld < C=%d", (long long)set_a->stride_voxel, (long long)set_b->stride_voxel, set_a->C);
-    if (!aligned(slot_a, 4) || !aligned(slot_b, 4) || !aligned(set_a->data, 4) || !aligned(set_b->data, 4) || !aligned(out_target, 4) || !aligned(out_cost, 4) ||
-        !aligned(out_axis_cost, 4))
-        return fail(D3F_ERR_BAD_LAYOUT, "volume_flow: slots, data and outputs must be 4-byte aligned");
-    const bool vec = set_a->C % 4 == 0 && set_a->stride_voxel % 4 == 0 && set_b->stride_voxel % 4 == 0 && aligned(set_a->data, 16) && aligned(set_b->data, 16);
+    if (const int rc = check_set_layout("volume_flow", 0, *set_a)) return rc;
+    if (const int rc = check_set_layout("volume_flow", 1, *set_b)) return rc;
+    if (!aligned(slot_a, 4) || !aligned(slot_b, 4) || !aligned(out_target, 4) || !aligned(out_cost, 4) || !aligned(out_axis_cost, 4))
+        return fail(D3F_ERR_BAD_LAYOUT, "volume_flow: slots and outputs must be 4-byte aligned");
+    const bool vec = set_reads_vectors(*set_a) && set_reads_vectors(*set_b);                // (one width: checked above)
     hipError_t e = d3f::launch_volume_flow(site_a, slot_a, set_a->data, set_a->stride_voxel, site_b, slot_b, set_b->data, set_b->stride_voxel, set_a->C, vec, nx,
                                            ny, nz, radius, max_cost2, out_target, out_cost, out_axis_cost, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_flow launch");
@@ -974,14 +998,11 @@ int d3f_volume_pool(const int32_t *label, int32_t nx, int32_t ny, int32_t nz, in
         if (modes[s] != D3F_POOL_MEAN && modes[s] != D3F_POOL_VOTES) return fail(D3F_ERR_INVALID_ARG, "volume_pool: set %d: unknown mode %d", s, modes[s]);
     }
     if (member_capacity < 0) return fail(D3F_ERR_INVALID_ARG, "volume_pool: member_capacity=%lld is negative", (long long)member_capacity);
-    if (!edt_shape_ok(nx, ny, nz))
-        return fail(D3F_ERR_BAD_SHAPE, "volume_pool: nx=%d ny=%d nz=%d, every extent must be in [1, %d] and the volume at most 2^31 - 1 voxels", nx, ny, nz,
-                    D3F_EDT_MAX_EXTENT);
+    if (const int rc = check_extents("volume_pool", nx, ny, nz)) return rc;
     if (!pool_shape_ok(nx, ny, nz, K)) return fail(D3F_ERR_BAD_SHAPE, "volume_pool: K=%d exceeds the %lld voxels", K, (long long)nx * ny * nz);
     int64_t mean_channels = 0;
     for (int s = 0; s < n_sets; ++s) {
-        if (sets[s].C < 1 || sets[s].C > D3F_VOLUME_MAX_CHANNELS)
-            return fail(D3F_ERR_BAD_SHAPE, "volume_pool: set %d: C=%d outside [1,%d]", s, sets[s].C, D3F_VOLUME_MAX_CHANNELS);
+        if (const int rc = check_set_shape("volume_pool", s, sets[s])) return rc;
         if (modes[s] == D3F_POOL_VOTES && sets[s].C > D3F_POOL_MAX_VOTE_CHANNELS)
             return fail(D3F_ERR_BAD_SHAPE, "volume_pool: set %d: votes over C=%d channels, more than %d", s, sets[s].C, D3F_POOL_MAX_VOTE_CHANNELS);
         if (modes[s] == D3F_POOL_MEAN) mean_channels += sets[s].C;
@@ -989,14 +1010,11 @@ int d3f_volume_pool(const int32_t *label, int32_t nx, int32_t ny, int32_t nz, in
     if (!aligned(label, 4) || !aligned(slot, 4) || !aligned(out_members, 8) || !aligned(out_count, 4) || !aligned(out_moments, 8))
         return fail(D3F_ERR_BAD_LAYOUT, "volume_pool: label / slot / out_members / out_count / out_moments must be aligned to their element size");
     for (int s = 0; s < n_sets; ++s) {
-        if (sets[s].stride_voxel < sets[s].C)
-            return fail(D3F_ERR_BAD_LAYOUT, "volume_pool: set %d: stride_voxel=%lld < C=%d", s, (long long)sets[s].stride_voxel, sets[s].C);
-        if (!aligned(sets[s].data, 4) || !aligned(sets[s].fill, 4) || !aligned(out_rows[s], 4))
-            return fail(D3F_ERR_BAD_LAYOUT, "volume_pool: set %d: data / fill / out_rows must be 4-byte aligned", s);
+        if (const int rc = check_set_layout("volume_pool", s, sets[s])) return rc;
+        if (!aligned(sets[s].fill, 4) || !aligned(out_rows[s], 4))
+            return fail(D3F_ERR_BAD_LAYOUT, "volume_pool: set %d: fill / out_rows must be 4-byte aligned", s);
     }
-    const int64_t need = d3f_volume_pool_workspace_bytes(nx, ny, nz, K, member_capacity, mean_channels);
-    if (!workspace || workspace_bytes < need) return fail(D3F_ERR_WORKSPACE, "volume_pool: needs %lld workspace bytes", (long long)need);
-    if (!aligned(workspace, 8)) return fail(D3F_ERR_BAD_LAYOUT, "volume_pool: workspace must be 8-byte aligned");
+    if (const int rc = check_workspace("volume_pool", workspace, workspace_bytes, d3f_volume_pool_workspace_bytes(nx, ny, nz, K, member_capacity, mean_channels), 8)) return rc;
     hipError_t e;
     if (K == 0) {
         e = d3f::launch_pool_nothing(out_members, static_cast<hipStream_t>(stream));
@@ -1040,17 +1058,13 @@ int d3f_part_motion(const int32_t *label, int32_t K, int32_t nx, int32_t ny, int
     if (!(tau2 > 0.0 && tau2 < __builtin_huge_val())) return fail(D3F_ERR_INVALID_ARG, "part_motion: tau2=%g, the squared inlier radius must be finite and > 0", tau2);
     if (min_pairs < 3) return fail(D3F_ERR_INVALID_ARG, "part_motion: min_pairs=%d, a rigid motion needs at least 3 pairs", min_pairs);
     if (member_capacity < 0) return fail(D3F_ERR_INVALID_ARG, "part_motion: member_capacity=%lld is negative", (long long)member_capacity);
-    if (!edt_shape_ok(nx, ny, nz))
-        return fail(D3F_ERR_BAD_SHAPE, "part_motion: nx=%d ny=%d nz=%d, every extent must be in [1, %d] and the volume at most 2^31 - 1 voxels", nx, ny, nz,
-                    D3F_EDT_MAX_EXTENT);
+    if (const int rc = check_extents("part_motion", nx, ny, nz)) return rc;
     if (!pool_shape_ok(nx, ny, nz, K)) return fail(D3F_ERR_BAD_SHAPE, "part_motion: K=%d exceeds the %lld voxels", K, (long long)nx * ny * nz);
     if (!aligned(label, 4) || !aligned(target, 4) || !aligned(offset, 8) || !aligned(ref, 4) || !aligned(out_members, 8) || !aligned(out_pairs, 4) ||
         !aligned(out_pose, 8) || !aligned(out_inliers, 4) || !aligned(out_rmse, 8) || !aligned(out_status, 4) || !aligned(out_fits, 4) ||
         !aligned(out_residual2, 8) || !aligned(out_sums, 8))
         return fail(D3F_ERR_BAD_LAYOUT, "part_motion: every pointer must be aligned to its element size");
-    const int64_t need = d3f_part_motion_workspace_bytes(nx, ny, nz, K, member_capacity);
-    if (!workspace || workspace_bytes < need) return fail(D3F_ERR_WORKSPACE, "part_motion: needs %lld workspace bytes", (long long)need);
-    if (!aligned(workspace, 8)) return fail(D3F_ERR_BAD_LAYOUT, "part_motion: workspace must be 8-byte aligned");
+    if (const int rc = check_workspace("part_motion", workspace, workspace_bytes, d3f_part_motion_workspace_bytes(nx, ny, nz, K, member_capacity), 8)) return rc;
     hipError_t e;
     if (K == 0) {
         e = d3f::launch_pool_nothing(out_members, static_cast<hipStream_t>(stream));
@@ -1083,12 +1097,12 @@ int d3f_part_motion(const int32_t *label, int32_t K, int32_t nx, int32_t ny, int
 }
 
 // ---- cost-to-go through free space (geodesic_kernels.hip) ----
-static const char *geo_weights_bad(int32_t connectivity, const int32_t *w)
+static int check_geo_weights(const char *who, int32_t connectivity, const int32_t *w)
 {
-    if (connectivity != 6 && connectivity != 18 && connectivity != 26) return "connectivity must be 6, 18 or 26";
-    if (!w) return "w is NULL";
-    if (!(1 <= w[0] && w[0] <= w[1] && w[1] <= w[2] && w[2] <= 255)) return "weights must satisfy 1 <= w1 <= w2 <= w3 <= 255";
-    return nullptr;
+    if (const int rc = check_connectivity(who, connectivity)) return rc;
+    if (!w) return fail(D3F_ERR_INVALID_ARG, "%s: w is NULL", who);
+    if (!(1 <= w[0] && w[0] <= w[1] && w[1] <= w[2] && w[2] <= 255)) return fail(D3F_ERR_INVALID_ARG, "%s: weights must satisfy 1 <= w1 <= w2 <= w3 <= 255", who);
+    return D3F_OK;
 }
 
 int64_t d3f_volume_geodesic_workspace_bytes(int32_t nx, int32_t ny, int32_t nz)
@@ -1102,13 +1116,9 @@ int d3f_volume_geodesic_init(const uint8_t *free, int32_t nx, int32_t ny, int32_
     if (!free || !out_cost) return fail(D3F_ERR_INVALID_ARG, "volume_geodesic_init: free or out_cost is NULL");
     if (n_seeds < 0) return fail(D3F_ERR_INVALID_ARG, "volume_geodesic_init: n_seeds=%lld is negative", (long long)n_seeds);
     if (n_seeds > 0 && !seeds) return fail(D3F_ERR_INVALID_ARG, "volume_geodesic_init: seeds is NULL with n_seeds=%lld", (long long)n_seeds);
-    if (!edt_shape_ok(nx, ny, nz))
-        return fail(D3F_ERR_BAD_SHAPE, "volume_geodesic_init: nx=%d ny=%d nz=%d, every extent must be in [1, %d] and the volume at most 2^31 - 1 voxels", nx,
-                    ny, nz, D3F_EDT_MAX_EXTENT);
+    if (const int rc = check_extents("volume_geodesic_init", nx, ny, nz)) return rc;
     if (!aligned(seeds, 4) || !aligned(out_cost, 4)) return fail(D3F_ERR_BAD_LAYOUT, "volume_geodesic_init: seeds / out_cost must be 4-byte aligned");
-    const int64_t need = d3f_volume_geodesic_workspace_bytes(nx, ny, nz);
-    if (!workspace || workspace_bytes < need) return fail(D3F_ERR_WORKSPACE, "volume_geodesic_init: needs %lld workspace bytes", (long long)need);
-    if (!aligned(workspace, 4)) return fail(D3F_ERR_BAD_LAYOUT, "volume_geodesic_init: workspace must be 4-byte aligned");
+    if (const int rc = check_workspace("volume_geodesic_init", workspace, workspace_bytes, d3f_volume_geodesic_workspace_bytes(nx, ny, nz), 4)) return rc;
     hipError_t e = d3f::launch_geodesic_init(free, nx, ny, nz, seeds, n_seeds, out_cost, workspace, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_geodesic_init launch");
 }
@@ -1117,17 +1127,13 @@ int d3f_volume_geodesic_relax(const uint8_t *free, const int32_t *penalty, int32
                               int32_t max_cost, int32_t rounds, int32_t *cost, int32_t *out_pending, void *workspace, int64_t workspace_bytes, void *stream)
 {
     if (!free || !cost || !out_pending) return fail(D3F_ERR_INVALID_ARG, "volume_geodesic_relax: free, cost or out_pending is NULL");
-    if (const char *bad = geo_weights_bad(connectivity, w)) return fail(D3F_ERR_INVALID_ARG, "volume_geodesic_relax: %s", bad);
+    if (const int rc = check_geo_weights("volume_geodesic_relax", connectivity, w)) return rc;
     if (max_cost < 1 || max_cost > 0x7ffffffe) return fail(D3F_ERR_INVALID_ARG, "volume_geodesic_relax: max_cost=%d outside [1, INT32_MAX - 1]", max_cost);
     if (rounds < 1) return fail(D3F_ERR_INVALID_ARG, "volume_geodesic_relax: rounds=%d, must be >= 1", rounds);
-    if (!edt_shape_ok(nx, ny, nz))
-        return fail(D3F_ERR_BAD_SHAPE, "volume_geodesic_relax: nx=%d ny=%d nz=%d, every extent must be in [1, %d] and the volume at most 2^31 - 1 voxels", nx,
-                    ny, nz, D3F_EDT_MAX_EXTENT);
+    if (const int rc = check_extents("volume_geodesic_relax", nx, ny, nz)) return rc;
     if (!aligned(penalty, 4) || !aligned(cost, 4) || !aligned(out_pending, 4))
         return fail(D3F_ERR_BAD_LAYOUT, "volume_geodesic_relax: penalty / cost / out_pending must be 4-byte aligned");
-    const int64_t need = d3f_volume_geodesic_workspace_bytes(nx, ny, nz);
-    if (!workspace || workspace_bytes < need) return fail(D3F_ERR_WORKSPACE, "volume_geodesic_relax: needs %lld workspace bytes", (long long)need);
-    if (!aligned(workspace, 4)) return fail(D3F_ERR_BAD_LAYOUT, "volume_geodesic_relax: workspace must be 4-byte aligned");
+    if (const int rc = check_workspace("volume_geodesic_relax", workspace, workspace_bytes, d3f_volume_geodesic_workspace_bytes(nx, ny, nz), 4)) return rc;
     hipError_t e = d3f::launch_geodesic_relax(free, penalty, nx, ny, nz, connectivity, w, max_cost, rounds, cost, out_pending, workspace,
                                               static_cast<hipStream_t>(stream));
     return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_geodesic_relax launch");
@@ -1138,11 +1144,9 @@ int d3f_volume_geodesic_finish(const uint8_t *free, const int32_t *penalty, int3
 {
     if (!free || !cost) return fail(D3F_ERR_INVALID_ARG, "volume_geodesic_finish: free or cost is NULL");
     if (!out_next && !out_dist) return fail(D3F_ERR_INVALID_ARG, "volume_geodesic_finish: out_next and out_dist are both NULL");
-    if (const char *bad = geo_weights_bad(connectivity, w)) return fail(D3F_ERR_INVALID_ARG, "volume_geodesic_finish: %s", bad);
-    if (out_dist && (!(step > 0.0f) || step * 0.0f != 0.0f)) return fail(D3F_ERR_INVALID_ARG, "volume_geodesic_finish: step must be > 0 and finite with out_dist");
-    if (!edt_shape_ok(nx, ny, nz))
-        return fail(D3F_ERR_BAD_SHAPE, "volume_geodesic_finish: nx=%d ny=%d nz=%d, every extent must be in [1, %d] and the volume at most 2^31 - 1 voxels", nx,
-                    ny, nz, D3F_EDT_MAX_EXTENT);
+    if (const int rc = check_geo_weights("volume_geodesic_finish", connectivity, w)) return rc;
+    if (out_dist && !positive_finite(step)) return fail(D3F_ERR_INVALID_ARG, "volume_geodesic_finish: step must be > 0 and finite with out_dist");
+    if (const int rc = check_extents("volume_geodesic_finish", nx, ny, nz)) return rc;
     if (!aligned(penalty, 4) || !aligned(cost, 4) || !aligned(out_next, 4) || !aligned(out_dist, 4))
         return fail(D3F_ERR_BAD_LAYOUT, "volume_geodesic_finish: penalty / cost / out_next / out_dist must be 4-byte aligned");
     hipError_t e = d3f::launch_geodesic_finish(free, penalty, nx, ny, nz, connectivity, w, step, cost, out_next, out_dist, static_cast<hipStream_t>(stream));
@@ -1157,7 +1161,7 @@ int d3f_volume_follow(const int32_t *next, int64_t n_voxels, const int32_t *star
     if (n > 0 && (!next || !starts || !out_voxels || !out_length || !out_reached))
         return fail(D3F_ERR_INVALID_ARG, "volume_follow: next, starts, out_voxels, out_length or out_reached is NULL with n=%lld", (long long)n);
     if (n_voxels < 1 || n_voxels > 0x7fffffffLL) return fail(D3F_ERR_BAD_SHAPE, "volume_follow: n_voxels=%lld outside [1, 2^31 - 1]", (long long)n_voxels);
-    if ((n + d3f::kBlock - 1) / d3f::kBlock > 0x7fffffffLL) return fail(D3F_ERR_BAD_SHAPE, "volume_follow: n=%lld too large for one launch", (long long)n);
+    if (const int rc = check_launch_blocks("volume_follow", n, d3f::kBlock)) return rc;
     if (!aligned(next, 4) || !aligned(starts, 4) || !aligned(out_voxels, 4) || !aligned(out_length, 4))
         return fail(D3F_ERR_BAD_LAYOUT, "volume_follow: next / starts / out_voxels / out_length must be 4-byte aligned");
     if (n == 0) return D3F_OK;
@@ -1175,10 +1179,8 @@ int d3f_volume_segments(const uint8_t *free, const int32_t *value, int32_t nx, i
     if (!out_clear && !out_last && !out_blocked && !out_min_value && !out_min_voxel)
         return fail(D3F_ERR_INVALID_ARG, "volume_segments: every output is NULL");
     if (!value && (out_min_value || out_min_voxel)) return fail(D3F_ERR_INVALID_ARG, "volume_segments: out_min_value / out_min_voxel need value");
-    if (!edt_shape_ok(nx, ny, nz))
-        return fail(D3F_ERR_BAD_SHAPE, "volume_segments: nx=%d ny=%d nz=%d, every extent must be in [1, %d] and the volume at most 2^31 - 1 voxels", nx, ny, nz,
-                    D3F_EDT_MAX_EXTENT);
-    if ((n + d3f::kBlock - 1) / d3f::kBlock > 0x7fffffffLL) return fail(D3F_ERR_BAD_SHAPE, "volume_segments: n=%lld too large for one launch", (long long)n);
+    if (const int rc = check_extents("volume_segments", nx, ny, nz)) return rc;
+    if (const int rc = check_launch_blocks("volume_segments", n, d3f::kBlock)) return rc;
     if (!aligned(value, 4) || !aligned(a, 4) || !aligned(b, 4) || !aligned(out_last, 4) || !aligned(out_blocked, 4) || !aligned(out_min_value, 4) ||
         !aligned(out_min_voxel, 4))
         return fail(D3F_ERR_BAD_LAYOUT, "volume_segments: value / a / b / out_last / out_blocked / out_min_value / out_min_voxel must be 4-byte aligned");
@@ -1198,10 +1200,8 @@ int d3f_path_shorten(const uint8_t *free, int32_t nx, int32_t ny, int32_t nz, co
     if (n > 0 && (!free || !voxels || !length)) return fail(D3F_ERR_INVALID_ARG, "path_shorten: free, voxels or length is NULL with n=%lld", (long long)n);
     if (!out_count) return fail(D3F_ERR_INVALID_ARG, "path_shorten: out_count is NULL");
     if (!out_index && !out_voxels) return fail(D3F_ERR_INVALID_ARG, "path_shorten: out_index and out_voxels are both NULL");
-    if (!edt_shape_ok(nx, ny, nz))
-        return fail(D3F_ERR_BAD_SHAPE, "path_shorten: nx=%d ny=%d nz=%d, every extent must be in [1, %d] and the volume at most 2^31 - 1 voxels", nx, ny, nz,
-                    D3F_EDT_MAX_EXTENT);
-    if ((n + 3) / 4 > 0x7fffffffLL) return fail(D3F_ERR_BAD_SHAPE, "path_shorten: n=%lld too large for one launch", (long long)n);
+    if (const int rc = check_extents("path_shorten", nx, ny, nz)) return rc;
+    if (const int rc = check_launch_blocks("path_shorten", n, 4)) return rc;            // four rows to a workgroup (segment_kernels.hip)
     if (!aligned(voxels, 4) || !aligned(length, 4) || !aligned(out_index, 4) || !aligned(out_voxels, 4) || !aligned(out_count, 4))
         return fail(D3F_ERR_BAD_LAYOUT, "path_shorten: voxels / length / out_index / out_voxels / out_count must be 4-byte aligned");
     if (n == 0) return D3F_OK;
@@ -1223,9 +1223,7 @@ int d3f_volume_peaks(const int32_t *slot, const uint8_t *mask, int32_t nx, int32
     if (stride_row < K || out_stride < K)
         return fail(D3F_ERR_INVALID_ARG, "volume_peaks: stride_row=%lld out_stride=%lld, both must be >= K=%d", (long long)stride_row, (long long)out_stride, K);
     if (M > 0 && K > 0 && (!score || !out)) return fail(D3F_ERR_INVALID_ARG, "volume_peaks: score or out is NULL with M=%lld K=%d", (long long)M, K);
-    if (!edt_shape_ok(nx, ny, nz))
-        return fail(D3F_ERR_BAD_SHAPE, "volume_peaks: nx=%d ny=%d nz=%d, every extent must be in [1, %d] and the volume at most 2^31 - 1 voxels", nx, ny, nz,
-                    D3F_EDT_MAX_EXTENT);
+    if (const int rc = check_extents("volume_peaks", nx, ny, nz)) return rc;
     const int64_t n_voxels = (int64_t)nx * ny * nz;
     if (!slot && M != n_voxels) return fail(D3F_ERR_INVALID_ARG, "volume_peaks: M=%lld without slot, must equal nx*ny*nz=%lld", (long long)M, (long long)n_voxels);
     if (slot && M > n_voxels) return fail(D3F_ERR_INVALID_ARG, "volume_peaks: M=%lld rows for %lld voxels", (long long)M, (long long)n_voxels);
@@ -1255,7 +1253,6 @@ int d3f_volume_peaks(const int32_t *slot, const uint8_t *mask, int32_t nx, int32
 
 // ---- rigid alignment of point sets to the baked field (align_kernels.hip) ----
 static bool align_counts_ok(int64_t I, int64_t n) { return I >= 0 && n >= 0; }
-static bool finite_nonneg(double v) { return v >= 0.0 && v * 0.0 == 0.0; }
 
 int64_t d3f_volume_align_workspace_bytes(int64_t I, int64_t n)
 {
@@ -1534,8 +1531,8 @@ int d3f_volume_raycast(const d3f_volume *vol, const float *origins, const float 
 {
     const int rc = check_volume("volume_raycast", vol);
     if (rc != D3F_OK) return rc;
-    if (!(vol->step > 0.0f) || vol->step * 0.0f != 0.0f) return fail(D3F_ERR_INVALID_ARG, "volume_raycast: vol->step must be > 0 and finite");
-    if (!(march_step > 0.0f) || march_step * 0.0f != 0.0f) return fail(D3F_ERR_INVALID_ARG, "volume_raycast: march_step must be > 0 and finite");
+    if (!positive_finite(vol->step)) return fail(D3F_ERR_INVALID_ARG, "volume_raycast: vol->step must be > 0 and finite");
+    if (!positive_finite(march_step)) return fail(D3F_ERR_INVALID_ARG, "volume_raycast: march_step must be > 0 and finite");
     const double ex = vol->nx - 1, ey = vol->ny - 1, ez = vol->nz - 1;
     const double steps = ceil((double)vol->step * sqrt(ex * ex + ey * ey + ez * ez) / (double)march_step);
     if (!(steps <= (double)D3F_RAYCAST_MAX_STEPS))

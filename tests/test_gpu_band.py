@@ -162,6 +162,35 @@ def test_lookup_is_the_dense_fields_where_in_band(dev, name, channels):
     assert list(d) == ["dist", "valid_mask", "in_band"] and torch.equal(d["in_band"], full["in_band"])
 
 
+def test_output_rows_off_16_bytes_equal_the_aligned_call(dev):
+    """out_sets[s] 4-byte but not 16-byte aligned while the compacted rows are (C = 8 on a 3x4x5 volume, 64 points; the entry point called
+    directly): the set drops to scalar stores and gives the aligned call's rows bit for bit, and nothing beside them is written"""
+    import volume_cases as VC
+    shape, n, C = (3, 4, 5), 64, 8
+    vol = VC.make_volume(shape, (C,), 2, 0.1, True, (0,))
+    banded = field_of(vol, dev).to_band(float(np.abs(vol["dist"][vol["valid"]]).max()) * 0.75)
+    lib = _lib.load()
+    pts = torch.from_numpy(np.concatenate([VC.special_points(shape)[:8], VC.inside_points(shape, n - 8, 2)])).to(dev)
+    assert banded._sets["s0"].data_ptr() % 16 == 0 and banded._sets["s0"].stride(-2) == C and 0 < banded.band_voxels.numel()
+
+    def run(offset):
+        buf = torch.full((n * C + 8,), float("nan"), dtype=torch.float32, device=dev)
+        rows = buf[offset:offset + n * C].view(n, C)
+        dist = torch.empty(n, dtype=torch.float32, device=dev)
+        valid, in_band = torch.empty(n, dtype=torch.uint8, device=dev), torch.empty(n, dtype=torch.uint8, device=dev)
+        v, b = banded._volume(), banded._band_struct()
+        _lib.check(lib.d3f_band_sample(ctypes.byref(v), ctypes.byref(b), _lib.ptr(pts), n, banded._set_array(["s0"]), 1, _lib.ptr(dist), _lib.ptr(valid),
+                                       _lib.ptr(in_band), (ctypes.c_void_p * 1)(rows.data_ptr()), _lib.current_stream_handle(dev)))
+        torch.cuda.synchronize()
+        assert rows.data_ptr() % 16 == 4 * offset and bool(torch.isnan(buf[:offset]).all()) and bool(torch.isnan(buf[offset + n * C:]).all())
+        return rows.view(torch.int32), dist.view(torch.int32), valid, in_band
+
+    aligned, shifted = run(0), run(1)
+    assert all(torch.equal(a, b) for a, b in zip(aligned, shifted))
+    assert 0 < int(aligned[3].sum()) < n and not bool(torch.isnan(aligned[0].view(torch.float32)).any())
+    assert torch.equal(aligned[0].view(torch.float32), banded.eval(pts)["s0"])
+
+
 @pytest.mark.parametrize("name", ["large sphere holes band 1h", "9x8x10 plane holes band 1.5h"])
 def test_everything_kept_and_nothing_kept(dev, name):
     vol = BC.volume(name, (3, 68), (0,))

@@ -15,6 +15,8 @@ Mutants of the kernel and the assert that catches each:
                                         exactly and every row of such a point the fill row; the poisoned corners would give NaN
   fill row not applied (projected name) test_points_that_are_not_valid (non-zero fill rows) and test_end_to_end_bake (the -b row)
 """
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -143,6 +145,34 @@ def test_points_that_are_not_valid(dev):
             far = (np.asarray(VC.ORIGIN) + (np.asarray(shape) - 1) * VC.STEP).astype(np.float32)
             on_far = np.any(pts == far, axis=1) & np.all(np.isfinite(pts), axis=1)
             assert on_far.sum() >= 4 and ok[on_far & np.all(pts <= far, axis=1)].all()
+
+
+def test_output_rows_off_16_bytes_equal_the_aligned_call(dev):
+    """out_sets[s] 4-byte but not 16-byte aligned while the stored rows are (C = 8 on a 3x4x5 volume, 64 points; the entry point called
+    directly): the set drops to scalar stores and gives the aligned call's rows bit for bit, and nothing beside them is written"""
+    shape, n, C = (3, 4, 5), 64, 8
+    vol = VC.make_volume(shape, (C,), 2, 0.1, True, (0,))
+    f = field_of(vol, dev)
+    lib = _lib.load()
+    pts = torch.from_numpy(np.concatenate([VC.special_points(shape)[:8], VC.inside_points(shape, n - 8, 2)])).to(dev)
+    assert f._sets["s0"].data_ptr() % 16 == 0 and f._sets["s0"].stride(-2) == C
+
+    def run(offset):
+        buf = torch.full((n * C + 8,), float("nan"), dtype=torch.float32, device=dev)
+        rows = buf[offset:offset + n * C].view(n, C)
+        dist = torch.empty(n, dtype=torch.float32, device=dev)
+        valid = torch.empty(n, dtype=torch.uint8, device=dev)
+        v = f._volume()
+        _lib.check(lib.d3f_volume_sample(ctypes.byref(v), _lib.ptr(pts), n, f._set_array(["s0"]), 1, _lib.ptr(dist), _lib.ptr(valid),
+                                         (ctypes.c_void_p * 1)(rows.data_ptr()), _lib.current_stream_handle(dev)))
+        torch.cuda.synchronize()
+        assert rows.data_ptr() % 16 == 4 * offset and bool(torch.isnan(buf[:offset]).all()) and bool(torch.isnan(buf[offset + n * C:]).all())
+        return rows.view(torch.int32), dist.view(torch.int32), valid
+
+    aligned, shifted = run(0), run(1)
+    assert all(torch.equal(a, b) for a, b in zip(aligned, shifted))
+    assert 0 < int(aligned[2].sum()) < n and not bool(torch.isnan(aligned[0].view(torch.float32)).any())
+    assert torch.equal(aligned[0].view(torch.float32), f.eval(pts)["s0"])
 
 
 BACKWARD = [((), 1003), ((3,), 1003), ((16,), 63), ((18,), 1003), ((20,), 1), ((68,), 1003), ((67,), 63), ((384,), 1003), ((1024,), 63),
