@@ -430,6 +430,17 @@ __global__ __launch_bounds__(64) void align_step_kernel(AlignStep S)
 
 int64_t align_chunks(int64_t n) { return (n + kBlock - 1) / kBlock; }
 
+// one row of sums per instance and workgroup
+AlignLayout align_layout(int64_t I, int64_t n)
+{
+    AlignLayout L;
+    Carve c;
+    L.chunks = align_chunks(n);
+    L.partial = c.take(I * L.chunks * kAlignRow * (int64_t)sizeof(double), 8);
+    L.total = c.at;
+    return L;
+}
+
 hipError_t launch_align_centroid(const float *pts, const float *weights, int64_t I, int64_t n, float *out, hipStream_t s)
 {
     hipLaunchKernelGGL(align_centroid_kernel, dim3((unsigned)I), dim3(64), 0, s, pts, weights, n, out);

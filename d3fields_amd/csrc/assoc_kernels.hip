@@ -54,11 +54,15 @@ hipError_t launch_pcd_to_index(const double *pts, int64_t n, const double *lower
 // ---- hash set of int32 keys with two membership bits ----------------------------------------------------------------
 constexpr unsigned long long kEmptySlot = ~0ULL;       // a live slot is (uint32 key) << 2 | bits, i.e. < 2^34
 
-int64_t voxset_capacity(int64_t n1, int64_t n2)
+VoxsetLayout voxset_layout(int64_t n1, int64_t n2)
 {
-    int64_t cap = 1024;
-    while (cap < 2 * (n1 + n2)) cap <<= 1;              // load factor <= 0.5
-    return cap;
+    VoxsetLayout L;
+    Carve c;
+    L.cap = 1024;
+    while (L.cap < 2 * (n1 + n2)) L.cap <<= 1;          // load factor <= 0.5
+    L.table = c.take(L.cap * 8, 8);
+    L.total = c.at;
+    return L;
 }
 
 __global__ __launch_bounds__(kBlock) void voxset_clear_kernel(unsigned long long *__restrict__ table, int64_t cap,
@@ -116,8 +120,9 @@ __global__ __launch_bounds__(kBlock) void voxset_count_kernel(const unsigned lon
 hipError_t launch_voxset_iou(const int32_t *a, int64_t na, const int32_t *b, int64_t nb, int64_t *counts, void *workspace,
                              hipStream_t s)
 {
-    const int64_t cap = voxset_capacity(na, nb);
-    unsigned long long *table = static_cast<unsigned long long *>(workspace);
+    const VoxsetLayout L = voxset_layout(na, nb);
+    const int64_t cap = L.cap;
+    unsigned long long *table = static_cast<unsigned long long *>(ws_at(workspace, L.table));
     unsigned long long *cnt = reinterpret_cast<unsigned long long *>(counts);
     const unsigned gcap = (unsigned)((cap + kBlock - 1) / kBlock);
     hipLaunchKernelGGL(voxset_clear_kernel, dim3(gcap), dim3(kBlock), 0, s, table, cap, cnt);
@@ -201,18 +206,20 @@ struct VoxSlot {
 constexpr unsigned long long kVoxEmpty = ~0ULL;
 constexpr double kVoxFix = 1099511627776.0;     // 2^40
 
-int64_t voxmean_capacity(int64_t n)
+// min bound (3 doubles in a header of 64 bytes), table, per-workgroup slot counts + 1, the compacted slot list (at most n entries), back to back
+VoxmeanLayout voxmean_layout(int64_t n)
 {
-    int64_t cap = 1024;
-    while (cap < 2 * n) cap <<= 1;
-    return cap;
-}
-
-int64_t voxmean_workspace_bytes(int64_t n)
-{
-    const int64_t cap = voxmean_capacity(n);
-    // min bound (3 doubles + pad), table, per-workgroup slot counts, the compacted slot list (cap worst case is n entries)
-    return 64 + cap * (int64_t)sizeof(VoxSlot) + ((cap + kBlock - 1) / kBlock + 1) * 8 + n * 8;
+    VoxmeanLayout L;
+    Carve c;
+    L.cap = 1024;
+    while (L.cap < 2 * n) L.cap <<= 1;
+    L.blocks = (L.cap + kBlock - 1) / kBlock;
+    L.minb = c.take(64, 8);
+    L.table = c.take(L.cap * (int64_t)sizeof(VoxSlot), 8);
+    L.counts = c.take((L.blocks + 1) * 8, 8);
+    L.list = c.take(n * 8, 8);
+    L.total = c.at;
+    return L;
 }
 
 __global__ __launch_bounds__(1024) void voxmean_minbound_kernel(const double *__restrict__ pts, int64_t n, double *__restrict__ out)
@@ -350,13 +357,13 @@ __global__ __launch_bounds__(kBlock) void voxmean_write_kernel(const VoxSlot *__
 hipError_t launch_voxel_mean(const double *pts, const double *col, int64_t n, double vs, double *out_pts, double *out_col, int64_t *count,
                              void *workspace, hipStream_t s)
 {
-    const int64_t cap = voxmean_capacity(n);
-    char *ws = static_cast<char *>(workspace);
-    double *minb = reinterpret_cast<double *>(ws);
-    VoxSlot *table = reinterpret_cast<VoxSlot *>(ws + 64);
-    const unsigned gcap = (unsigned)((cap + kBlock - 1) / kBlock);
-    int64_t *counts = reinterpret_cast<int64_t *>(ws + 64 + cap * (int64_t)sizeof(VoxSlot));
-    int64_t *list = counts + gcap + 1;
+    const VoxmeanLayout L = voxmean_layout(n);
+    const int64_t cap = L.cap;
+    double *minb = static_cast<double *>(ws_at(workspace, L.minb));
+    VoxSlot *table = static_cast<VoxSlot *>(ws_at(workspace, L.table));
+    const unsigned gcap = (unsigned)L.blocks;
+    int64_t *counts = static_cast<int64_t *>(ws_at(workspace, L.counts));
+    int64_t *list = static_cast<int64_t *>(ws_at(workspace, L.list));
     hipLaunchKernelGGL(voxmean_minbound_kernel, dim3(1), dim3(1024), 0, s, pts, n, minb);
     hipLaunchKernelGGL(voxmean_clear_kernel, dim3(gcap), dim3(kBlock), 0, s, table, cap);
     hipLaunchKernelGGL(voxmean_insert_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, pts, col, n, vs, minb, table, cap);
@@ -435,10 +442,12 @@ __global__ __launch_bounds__(kBlock) void nonzero_write_kernel(const uint8_t *__
 }
 
 hipError_t launch_nonzero_pixels(const uint8_t *img, int H, int W, int64_t capacity, int32_t *out_rc, int64_t *count,
-                                 int64_t *block_counts, hipStream_t s)
+                                 void *workspace, hipStream_t s)
 {
     const int64_t npix = (int64_t)H * W;
-    const unsigned nb = (unsigned)((npix + kBlock - 1) / kBlock);
+    const PixelCountsLayout L = pixel_counts_layout(npix);
+    int64_t *block_counts = static_cast<int64_t *>(ws_at(workspace, L.counts));
+    const unsigned nb = (unsigned)L.blocks;
     hipLaunchKernelGGL(nonzero_count_kernel, dim3(nb), dim3(kBlock), 0, s, img, npix, block_counts);
     hipLaunchKernelGGL(nonzero_write_kernel, dim3(nb), dim3(kBlock), 0, s, img, npix, W, block_counts, capacity, out_rc, count);
     return hipGetLastError();

@@ -359,13 +359,25 @@ __global__ __launch_bounds__(kBlock) void ccl_box_kernel(const int32_t *__restri
 
 }  // namespace
 
-// parent, size, rank: int32 [n] each, then the scratch of the scan
-int64_t ccl_workspace_bytes(int64_t n) { return 12 * n + scan_scratch_bytes(n); }
+// parent, size, rank: int32 [n] each, back to back, then the scratch of the scan
+CclLayout ccl_layout(int64_t n)
+{
+    CclLayout L;
+    Carve c;
+    L.parent = c.take(4 * n, 4);
+    L.size = c.take(4 * n, 4);
+    L.rank = c.take(4 * n, 4);
+    L.scan = c.take(scan_scratch_bytes(n), 4);
+    L.total = c.at;
+    return L;
+}
 
 // flatten, count, number, label and box: everything after the merge kernel, the same for both labellings
-static hipError_t ccl_finish(int ny, int nz, int64_t n, int min_voxels, int32_t *parent, int32_t *size, uint32_t *rank, int32_t *out_label, int32_t *out_count,
+static hipError_t ccl_finish(int ny, int nz, int64_t n, int min_voxels, void *workspace, const CclLayout &L, int32_t *out_label, int32_t *out_count,
                              int32_t *out_stats, int capacity, hipStream_t s)
 {
+    int32_t *parent = static_cast<int32_t *>(ws_at(workspace, L.parent)), *size = static_cast<int32_t *>(ws_at(workspace, L.size));
+    uint32_t *rank = static_cast<uint32_t *>(ws_at(workspace, L.rank));
     const dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
     // about 512 workgroups, at most 64 turns each: few enough adds on the word of a component that spans the volume, enough waves to hide the walks
     const int iters = (int)std::min<int64_t>(64, (n + kCclFlattenSpan - 1) / kCclFlattenSpan);
@@ -374,7 +386,7 @@ static hipError_t ccl_finish(int ny, int nz, int64_t n, int min_voxels, int32_t 
     hipLaunchKernelGGL(ccl_flag_kernel, grid, block, 0, s, parent, size, rank, min_voxels, n);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    e = launch_exclusive_scan_u32(rank, rank, n, rank + n, s);
+    e = launch_exclusive_scan_u32(rank, rank, n, ws_at(workspace, L.scan), s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(ccl_label_kernel, grid, block, 0, s, parent, size, rank, out_label, out_count, out_stats, capacity, min_voxels, n);
     if (capacity > 0) hipLaunchKernelGGL(ccl_box_kernel, dim3((unsigned)((n + span - 1) / span)), block, 0, s, out_label, out_stats, capacity, ny, nz, iters, n);
@@ -385,9 +397,8 @@ hipError_t launch_volume_components(const uint8_t *site, int nx, int ny, int nz,
                                     int32_t *out_stats, int capacity, void *workspace, hipStream_t s)
 {
     const int64_t n = (int64_t)nx * ny * nz;
-    int32_t *parent = static_cast<int32_t *>(workspace);
-    int32_t *size = parent + n;
-    uint32_t *rank = reinterpret_cast<uint32_t *>(size + n);
+    const CclLayout L = ccl_layout(n);
+    int32_t *parent = static_cast<int32_t *>(ws_at(workspace, L.parent)), *size = static_cast<int32_t *>(ws_at(workspace, L.size));
     const dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
     hipLaunchKernelGGL(ccl_init_kernel, grid, block, 0, s, site, parent, size, out_count, nz, n);
     if (connectivity == 6)
@@ -396,21 +407,20 @@ hipError_t launch_volume_components(const uint8_t *site, int nx, int ny, int nz,
         hipLaunchKernelGGL(ccl_merge_kernel<18>, grid, block, 0, s, site, parent, ny, nz, n);
     else
         hipLaunchKernelGGL(ccl_merge_kernel<26>, grid, block, 0, s, site, parent, ny, nz, n);
-    return ccl_finish(ny, nz, n, min_voxels, parent, size, rank, out_label, out_count, out_stats, capacity, s);
+    return ccl_finish(ny, nz, n, min_voxels, workspace, L, out_label, out_count, out_stats, capacity, s);
 }
 
 hipError_t launch_volume_components_linked(const uint8_t *site, const uint16_t *links, int nx, int ny, int nz, int connectivity, int min_voxels,
                                            int32_t *out_label, int32_t *out_count, int32_t *out_stats, int capacity, void *workspace, hipStream_t s)
 {
     const int64_t n = (int64_t)nx * ny * nz;
-    int32_t *parent = static_cast<int32_t *>(workspace);
-    int32_t *size = parent + n;
-    uint32_t *rank = reinterpret_cast<uint32_t *>(size + n);
+    const CclLayout L = ccl_layout(n);
+    int32_t *parent = static_cast<int32_t *>(ws_at(workspace, L.parent)), *size = static_cast<int32_t *>(ws_at(workspace, L.size));
     const dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
     const uint32_t conn_mask = connectivity == 6 ? 0x1410u : connectivity == 18 ? 0x1ebau : 0x1fffu;      // bits by |dx|+|dy|+|dz| (parts_kernels.hip)
     hipLaunchKernelGGL(ccl_linked_init_kernel, grid, block, 0, s, site, links, parent, size, out_count, nz, conn_mask, n);
     hipLaunchKernelGGL(ccl_linked_merge_kernel, grid, block, 0, s, site, links, parent, ny, nz, conn_mask, n);
-    return ccl_finish(ny, nz, n, min_voxels, parent, size, rank, out_label, out_count, out_stats, capacity, s);
+    return ccl_finish(ny, nz, n, min_voxels, workspace, L, out_label, out_count, out_stats, capacity, s);
 }
 
 }  // namespace d3f

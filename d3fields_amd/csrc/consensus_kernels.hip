@@ -474,6 +474,24 @@ __global__ __launch_bounds__(64) void pose_refit_kernel(const float *__restrict_
 
 int64_t consensus_blocks(int64_t T) { return (T + kBlock - 1) / kBlock; }
 
+// the head; an eq and a fl word per workgroup of hypotheses and their scan's scratch; per survivor a hypothesis, a count, a flag, an assignment
+ConsensusLayout consensus_layout(int64_t T, int64_t max_survivors)
+{
+    const int64_t nb = consensus_blocks(T);
+    ConsensusLayout L;
+    Carve c;
+    L.head = c.take(kConsHeadWords * 4);
+    L.eq = c.take(nb * 4);
+    L.fl = c.take(nb * 4);
+    L.scan = c.take(scan_scratch_bytes(nb));
+    L.surv_h = c.take(max_survivors * 4);
+    L.surv_count = c.take(max_survivors);
+    L.alive = c.take(max_survivors);
+    L.surv_assign = c.take(max_survivors * kConsMaxM);
+    L.total = c.at;
+    return L;
+}
+
 hipError_t launch_consensus_score(const ConsensusParams &C, hipStream_t s)
 {
     hipError_t e = hipMemsetAsync(C.head, 0, kConsHeadWords * sizeof(uint32_t), s);

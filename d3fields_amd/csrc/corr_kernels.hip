@@ -822,35 +822,62 @@ __global__ __launch_bounds__(kBlock) void topk_write_kernel(const Cand *__restri
     if (val_out) val_out[t] = real ? x[(int64_t)cnd.i * cols + col] : NAN;     // the matrix AFTER exp / softmax was applied
 }
 
-int64_t topk_workspace_bytes(int64_t rows, int64_t cols)
+// levels of 256-fold reduction until one candidate list per column: level l folds items[l] rows into chunks[l] lists of kTopK candidates
+// per column, back to back
+TopkLayout topk_layout(int64_t rows, int64_t cols)
 {
-    if (rows <= 0 || cols <= 0) return 0;
-    int64_t total = 0, n = rows;
-    while (true) {                                  // levels of 256-fold reduction until one candidate list per column
-        const int64_t chunks = (n + kTopkRows - 1) / kTopkRows;
-        total += chunks * kTopK * cols * (int64_t)sizeof(Cand);
-        if (chunks == 1) break;
-        n = chunks * kTopK;
-    }
-    return total;
+    TopkLayout L;
+    Carve c;
+    L.levels = 0;
+    int64_t n = rows;
+    do {
+        L.items[L.levels] = n;
+        L.chunks[L.levels] = (n + kTopkRows - 1) / kTopkRows;
+        L.list[L.levels] = c.take(L.chunks[L.levels] * kTopK * cols * (int64_t)sizeof(Cand), sizeof(Cand));
+        n = L.chunks[L.levels++] * kTopK;
+    } while (n > kTopK);
+    L.total = c.at;
+    return L;
 }
 
-// dist [rows, cols] -> workspace ends with the final [kTopK, cols] list; returns a pointer to it
+int64_t topk_workspace_bytes(int64_t rows, int64_t cols) { return rows <= 0 || cols <= 0 ? 0 : topk_layout(rows, cols).total; }
+
+// one block of column statistics per 64 rows and one more, 16 bytes per column each
+SoftmaxLayout softmax_layout(int64_t rows, int64_t cols)
+{
+    SoftmaxLayout L;
+    Carve c;
+    L.stats = c.take(((rows + kSoftmaxRowsPerBlock - 1) / kSoftmaxRowsPerBlock + 1) * cols * (int64_t)sizeof(ColStat), sizeof(ColStat));
+    L.total = c.at;
+    return L;
+}
+
+// d3f_pairwise_similarity_topk: the column statistics, then from the next multiple of 256 the top-k levels
+PairTopkLayout pair_topk_layout(int64_t rows, int64_t cols)
+{
+    PairTopkLayout L;
+    Carve c;
+    const int64_t stats = softmax_layout(rows, cols).total;
+    L.stats = c.take(stats);
+    L.topk = c.take(topk_workspace_bytes(rows, cols), 1);
+    // slack nobody uses: the size has always been stats + top-k + 256, stated before the top-k's start was rounded up; kept so that no size changes
+    L.slack = c.take(stats + 256 - pad256(stats), 1);
+    L.total = c.at;
+    return L;
+}
+
+// dist [rows, cols] -> the last level of the workspace is the final [kTopK, cols] list; returns a pointer to it
 hipError_t launch_topk_select(const float *dist, int64_t rows, int64_t cols, void *workspace, const void **final_list, hipStream_t s)
 {
-    Cand *level = static_cast<Cand *>(workspace);
+    const TopkLayout L = topk_layout(rows, cols);
     const Cand *in = nullptr;
-    int64_t n = rows;
-    while (true) {
-        const int64_t chunks = (n + kTopkRows - 1) / kTopkRows;
-        hipLaunchKernelGGL(topk_chunk_kernel, dim3((unsigned)((cols + 63) / 64), (unsigned)chunks), dim3(kBlock), 0, s,
-                           in ? nullptr : dist, in, n, cols, level);
-        if (chunks == 1) break;
+    for (int l = 0; l < L.levels; ++l) {
+        Cand *level = static_cast<Cand *>(ws_at(workspace, L.list[l]));
+        hipLaunchKernelGGL(topk_chunk_kernel, dim3((unsigned)((cols + 63) / 64), (unsigned)L.chunks[l]), dim3(kBlock), 0, s,
+                           in ? nullptr : dist, in, L.items[l], cols, level);
         in = level;
-        n = chunks * kTopK;
-        level += chunks * kTopK * cols;
     }
-    *final_list = level;
+    *final_list = in;
     return hipGetLastError();
 }
 

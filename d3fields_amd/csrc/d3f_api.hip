@@ -294,7 +294,7 @@ int eval_common(const d3f_views *views, const float *pts, int64_t n, const d3f_c
     plan_family_and_order(q, P, pl);
     if (!pl.walk && pl.reorder && !plan_only) {
         if (flags & D3F_FLAG_REUSE_POINT_ORDER) {
-            P.order = d3f::stored_point_order(workspace, n);       // written by an earlier call for the same points
+            P.order = static_cast<const uint32_t *>(d3f::ws_at(workspace, d3f::order_layout(n).order));       // written by an earlier call for the same points
         } else {
             // Hilbert order of the cells of a 512^3 grid over the cloud's box, exact (order_kernels.hip); experiments builds: D3F_EXP_ORDER_MORTON=1 = the Z curve of rounds 1-4
             hipError_t eo = d3f::build_point_order(pts, n, workspace, workspace_bytes, &P.order, hs,
@@ -333,8 +333,9 @@ int eval_common(const d3f_views *views, const float *pts, int64_t n, const d3f_c
     // a cloud on the gated pair of launches: the window side (this pass) and the cell-run side (the next) read one device word
     const bool gated_window = cloud_side == 1 && pl.family == kFamWindow && !pl.walk && P.order != nullptr;
     const bool gated_runs = cloud_side == 2;
-    if (gated_window || gated_runs) {
-        P.gate = d3f::order_gate_words(workspace, n);
+    uint32_t *gate = (gated_window || gated_runs) ? static_cast<uint32_t *>(d3f::ws_at(workspace, d3f::order_layout(n).gate)) : nullptr;
+    if (gate) {
+        P.gate = gate;
         P.gate_min = (uint32_t)D3F_GATE_MIN_FIT;                   // three quarters of the sampled tiles fit their pool
         if ((flags & D3F_TUNE_WINDOW_SIDE) || tune.gate > 0) P.gate_min = 0u;          // always the window side
         if (tune.gate < 0) P.gate_min = 0xffffffffu;                                    // experiments: always the cell runs
@@ -345,7 +346,7 @@ int eval_common(const d3f_views *views, const float *pts, int64_t n, const d3f_c
     if (!gated_window) g_prof_stop = nullptr;
     if (ev0) (void)hipEventRecord(ev0, hs);
     if (gated_window) {
-        hipError_t ep = d3f::launch_window_gate_probe(P, d3f::order_gate_words(workspace, n), d3f::kGateSamples, hs);
+        hipError_t ep = d3f::launch_window_gate_probe(P, gate, d3f::kGateSamples, hs);
         if (ep != hipSuccess) return hip_fail(ep, "window gate probe");
     }
     if (tile_depth) {                                  // (inside the timed pair)
@@ -400,7 +401,7 @@ const char *d3f_plan_family_takes(int32_t family) { return (family >= 0 && famil
 
 int64_t d3f_eval_gate_offset(int64_t n)
 {
-    return n <= 0 ? 0 : d3f::order_gate_offset(n);
+    return n <= 0 ? 0 : d3f::order_layout(n).gate;
 }
 
 void d3f_profile_next_eval(void *start_event, void *stop_event)
@@ -434,7 +435,7 @@ int d3f_eval_plan_query_lattice(const d3f_views *views, int32_t nx, int32_t ny, 
 int64_t d3f_backproject_workspace_bytes(int32_t H, int32_t W)
 {
     if (H <= 0 || W <= 0) return 0;
-    return (((int64_t)H * W + d3f::kBlock - 1) / d3f::kBlock + 1) * (int64_t)sizeof(int64_t);
+    return d3f::pixel_counts_layout((int64_t)H * W).total;
 }
 
 int d3f_backproject_view(const double *depth, const uint8_t *mask, int32_t H, int32_t W, const double *cam_params,
@@ -446,7 +447,7 @@ int d3f_backproject_view(const double *depth, const uint8_t *mask, int32_t H, in
         return fail(D3F_ERR_INVALID_ARG, "backproject: NULL pointer or negative capacity");
     if (!(cam_params[0] != 0.0) || !(cam_params[1] != 0.0)) return fail(D3F_ERR_INVALID_ARG, "backproject: fx/fy must be non-zero");
     hipError_t e = d3f::launch_backproject(depth, mask, H, W, cam_params, cam_to_world, bounds, capacity, out_pts, out_pixel,
-                                           count_out, static_cast<int64_t *>(workspace), static_cast<hipStream_t>(stream));
+                                           count_out, workspace, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? D3F_OK : hip_fail(e, "backproject launch");
 }
 
@@ -475,7 +476,7 @@ int d3f_pcd_to_index(const double *pts, int64_t n, const double *lower, double v
 int64_t d3f_vox_iou_workspace_bytes(int64_t n1, int64_t n2)
 {
     if (n1 < 0 || n2 < 0) return 0;
-    return d3f::voxset_capacity(n1, n2) * (int64_t)sizeof(unsigned long long);
+    return d3f::voxset_layout(n1, n2).total;
 }
 
 int d3f_vox_idx_iou(const int32_t *idx1, int64_t n1, const int32_t *idx2, int64_t n2, int64_t *out_counts, void *workspace,
@@ -509,7 +510,7 @@ int d3f_compose_labels(const uint8_t *dets, int32_t n_dets, int64_t n_pix, const
     return e == hipSuccess ? D3F_OK : hip_fail(e, "compose_labels launch");
 }
 
-int64_t d3f_voxel_downsample_workspace_bytes(int64_t n) { return n > 0 ? d3f::voxmean_workspace_bytes(n) : 0; }
+int64_t d3f_voxel_downsample_workspace_bytes(int64_t n) { return n > 0 ? d3f::voxmean_layout(n).total : 0; }
 
 int d3f_voxel_downsample(const double *pts, const double *colors, int64_t n, double voxel_size, double *out_pts, double *out_colors,
                          int64_t *count_out, void *workspace, int64_t workspace_bytes, void *stream)
@@ -541,8 +542,7 @@ int d3f_nonzero_pixels(const uint8_t *image, int32_t H, int32_t W, int64_t capac
     if (H < 1 || W < 1 || (int64_t)H * W > 0x7fffffffLL) return fail(D3F_ERR_BAD_SHAPE, "nonzero_pixels: H=%d W=%d", H, W);
     if (!image || !count_out || !workspace || capacity < 0 || (capacity > 0 && !out_row_col))
         return fail(D3F_ERR_INVALID_ARG, "nonzero_pixels: NULL pointer or negative capacity");
-    hipError_t e = d3f::launch_nonzero_pixels(image, H, W, capacity, out_row_col, count_out, static_cast<int64_t *>(workspace),
-                                              static_cast<hipStream_t>(stream));
+    hipError_t e = d3f::launch_nonzero_pixels(image, H, W, capacity, out_row_col, count_out, workspace, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? D3F_OK : hip_fail(e, "nonzero_pixels launch");
 }
 
@@ -589,7 +589,7 @@ int d3f_eval_lattice(const d3f_views *views, const float *pts, int32_t nx, int32
 int64_t d3f_grid_shell_workspace_bytes(const d3f_grid *grid)
 {
     if (!grid || grid->nx <= 0 || grid->ny <= 0 || grid->nz <= 0) return 0;
-    return d3f::grid_shell_workspace_bytes((int64_t)grid->nx * grid->ny * grid->nz);
+    return d3f::grid_shell_layout((int64_t)grid->nx * grid->ny * grid->nz).total;
 }
 
 int d3f_grid_shell(const d3f_views *views, const d3f_grid *grid, float mu, float dist_thr, int64_t capacity, int64_t *idx_out,
@@ -605,10 +605,9 @@ int d3f_grid_shell(const d3f_views *views, const d3f_grid *grid, float mu, float
     if (!(mu > 0.0f)) return fail(D3F_ERR_INVALID_ARG, "mu must be > 0");
     if (((int64_t)grid->nx * grid->ny * grid->nz + d3f::kBlock - 1) / d3f::kBlock > 0x7fffffffLL) return fail(D3F_ERR_BAD_SHAPE, "grid too large for one launch");
     // a workspace with d3f_eval_dist_workspace_bytes(views, n) bytes MORE than the shell needs: the depth lookups go to a tiled copy there
-    const int64_t n_grid = (int64_t)grid->nx * grid->ny * grid->nz, shell_bytes = (d3f_grid_shell_workspace_bytes(grid) + 255) / 256 * 256;
-    const int64_t tiled_bytes = d3f_eval_dist_workspace_bytes(views, n_grid);
-    float *tiled = (tiled_bytes > 0 && workspace_bytes >= shell_bytes + tiled_bytes)
-                       ? reinterpret_cast<float *>(static_cast<unsigned char *>(workspace) + shell_bytes) : nullptr;
+    const int64_t n_grid = (int64_t)grid->nx * grid->ny * grid->nz, tiled_bytes = d3f_eval_dist_workspace_bytes(views, n_grid);
+    const d3f::ShellTiledLayout L = d3f::grid_shell_tiled_layout(n_grid, tiled_bytes);
+    float *tiled = (tiled_bytes > 0 && workspace_bytes >= L.total) ? static_cast<float *>(d3f::ws_at(workspace, L.tiles)) : nullptr;
     hipError_t e = d3f::launch_grid_shell(views->depth, views->K, views->pose, views->V, views->H, views->W, grid->x, grid->y,
                                           grid->z, grid->nx, grid->ny, grid->nz, mu, dist_thr, capacity, idx_out,
                                           reinterpret_cast<unsigned long long *>(count_out), workspace, static_cast<hipStream_t>(stream),
@@ -631,7 +630,7 @@ static int check_mesh(const char *who, const float *volume, int32_t nx, int32_t 
 int64_t d3f_mesh_workspace_bytes(int32_t nx, int32_t ny, int32_t nz)
 {
     if (nx < 2 || ny < 2 || nz < 2) return 0;
-    return d3f::mesh_workspace_bytes((int64_t)nx * ny * nz);
+    return d3f::mesh_layout((int64_t)nx * ny * nz).total;
 }
 
 int d3f_mesh_count(const float *volume, const uint8_t *valid, int32_t nx, int32_t ny, int32_t nz, float iso, int64_t *counts_out,
@@ -865,7 +864,7 @@ int d3f_band_sample_backward(const d3f_volume *vol, const d3f_band *band, const 
 // ---- the exact Euclidean distance transform of a site volume (edt_kernels.hip) ----
 int64_t d3f_volume_edt_workspace_bytes(int32_t nx, int32_t ny, int32_t nz)
 {
-    return edt_shape_ok(nx, ny, nz) ? d3f::edt_workspace_bytes((int64_t)nx * ny * nz) : 0;
+    return edt_shape_ok(nx, ny, nz) ? d3f::edt_layout((int64_t)nx * ny * nz).total : 0;
 }
 
 int d3f_volume_edt(const uint8_t *site, int32_t nx, int32_t ny, int32_t nz, float step, int32_t max_d2, int32_t *out_d2, int32_t *out_nearest,
@@ -887,7 +886,7 @@ int d3f_volume_edt(const uint8_t *site, int32_t nx, int32_t ny, int32_t nz, floa
 // ---- connected components of a site volume (ccl_kernels.hip) ----
 int64_t d3f_volume_components_workspace_bytes(int32_t nx, int32_t ny, int32_t nz)
 {
-    return edt_shape_ok(nx, ny, nz) ? d3f::ccl_workspace_bytes((int64_t)nx * ny * nz) : 0;
+    return edt_shape_ok(nx, ny, nz) ? d3f::ccl_layout((int64_t)nx * ny * nz).total : 0;
 }
 
 // both forms: every pair of neighbouring sites is joined, or (linked) only the pairs whose bit of links is set (d3f_volume_links)
@@ -1107,7 +1106,7 @@ static int check_geo_weights(const char *who, int32_t connectivity, const int32_
 
 int64_t d3f_volume_geodesic_workspace_bytes(int32_t nx, int32_t ny, int32_t nz)
 {
-    return edt_shape_ok(nx, ny, nz) ? d3f::geodesic_workspace_bytes(nx, ny, nz) : 0;
+    return edt_shape_ok(nx, ny, nz) ? d3f::geodesic_layout(nx, ny, nz).total : 0;
 }
 
 int d3f_volume_geodesic_init(const uint8_t *free, int32_t nx, int32_t ny, int32_t nz, const int32_t *seeds, int64_t n_seeds, int32_t *out_cost,
@@ -1259,7 +1258,7 @@ int64_t d3f_volume_align_workspace_bytes(int64_t I, int64_t n)
     if (I <= 0 || n <= 0) return 0;
     const int64_t chunks = d3f::align_chunks(n);
     if (chunks > 0x7fffffffLL / I) return 0;
-    return I * chunks * d3f::kAlignRow * (int64_t)sizeof(double);
+    return d3f::align_layout(I, n).total;
 }
 
 int d3f_volume_align_centroid(const float *points, const float *weights, int64_t I, int64_t n, float *centroids_out, void *stream)
@@ -1315,7 +1314,7 @@ int d3f_volume_align_accumulate(const d3f_volume *vol, const d3f_band *band, con
     A.wf = feat_weight;
     A.outside = outside;
     A.chunks = chunks;
-    A.partial = static_cast<double *>(workspace);
+    A.partial = static_cast<double *>(d3f::ws_at(workspace, d3f::align_layout(I, n).partial));
     hipError_t e = d3f::launch_align_accumulate(A, out, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_align_accumulate launch");
 }
@@ -1339,7 +1338,7 @@ int d3f_volume_align_step(double *state, const void *workspace, int64_t workspac
         return fail(D3F_ERR_WORKSPACE, "%s: needs %lld workspace bytes", who, (long long)d3f_volume_align_workspace_bytes(I, n));
     d3f::AlignStep S;
     S.state = state;
-    S.partial = static_cast<const double *>(workspace);
+    S.partial = static_cast<const double *>(d3f::ws_at(const_cast<void *>(workspace), d3f::align_layout(I, n).partial));
     S.chunks = chunks;
     S.out = out;
     S.it = it;
@@ -1355,28 +1354,6 @@ int d3f_volume_align_step(double *state, const void *workspace, int64_t workspac
 
 // ---- consensus poses from (model point, candidate) triples (consensus_kernels.hip) ----
 namespace {
-
-int64_t up256(int64_t b) { return (b + 255) / 256 * 256; }
-
-// the pieces of the workspace, in order; -> total bytes
-struct ConsensusLayout {
-    int64_t head, eq, fl, scan, surv_h, surv_count, alive, surv_assign, total;
-};
-ConsensusLayout consensus_layout(int64_t T, int64_t max_survivors)
-{
-    const int64_t nb = d3f::consensus_blocks(T);
-    ConsensusLayout L;
-    L.head = 0;
-    L.eq = up256(d3f::kConsHeadWords * 4);
-    L.fl = L.eq + up256(nb * 4);
-    L.scan = L.fl + up256(nb * 4);
-    L.surv_h = L.scan + up256(d3f::scan_scratch_bytes(nb));
-    L.surv_count = L.surv_h + up256(max_survivors * 4);
-    L.alive = L.surv_count + up256(max_survivors);
-    L.surv_assign = L.alive + up256(max_survivors);
-    L.total = L.surv_assign + up256(max_survivors * d3f::kConsMaxM);
-    return L;
-}
 
 // M, k, n_trip -> T, or a status
 int consensus_shape(const char *who, int32_t M, int32_t k, int64_t n_trip, int64_t &T)
@@ -1405,7 +1382,7 @@ int64_t d3f_pose_consensus_workspace_bytes(int32_t M, int32_t k, int64_t n_trip,
     int64_t T = 0;
     if (consensus_shape("pose_consensus_workspace_bytes", M, k, n_trip, T) != D3F_OK) return 0;
     if (max_survivors < 1 || max_survivors > D3F_CONSENSUS_MAX_SURVIVORS) return 0;
-    return consensus_layout(T, max_survivors).total;
+    return d3f::consensus_layout(T, max_survivors).total;
 }
 
 int d3f_pose_consensus_score(const float *model, const float *cand, int32_t M, int32_t k, const int32_t *triplets, const int32_t *triplets_host,
@@ -1427,7 +1404,8 @@ int d3f_pose_consensus_score(const float *model, const float *cand, int32_t M, i
     }
     if (!aligned(model, 4) || !aligned(cand, 4) || !aligned(triplets, 4) || !aligned(pose_out, 4) || !aligned(workspace, 16))
         return fail(D3F_ERR_BAD_LAYOUT, "%s: model / cand / triplets / pose_out must be 4-byte aligned, the workspace 16-byte aligned", who);
-    if (workspace_bytes < up256(d3f::kConsHeadWords * 4)) return fail(D3F_ERR_WORKSPACE, "%s: needs %lld workspace bytes", who, (long long)up256(d3f::kConsHeadWords * 4));
+    const d3f::ConsensusLayout L = d3f::consensus_layout(T, 1);
+    if (workspace_bytes < L.eq) return fail(D3F_ERR_WORKSPACE, "%s: needs %lld workspace bytes", who, (long long)L.eq);
     d3f::ConsensusParams C;
     C.model = model;
     C.cand = cand;
@@ -1442,7 +1420,7 @@ int d3f_pose_consensus_score(const float *model, const float *cand, int32_t M, i
     C.count = count_out;
     C.pose_dbg = pose_out;
     C.assign_dbg = assign_out;
-    C.head = static_cast<uint32_t *>(workspace);
+    C.head = static_cast<uint32_t *>(d3f::ws_at(workspace, L.head));
     hipError_t e = d3f::launch_consensus_score(C, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? D3F_OK : hip_fail(e, "pose_consensus_score launch");
 }
@@ -1469,7 +1447,7 @@ int d3f_pose_consensus_select(const float *model, const float *cand, int32_t M, 
     if (!aligned(model, 4) || !aligned(cand, 4) || !aligned(triplets, 4) || !aligned(hyp_out, 4) || !aligned(inliers_out, 4) || !aligned(assign_out, 4) ||
         !aligned(pose_out, 4) || !aligned(stats_out, 4) || !aligned(workspace, 16))
         return fail(D3F_ERR_BAD_LAYOUT, "%s: float / int32 arrays and assign_out must be 4-byte aligned, the workspace 16-byte aligned", who);
-    const ConsensusLayout L = consensus_layout(T, max_survivors);
+    const d3f::ConsensusLayout L = d3f::consensus_layout(T, max_survivors);
     if (workspace_bytes < L.total) return fail(D3F_ERR_WORKSPACE, "%s: needs %lld workspace bytes", who, (long long)L.total);
     unsigned char *ws = static_cast<unsigned char *>(workspace);
     d3f::ConsensusSelect S;
@@ -1586,8 +1564,8 @@ int d3f_volume_raycast(const d3f_volume *vol, const float *origins, const float 
     return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_raycast launch");
 }
 
-int64_t d3f_fps_workspace_bytes(int64_t n) { return n > 0 ? d3f::fps_workspace_bytes(n, 4) : 0; }
-int64_t d3f_fps_pixels_workspace_bytes(int64_t n) { return n > 0 ? d3f::fps_workspace_bytes(n, 8) : 0; }
+int64_t d3f_fps_workspace_bytes(int64_t n) { return n > 0 ? d3f::fps_layout(n, 4).total : 0; }
+int64_t d3f_fps_pixels_workspace_bytes(int64_t n) { return n > 0 ? d3f::fps_layout(n, 8).total : 0; }
 
 int d3f_farthest_point_sampling(const float *pts, int64_t n, int32_t k, int64_t init_idx, int64_t *out_idx, float *out_maxdist,
                                 void *workspace, void *stream)
@@ -1807,8 +1785,13 @@ int d3f_instance2onehot(const uint8_t *instance, int64_t n, int32_t NI, uint8_t 
 int64_t d3f_softmax_workspace_bytes(int64_t rows, int64_t cols)
 {
     if (rows <= 0 || cols <= 0) return 0;
-    const int64_t nchunks = (rows + d3f::kSoftmaxRowsPerBlock - 1) / d3f::kSoftmaxRowsPerBlock;
-    return (nchunks + 1) * cols * (int64_t)sizeof(d3f::ColStat);
+    return d3f::softmax_layout(rows, cols).total;
+}
+
+// the column statistics inside a workspace of d3f_softmax_workspace_bytes(rows, cols) (or of a layout that begins with them); NULL stays NULL
+static d3f::ColStat *softmax_stats(void *workspace, int64_t rows, int64_t cols)
+{
+    return workspace ? static_cast<d3f::ColStat *>(d3f::ws_at(workspace, d3f::softmax_layout(rows, cols).stats)) : nullptr;
 }
 
 static int check_sim_enums(int32_t dist_type, int32_t mode)
@@ -1836,7 +1819,7 @@ int d3f_similarity_to_target(const float *src, int64_t B, int64_t inner, int32_t
         e = d3f::launch_exp_neg_scale(out, B * inner, scale, s);
         if (e != hipSuccess) return hip_fail(e, "exp launch");
     } else if (mode == D3F_SIM_SOFTMAX_DIM0) {
-        e = d3f::launch_softmax_dim0(out, B, inner, scale, nullptr, static_cast<d3f::ColStat *>(workspace), false, s);
+        e = d3f::launch_softmax_dim0(out, B, inner, scale, nullptr, softmax_stats(workspace, B, inner), false, s);
         if (e != hipSuccess) return hip_fail(e, "softmax launch");
     }
     return D3F_OK;
@@ -1856,7 +1839,7 @@ int d3f_pairwise_similarity(const float *src, const float *tgt, int64_t B1, int6
     if (need_ws && (!workspace || workspace_bytes < d3f_softmax_workspace_bytes(B1, B2)))
         return fail(D3F_ERR_WORKSPACE, "pairwise: needs %lld workspace bytes", (long long)d3f_softmax_workspace_bytes(B1, B2));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    d3f::ColStat *ws = static_cast<d3f::ColStat *>(workspace);
+    d3f::ColStat *ws = softmax_stats(workspace, B1, B2);
     // the column statistics (softmax / best match) come out of the distance kernel's epilogue, per 64-row tile
     hipError_t e = d3f::launch_pairwise_dist(src, tgt, B1, B2, C, dist_type, out, s, need_ws ? ws : nullptr,
                                              mode == D3F_SIM_SOFTMAX_DIM0 ? scale : 1.0f);
@@ -1880,7 +1863,7 @@ int d3f_pairwise_similarity(const float *src, const float *tgt, int64_t B1, int6
 int64_t d3f_pairwise_topk_workspace_bytes(int64_t B1, int64_t B2)
 {
     if (B1 <= 0 || B2 <= 0) return 0;
-    return d3f_softmax_workspace_bytes(B1, B2) + d3f::topk_workspace_bytes(B1, B2) + 256;
+    return d3f::pair_topk_layout(B1, B2).total;
 }
 
 int d3f_pairwise_similarity_topk(const float *src, const float *tgt, int64_t B1, int64_t B2, int32_t C, float scale,
@@ -1902,8 +1885,9 @@ int d3f_pairwise_similarity_topk(const float *src, const float *tgt, int64_t B1,
     hipError_t e = hipSuccess;
     const void *final_list = nullptr;
     if (B1 > 0) {
-        d3f::ColStat *ws = static_cast<d3f::ColStat *>(workspace);
-        unsigned char *tk = static_cast<unsigned char *>(workspace) + (d3f_softmax_workspace_bytes(B1, B2) + 255) / 256 * 256;
+        const d3f::PairTopkLayout L = d3f::pair_topk_layout(B1, B2);
+        d3f::ColStat *ws = static_cast<d3f::ColStat *>(d3f::ws_at(workspace, L.stats));
+        void *tk = d3f::ws_at(workspace, L.topk);
         const bool stats = mode == D3F_SIM_SOFTMAX_DIM0;
         e = d3f::launch_pairwise_dist(src, tgt, B1, B2, C, dist_type, out, s, stats ? ws : nullptr, stats ? scale : 1.0f);
         if (e != hipSuccess) return hip_fail(e, "pairwise_dist launch");
@@ -1966,10 +1950,10 @@ int d3f_pairwise_softmax_local(const float *src, const float *tgt, int64_t B1, i
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipError_t e = hipSuccess;
     if (B1 > 0) {
-        e = d3f::launch_pairwise_dist(src, tgt, B1, B2, C, dist_type, out, s, static_cast<d3f::ColStat *>(workspace), scale);
+        e = d3f::launch_pairwise_dist(src, tgt, B1, B2, C, dist_type, out, s, softmax_stats(workspace, B1, B2), scale);
         if (e != hipSuccess) return hip_fail(e, "pairwise_dist launch");
     }
-    e = d3f::launch_softmax_local_stats(out, B1, B2, scale, row_offset, static_cast<d3f::ColStat *>(workspace),
+    e = d3f::launch_softmax_local_stats(out, B1, B2, scale, row_offset, softmax_stats(workspace, B1, B2),
                                         reinterpret_cast<d3f::ColStat *>(stats), true, s);
     return e == hipSuccess ? D3F_OK : hip_fail(e, "softmax statistics launch");
 }

@@ -5,6 +5,7 @@
 #include <stdio.h>
 
 #include "../../include/d3fields_hip.h"
+#include "d3f_workspace.h"
 
 // the planner's kernel families (d3f_plan.h: kFamilies; the value of d3f_eval_plan.family)
 enum FamilyId { kFamDistOnly = 0, kFamWindow, kFamRuns, kFamSliced, kFamDirect, kFamRows };
@@ -140,8 +141,6 @@ hipError_t launch_window(const EvalParams &P, const Launch &L);                 
 hipError_t launch_rows(const EvalParams &P, const Launch &L);                         // fuse_rows.hip
 constexpr int kGateSamples = D3F_GATE_SAMPLES;            // tiles the probe looks at (evenly spaced over the order)
 hipError_t launch_window_gate_probe(const EvalParams &P, uint32_t *gate, int nsamples, hipStream_t stream);
-int64_t order_gate_offset(int64_t n);
-uint32_t *order_gate_words(void *workspace, int64_t n);      // 4 words at the end of a workspace of order_workspace_bytes(n)
 
 // fuse_backward.hip
 struct BackwardParams {
@@ -161,17 +160,20 @@ struct BackwardParams {
 };
 hipError_t launch_fused_backward(const BackwardParams &P, int mode, hipStream_t stream);
 
-// scan_kernels.hip: exclusive prefix sum of uint32 counters (in == out allowed); scratch >= scan_scratch_bytes(n)
-int64_t scan_scratch_bytes(int64_t n);
+// scan_kernels.hip: exclusive prefix sum of uint32 counters (in == out allowed); scratch laid out by scan_layout(n)
+struct ScanLayout { int64_t sums[6], spare, total; int64_t blocks[6]; int levels; };
+ScanLayout scan_layout(int64_t n);
+int64_t scan_scratch_bytes(int64_t n);      // scan_layout(n).total
 hipError_t launch_exclusive_scan_u32(const uint32_t *in, uint32_t *out, int64_t n, void *scratch, hipStream_t s);
 int64_t scan_status_words(int64_t n);      // single-launch form (decoupled look-back): zeroed status words, total < 2^30
 hipError_t launch_exclusive_scan_lookback_u32(const uint32_t *in, uint32_t *out, int64_t n, uint32_t *status, hipStream_t s);
 
-// order_kernels.hip
-int64_t order_workspace_bytes(int64_t n);
+// order_kernels.hip; gate: the word of the gated pair of launches (4 words are cleared), public as d3f_eval_gate_offset
+struct OrderLayout { int64_t keys, ranks, order, slots, table, scan, gate, parts, total; };
+OrderLayout order_layout(int64_t n);
+int64_t order_workspace_bytes(int64_t n);   // 0 for n <= 0, else order_layout(n).total
 hipError_t build_point_order(const float *pts, int64_t n, void *workspace, int64_t workspace_bytes,
                              const uint32_t **order_out, hipStream_t stream, int fine = 0);
-const uint32_t *stored_point_order(void *workspace, int64_t n);
 // is pts a z-fastest lattice?  out: 3 device int32 (nx, ny, nz), zeros when not
 hipError_t launch_lattice_probe(const float *pts, int64_t n, int32_t *out_dims, hipStream_t stream);
 // mean L1 step between consecutive points vs between points n/2 apart (out: 2 device floats)
@@ -184,13 +186,18 @@ hipError_t launch_grid_shell(const float *depth, const float *K, const float *po
                              const float *gy, const float *gz, int nx, int ny, int nz, float mu, float dist_thr,
                              int64_t capacity, int64_t *idx_out, unsigned long long *count, void *workspace, hipStream_t s,
                              float *tiled_scratch);
-int64_t grid_shell_workspace_bytes(int64_t n);
+struct ShellLayout { int64_t ballots, counts, offsets, scan, total; int64_t blocks; };
+ShellLayout grid_shell_layout(int64_t n);
+struct ShellTiledLayout { int64_t shell, tiles, total; };
+ShellTiledLayout grid_shell_tiled_layout(int64_t n, int64_t tiled_bytes);
 hipError_t launch_fps(const float *pts, int64_t n, int k, int64_t init_idx, int64_t *out_idx, float *out_maxdist,
                       void *workspace, hipStream_t s);
-int64_t fps_workspace_bytes(int64_t n, int dist_bytes);     // n distances + two arrays of per-workgroup maxima
+struct FpsLayout { int64_t dist, maxima, total; };
+FpsLayout fps_layout(int64_t n, int dist_bytes);            // dist_bytes: 4 (d3f_farthest_point_sampling) or 8 (d3f_fps_pixels)
 
 // mesh_kernels.hip
-int64_t mesh_workspace_bytes(int64_t n);
+struct MeshLayout { int64_t voff, toff, scan, total; int64_t blocks; };
+MeshLayout mesh_layout(int64_t n);
 hipError_t launch_mesh(const float *vol, const uint8_t *valid, int nx, int ny, int nz, float iso, int64_t vertex_capacity,
                        int64_t triangle_capacity, int64_t *keys, float *ts, int32_t *tris, int64_t *counts_out, void *workspace,
                        bool extract, hipStream_t s);
@@ -241,12 +248,14 @@ hipError_t launch_band_sample(const BandParams &B, hipStream_t s);
 hipError_t launch_band_backward(const BandParams &B, hipStream_t s);
 
 // edt_kernels.hip: the exact Euclidean distance transform of a site volume; cap: max_d2, or INT32_MAX for none
-int64_t edt_workspace_bytes(int64_t n);
+struct EdtLayout { int64_t B, A, total; };
+EdtLayout edt_layout(int64_t n);
 hipError_t launch_volume_edt(const uint8_t *site, int nx, int ny, int nz, float step, int32_t cap, int32_t *out_d2, int32_t *out_nearest, float *out_dist,
                              void *workspace, hipStream_t s);
 
 // ccl_kernels.hip: connected components of a site volume
-int64_t ccl_workspace_bytes(int64_t n);
+struct CclLayout { int64_t parent, size, rank, scan, total; };
+CclLayout ccl_layout(int64_t n);
 hipError_t launch_volume_components(const uint8_t *site, int nx, int ny, int nz, int connectivity, int min_voxels, int32_t *out_label, int32_t *out_count,
                                     int32_t *out_stats, int capacity, void *workspace, hipStream_t s);
 hipError_t launch_volume_components_linked(const uint8_t *site, const uint16_t *links, int nx, int ny, int nz, int connectivity, int min_voxels,
@@ -277,7 +286,7 @@ struct PoolArgs {
     void *const *out_rows;       // host memory
     void *workspace;
 };
-int64_t pool_workspace_bytes(int64_t n, int64_t K, int64_t cap, int64_t mean_channels);
+int64_t pool_workspace_bytes(int64_t n, int64_t K, int64_t cap, int64_t mean_channels);      // cap clamped to n, then pool_layout(...).total
 int pool_levels(int64_t cap);                                       // fold levels a member capacity needs: 1..4
 hipError_t launch_volume_pool(const PoolArgs &A, hipStream_t s);
 hipError_t launch_pool_nothing(int64_t *out_members, hipStream_t s);   // K == 0: out_members = 0
@@ -291,9 +300,9 @@ struct PoolPlan {
     uint32_t *work[4];
     uint32_t *part[3];
 };
-// what the workspace holds, in this order (every piece padded to 256 bytes); pitch: the 4-byte words of a partial row
+// pitch: the 4-byte words of a partial row; first / work / part: the arrays of PoolPlan
 struct PoolLayout {
-    int64_t flag, flag_scan, keys[2], vals[2], counters, counters_scan, plan, plan_scan, rows[2], total;
+    int64_t flag, flag_scan, keys[2], vals[2], counters, counters_scan, first, work[4], part[3], plan_scan, rows[2], total;
     int64_t waves_total, rows_a, rows_b;
 };
 PoolLayout pool_layout(int64_t n, int64_t K, int64_t cap, int64_t pitch);
@@ -334,11 +343,17 @@ struct MotionArgs {
     double *out_sums;            // or nullptr
     void *workspace;
 };
-int64_t motion_workspace_bytes(int64_t n, int64_t K, int64_t cap);
+struct MotionLayout {
+    int64_t lab, pool, sums, fsum, centre, total;
+    PoolLayout P;                // of the pool region, offsets from its start
+};
+MotionLayout motion_layout(int64_t n, int64_t K, int64_t cap);
+int64_t motion_workspace_bytes(int64_t n, int64_t K, int64_t cap);          // cap clamped to n, then motion_layout(n, K, cap).total
 hipError_t launch_part_motion(const MotionArgs &A, hipStream_t s);
 
 // geodesic_kernels.hip: cost-to-go through free space, exact shortest paths on the lattice; w: host int32[3]
-int64_t geodesic_workspace_bytes(int nx, int ny, int nz);
+struct GeoLayout { int64_t header, flags, list, total; int64_t tiles; };
+GeoLayout geodesic_layout(int nx, int ny, int nz);
 hipError_t launch_geodesic_init(const uint8_t *free, int nx, int ny, int nz, const int32_t *seeds, int64_t n_seeds, int32_t *out_cost, void *workspace,
                                 hipStream_t s);
 hipError_t launch_geodesic_relax(const uint8_t *free, const int32_t *penalty, int nx, int ny, int nz, int connectivity, const int32_t *w, int32_t max_cost,
@@ -394,6 +409,11 @@ struct AlignStep {
     double *history;           // [I, iters + 1]
 };
 int64_t align_chunks(int64_t n);
+struct AlignLayout {
+    int64_t partial, total;
+    int64_t chunks;            // workgroups per instance
+};
+AlignLayout align_layout(int64_t I, int64_t n);
 hipError_t launch_align_centroid(const float *pts, const float *weights, int64_t I, int64_t n, float *out, hipStream_t s);
 hipError_t launch_align_accumulate(const AlignParams &A, double *out, hipStream_t s);
 hipError_t launch_align_step(const AlignStep &S, int64_t I, hipStream_t s);
@@ -429,6 +449,10 @@ struct ConsensusSelect {
     float *pose_out;           // [n_poses, 12]
 };
 int64_t consensus_blocks(int64_t T);
+struct ConsensusLayout {       // the scoring pass uses the head alone: the bytes in front of eq
+    int64_t head, eq, fl, scan, surv_h, surv_count, alive, surv_assign, total;
+};
+ConsensusLayout consensus_layout(int64_t T, int64_t max_survivors);
 hipError_t launch_consensus_score(const ConsensusParams &C, hipStream_t s);
 hipError_t launch_consensus_select(const ConsensusSelect &S, hipStream_t s);
 hipError_t launch_pose_refit(const float *model, const float *cand, int M, int k, const int8_t *assign, int n_poses, float tau2, float *pose_out, double *rmse_out,
@@ -459,16 +483,29 @@ hipError_t launch_volume_raycast(const RayParams &P, bool camera, hipStream_t s)
 // pcd_kernels.hip
 hipError_t launch_backproject(const double *depth, const uint8_t *mask, int H, int W, const double *cam, const double *T,
                               const double *bounds, int64_t capacity, double *out_pts, int32_t *out_pixel, int64_t *count,
-                              int64_t *block_counts, hipStream_t s);
+                              void *workspace, hipStream_t s);
+struct PixelCountsLayout {     // d3f_backproject_view and d3f_nonzero_pixels
+    int64_t counts, total;
+    int64_t blocks;
+};
+PixelCountsLayout pixel_counts_layout(int64_t npix);
 hipError_t launch_nearest(const double *a, int64_t na, const double *b, int64_t nb, double *min_dist, int64_t *argmin, hipStream_t s);
 
 // assoc_kernels.hip
 hipError_t launch_pcd_to_index(const double *pts, int64_t n, const double *lower, double voxel_size, const int32_t *voxel_num,
                                int32_t *out_index, int32_t *out_voxel, hipStream_t s);
-int64_t voxset_capacity(int64_t n1, int64_t n2);
+struct VoxsetLayout {
+    int64_t table, total;
+    int64_t cap;               // slots, a power of two
+};
+VoxsetLayout voxset_layout(int64_t n1, int64_t n2);
 hipError_t launch_voxset_iou(const int32_t *a, int64_t na, const int32_t *b, int64_t nb, int64_t *counts, void *workspace,
                              hipStream_t s);
-int64_t voxmean_workspace_bytes(int64_t n);
+struct VoxmeanLayout {
+    int64_t minb, table, counts, list, total;
+    int64_t cap, blocks;       // slots, workgroups over them
+};
+VoxmeanLayout voxmean_layout(int64_t n);
 hipError_t launch_voxel_mean(const double *pts, const double *col, int64_t n, double vs, double *out_pts, double *out_col, int64_t *count,
                              void *workspace, hipStream_t s);
 hipError_t launch_erode(const uint8_t *src, int H, int W, int kh, int kw, uint8_t *dst, hipStream_t s);
@@ -476,7 +513,7 @@ hipError_t launch_compose_labels(const uint8_t *dets, int n_dets, int64_t n_pix,
 hipError_t launch_mask_gate(const float *mask, int64_t sy, int64_t sx, const float *depth, int H, int W, float lo, float hi,
                             uint8_t *out, hipStream_t s);
 hipError_t launch_nonzero_pixels(const uint8_t *img, int H, int W, int64_t capacity, int32_t *out_rc, int64_t *count,
-                                 int64_t *block_counts, hipStream_t s);
+                                 void *workspace, hipStream_t s);
 hipError_t launch_fps_pixels(const int32_t *pts, int64_t n, int k, int64_t init_idx, int64_t *out_idx, double *out_maxdist,
                              void *workspace, hipStream_t s);
 
@@ -494,7 +531,14 @@ hipError_t launch_project_maps(const void *data, int V, int fh, int fw, int C, i
                                int k, float *dst, hipStream_t s);
 
 // moment_kernels.hip
-int64_t row_moments_workspace_bytes(int64_t M, int C);
+struct MomentPlan {
+    int panels, pairs, cpad;
+    int64_t sum_slabs, sum_rows;                 // pass 1: slabs and rows per slab
+    int64_t slabs, slab_rows;                    // pass 2
+    int64_t off_wsum_part, off_sum_part, off_wsum, off_m32, off_col_part, off_tiles, bytes;
+};
+MomentPlan moment_plan(int64_t M, int C);
+int64_t row_moments_workspace_bytes(int64_t M, int C);      // moment_plan(M, C).bytes
 hipError_t launch_row_moments(const void *rows, bool half, int64_t M, int C, int64_t row_stride, const float *weights, double *wsum_out,
                               double *mean_out, double *scatter_out, void *workspace, hipStream_t s);
 
@@ -525,7 +569,17 @@ hipError_t launch_argmin_dim0(const float *x, int64_t rows, int64_t cols, int64_
                               bool have_stats, hipStream_t s);
 
 // k smallest entries per column of a [rows, cols] distance matrix (k <= 8), ties -> lower row, NaN last
-int64_t topk_workspace_bytes(int64_t rows, int64_t cols);
+struct SoftmaxLayout { int64_t stats, total; };
+SoftmaxLayout softmax_layout(int64_t rows, int64_t cols);
+struct TopkLayout {
+    int64_t list[16], total;       // 2^31 - 1 rows (the entry points' limit): 7 levels; any int64: 13
+    int64_t items[16], chunks[16];
+    int levels;
+};
+TopkLayout topk_layout(int64_t rows, int64_t cols);
+int64_t topk_workspace_bytes(int64_t rows, int64_t cols);   // 0 without rows or columns, else topk_layout(rows, cols).total
+struct PairTopkLayout { int64_t stats, topk, slack, total; };
+PairTopkLayout pair_topk_layout(int64_t rows, int64_t cols);
 hipError_t launch_topk_select(const float *dist, int64_t rows, int64_t cols, void *workspace, const void **final_list, hipStream_t s);
 hipError_t launch_topk_write(const void *final_list, const float *x, int64_t rows, int64_t cols, int k, int64_t *idx_out,
                              float *val_out, hipStream_t s);

@@ -195,15 +195,24 @@ hipError_t launch_pass(const EdtPass &P, hipStream_t s)
 
 }  // namespace
 
-// B int32 [n] then A int16 [n]
-int64_t edt_workspace_bytes(int64_t n) { return 4 * n + 2 * ((n + 1) / 2 * 2); }
+// B int32 [n] then A int16 [n], an even count of them
+EdtLayout edt_layout(int64_t n)
+{
+    EdtLayout L;
+    Carve c;
+    L.B = c.take(4 * n, 4);
+    L.A = c.take(2 * n, 4);
+    L.total = c.at;
+    return L;
+}
 
 hipError_t launch_volume_edt(const uint8_t *site, int nx, int ny, int nz, float step, int32_t cap, int32_t *out_d2, int32_t *out_nearest, float *out_dist,
                              void *workspace, hipStream_t s)
 {
     const int64_t n = (int64_t)nx * ny * nz;
-    int32_t *B = static_cast<int32_t *>(workspace);
-    int16_t *A = reinterpret_cast<int16_t *>(B + n);
+    const EdtLayout L = edt_layout(n);
+    int32_t *B = static_cast<int32_t *>(ws_at(workspace, L.B));
+    int16_t *A = static_cast<int16_t *>(ws_at(workspace, L.A));
     const uint32_t best0 = cap == 0x7fffffff ? kEdtNone : (uint32_t)cap + 1u;
     const int64_t zlines = (int64_t)nx * ny;
     if (nz <= 64) {

@@ -333,17 +333,28 @@ unsigned geo_blocks(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
 }  // namespace
 
-// the header (two list counts, padded to 16 words), then one flag word and one list word per tile
-int64_t geodesic_workspace_bytes(int nx, int ny, int nz) { return 4 * (kGeoHeaderWords + 2 * geo_tile_count(geo_tiles(nx, ny, nz))); }
+// the header (two list counts, padded to 16 words), then one flag word and one list word per tile, back to back
+GeoLayout geodesic_layout(int nx, int ny, int nz)
+{
+    GeoLayout L;
+    Carve c;
+    L.tiles = geo_tile_count(geo_tiles(nx, ny, nz));
+    L.header = c.take(4 * kGeoHeaderWords, 4);
+    L.flags = c.take(4 * L.tiles, 4);
+    L.list = c.take(4 * L.tiles, 4);
+    L.total = c.at;
+    return L;
+}
 
 hipError_t launch_geodesic_init(const uint8_t *free, int nx, int ny, int nz, const int32_t *seeds, int64_t n_seeds, int32_t *out_cost, void *workspace,
                                 hipStream_t s)
 {
     const GeoTiles G = geo_tiles(nx, ny, nz);
-    const int64_t n = (int64_t)nx * ny * nz, tiles = geo_tile_count(G);
-    uint32_t *header = static_cast<uint32_t *>(workspace);
-    uint32_t *flags = header + kGeoHeaderWords;
-    uint32_t *list = flags + tiles;
+    const GeoLayout L = geodesic_layout(nx, ny, nz);
+    const int64_t n = (int64_t)nx * ny * nz, tiles = L.tiles;
+    uint32_t *header = static_cast<uint32_t *>(ws_at(workspace, L.header));
+    uint32_t *flags = static_cast<uint32_t *>(ws_at(workspace, L.flags));
+    uint32_t *list = static_cast<uint32_t *>(ws_at(workspace, L.list));
     hipLaunchKernelGGL(geo_init_kernel, dim3(geo_blocks(std::max<int64_t>(std::max(n, tiles), kGeoHeaderWords))), dim3(kBlock), 0, s, out_cost, header, flags, n,
                        tiles);
     if (n_seeds > 0) hipLaunchKernelGGL(geo_seed_kernel, dim3(geo_blocks(n_seeds)), dim3(kBlock), 0, s, free, seeds, n_seeds, out_cost, flags, G, n);
@@ -359,10 +370,11 @@ hipError_t launch_geodesic_relax(const uint8_t *free, const int32_t *penalty, in
     P.penalty = penalty;
     P.cost = cost;
     P.G = geo_tiles(nx, ny, nz);
-    const int64_t tiles = geo_tile_count(P.G);
-    uint32_t *header = static_cast<uint32_t *>(workspace);
-    P.flags = header + kGeoHeaderWords;
-    uint32_t *list = P.flags + tiles;
+    const GeoLayout L = geodesic_layout(nx, ny, nz);
+    const int64_t tiles = L.tiles;
+    uint32_t *header = static_cast<uint32_t *>(ws_at(workspace, L.header));
+    P.flags = static_cast<uint32_t *>(ws_at(workspace, L.flags));
+    uint32_t *list = static_cast<uint32_t *>(ws_at(workspace, L.list));
     P.list = list;
     P.w1 = (uint32_t)w[0];
     P.w2 = (uint32_t)w[1];

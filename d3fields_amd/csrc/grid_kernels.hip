@@ -154,14 +154,32 @@ __global__ void grid_shell_total_kernel(const uint32_t *__restrict__ block_count
     *count = (unsigned long long)block_offsets[nb - 1] + block_counts[nb - 1];
 }
 
-int64_t grid_shell_workspace_bytes(int64_t n)
+// one 64-bit ballot per wave (not padded), one count and one offset per workgroup, the scan's scratch
+ShellLayout grid_shell_layout(int64_t n)
 {
-    const int64_t nb = (n + kBlock - 1) / kBlock;
-    return nb * (kBlock / 64) * 8 + 2 * ((nb * 4 + 255) / 256 * 256) + scan_scratch_bytes(nb);   // ballots + counts + offsets + scan scratch
+    ShellLayout L;
+    Carve c;
+    L.blocks = (n + kBlock - 1) / kBlock;
+    L.ballots = c.take(L.blocks * (kBlock / 64) * 8, 8);
+    L.counts = c.take(L.blocks * 4);
+    L.offsets = c.take(L.blocks * 4);
+    L.scan = c.take(scan_scratch_bytes(L.blocks));
+    L.total = c.at;
+    return L;
 }
 
-// tiled_scratch: nullptr, or depth_tiled_bytes(V, H, W) bytes BEHIND the workspace proper (d3f_grid_shell: the caller handed
-// over d3f_grid_shell_workspace_bytes + d3f_eval_dist_workspace_bytes)
+// the shell's workspace and, behind its bytes rounded up to 256 (the header's rule), the tiled copy of the depth maps
+ShellTiledLayout grid_shell_tiled_layout(int64_t n, int64_t tiled_bytes)
+{
+    ShellTiledLayout L;
+    Carve c;
+    L.shell = c.take(grid_shell_layout(n).total);
+    L.tiles = c.take(tiled_bytes, 1);
+    L.total = c.at;
+    return L;
+}
+
+// tiled_scratch: nullptr, or depth_tiled_bytes(V, H, W) bytes BEHIND the workspace proper (d3f_grid_shell: grid_shell_tiled_layout)
 hipError_t launch_grid_shell(const float *depth, const float *K, const float *pose, int V, int H, int W, const float *gx,
                              const float *gy, const float *gz, int nx, int ny, int nz, float mu, float dist_thr,
                              int64_t capacity, int64_t *idx_out, unsigned long long *count, void *workspace, hipStream_t s,
@@ -170,13 +188,12 @@ hipError_t launch_grid_shell(const float *depth, const float *K, const float *po
     const int64_t n = (int64_t)nx * ny * nz;
     hipError_t e = hipMemsetAsync(count, 0, sizeof(unsigned long long), s);
     if (e != hipSuccess || n == 0) return e;
-    const int64_t nb = (n + kBlock - 1) / kBlock;
-    unsigned char *base = static_cast<unsigned char *>(workspace);
-    unsigned long long *ballots = reinterpret_cast<unsigned long long *>(base);
-    const size_t seg = (size_t)((nb * 4 + 255) / 256 * 256);
-    uint32_t *counts = reinterpret_cast<uint32_t *>(base + nb * (kBlock / 64) * 8);
-    uint32_t *offsets = reinterpret_cast<uint32_t *>(base + nb * (kBlock / 64) * 8 + seg);
-    void *scratch = base + nb * (kBlock / 64) * 8 + 2 * seg;
+    const ShellLayout L = grid_shell_layout(n);
+    const int64_t nb = L.blocks;
+    unsigned long long *ballots = static_cast<unsigned long long *>(ws_at(workspace, L.ballots));
+    uint32_t *counts = static_cast<uint32_t *>(ws_at(workspace, L.counts));
+    uint32_t *offsets = static_cast<uint32_t *>(ws_at(workspace, L.offsets));
+    void *scratch = ws_at(workspace, L.scan);
     if (V <= 8 && n < 0xffffffffLL) {
         EvalParams P;
         memset(&P, 0, sizeof(P));
@@ -252,10 +269,15 @@ int64_t fps_blocks(int64_t n)
     return (n + per - 1) / per;
 }
 
-int64_t fps_workspace_bytes(int64_t n, int dist_bytes)
+// n distances, then two arrays of per-workgroup maxima (16 bytes each), 16-byte aligned
+FpsLayout fps_layout(int64_t n, int dist_bytes)
 {
-    // n distances, then two arrays of per-workgroup maxima (16 bytes each), 16-byte aligned
-    return (n * dist_bytes + 15) / 16 * 16 + 2 * kFpsMaxBlocks * 16;
+    FpsLayout L;
+    Carve c;
+    L.dist = c.take(n * dist_bytes, 16);
+    L.maxima = c.take(2 * kFpsMaxBlocks * 16, 16);
+    L.total = c.at;
+    return L;
 }
 
 template <typename M>
@@ -334,8 +356,9 @@ static hipError_t launch_fps_rounds(const typename M::coord_t *pts, int64_t n, i
                                     void *workspace, hipStream_t s)
 {
     using D = typename M::dist_t;
-    D *dist = static_cast<D *>(workspace);
-    FpsMax<M> *maxima = reinterpret_cast<FpsMax<M> *>(static_cast<char *>(workspace) + (n * (int64_t)sizeof(D) + 15) / 16 * 16);
+    const FpsLayout L = fps_layout(n, (int)sizeof(D));
+    D *dist = static_cast<D *>(ws_at(workspace, L.dist));
+    FpsMax<M> *maxima = static_cast<FpsMax<M> *>(ws_at(workspace, L.maxima));
     const int nb = (int)fps_blocks(n);
     for (int round = 0; round <= k; ++round)
         hipLaunchKernelGGL(fps_round_kernel<M>, dim3(round == k ? 1 : nb), dim3(kBlock), 0, s, pts, n, round, k, init_idx, out_idx, out_maxdist,

@@ -307,17 +307,21 @@ MeshParams mesh_params(const float *vol, const uint8_t *valid, int nx, int ny, i
     return P;
 }
 
-int64_t round256(int64_t b) { return (b + 255) / 256 * 256; }
-
 }  // namespace
 
 int64_t mesh_blocks(int64_t n) { return (n + kMeshPerBlock - 1) / kMeshPerBlock; }
 
 // two arrays of (workgroups + 1) words (vertex and triangle totals, scanned in place) + the scan's own scratch
-int64_t mesh_workspace_bytes(int64_t n)
+MeshLayout mesh_layout(int64_t n)
 {
-    const int64_t nb = mesh_blocks(n);
-    return 2 * round256((nb + 1) * 4) + scan_scratch_bytes(nb + 1);
+    MeshLayout L;
+    Carve c;
+    L.blocks = mesh_blocks(n);
+    L.voff = c.take((L.blocks + 1) * 4);
+    L.toff = c.take((L.blocks + 1) * 4);
+    L.scan = c.take(scan_scratch_bytes(L.blocks + 1));
+    L.total = c.at;
+    return L;
 }
 
 // counts_out: 2 x int64 on the device (vertices, triangles).  keys == nullptr: count only.
@@ -326,11 +330,11 @@ hipError_t launch_mesh(const float *vol, const uint8_t *valid, int nx, int ny, i
                        bool extract, hipStream_t s)
 {
     const MeshParams P = mesh_params(vol, valid, nx, ny, nz, iso);
-    const int64_t nb = mesh_blocks(P.n);
-    unsigned char *w = static_cast<unsigned char *>(workspace);
-    uint32_t *voff = reinterpret_cast<uint32_t *>(w);
-    uint32_t *toff = reinterpret_cast<uint32_t *>(w + round256((nb + 1) * 4));
-    void *scratch = w + 2 * round256((nb + 1) * 4);
+    const MeshLayout L = mesh_layout(P.n);
+    const int64_t nb = L.blocks;
+    uint32_t *voff = static_cast<uint32_t *>(ws_at(workspace, L.voff));
+    uint32_t *toff = static_cast<uint32_t *>(ws_at(workspace, L.toff));
+    void *scratch = ws_at(workspace, L.scan);
     hipLaunchKernelGGL(mesh_count_kernel, dim3((unsigned)nb), dim3(kBlock), 0, s, P, voff, toff, nb);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;

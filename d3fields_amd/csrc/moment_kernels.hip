@@ -35,16 +35,9 @@ constexpr int kMomSumSlabs = 2048;               // workgroups the column sums a
 constexpr int kMomScatterGroups = 1024;          // workgroups the scatter pass aims for
 constexpr int kMomMaxSlabs = 256;
 
-struct MomentPlan {
-    int panels, pairs, cpad;
-    int64_t sum_slabs, sum_rows;                 // pass 1: slabs and rows per slab
-    int64_t slabs, slab_rows;                    // pass 2
-    int64_t off_wsum_part, off_sum_part, off_wsum, off_m32, off_col_part, off_tiles, bytes;
-};
-
 static int64_t mom_ceil(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
-static MomentPlan moment_plan(int64_t M, int C)
+MomentPlan moment_plan(int64_t M, int C)
 {
     MomentPlan p;
     p.panels = (C + kMomPanel - 1) / kMomPanel;
@@ -58,15 +51,16 @@ static MomentPlan moment_plan(int64_t M, int C)
     if (want > kMomMaxSlabs) want = kMomMaxSlabs;
     p.slab_rows = mom_ceil(mom_ceil(M, want), kMomRows) * kMomRows;
     p.slabs = mom_ceil(M, p.slab_rows);
-    int64_t o = 0;
-    p.off_wsum = o; o += 8;                                                    // double
-    p.off_wsum_part = o; o += p.sum_slabs * 8;                                 // double [sum_slabs]
-    p.off_sum_part = o; o += p.sum_slabs * p.cpad * 8;                         // double [sum_slabs][cpad]
-    p.off_col_part = o; o += p.slabs * p.cpad * 8;                             // double [slabs][cpad]
-    p.off_tiles = o; o += p.slabs * p.pairs * (int64_t)(kMomPanel * kMomPanel) * 8;   // double [slabs][pairs][64][64]
-    o = (o + 15) / 16 * 16;
-    p.off_m32 = o; o += (int64_t)p.cpad * 4;                                   // float [cpad], 16-byte aligned
-    p.bytes = (o + 255) / 256 * 256;
+    Carve c;
+    p.off_wsum = c.take(8, 8);                                                          // double
+    p.off_wsum_part = c.take(p.sum_slabs * 8, 8);                                       // double [sum_slabs]
+    p.off_sum_part = c.take(p.sum_slabs * p.cpad * 8, 8);                               // double [sum_slabs][cpad]
+    p.off_col_part = c.take(p.slabs * p.cpad * 8, 8);                                   // double [slabs][cpad]
+    p.off_tiles = c.take(p.slabs * p.pairs * (int64_t)(kMomPanel * kMomPanel) * 8, 8);  // double [slabs][pairs][64][64]
+    c.take((16 - c.at % 16) % 16, 1);                                                   // m32 starts at a multiple of 16 (the doubles so far may be an odd number)
+    p.off_m32 = c.take((int64_t)p.cpad * 4, 4);                                         // float [cpad]
+    c.take((256 - c.at % 256) % 256, 1);                                                // the whole is a multiple of 256
+    p.bytes = c.at;
     return p;
 }
 
@@ -305,7 +299,6 @@ hipError_t launch_row_moments(const void *rows, bool half, int64_t M, int C, int
                               double *mean_out, double *scatter_out, void *workspace, hipStream_t s)
 {
     const MomentPlan p = moment_plan(M, C);
-    char *ws = static_cast<char *>(workspace);
     MomentArgs A;
     A.rows = static_cast<const char *>(rows);
     A.w = weights;
@@ -314,12 +307,12 @@ hipError_t launch_row_moments(const void *rows, bool half, int64_t M, int C, int
     A.vec = (reinterpret_cast<uintptr_t>(rows) % (half ? 8 : 16) == 0 && row_stride % 4 == 0) ? 1 : 0;
     A.panels = p.panels; A.pairs = p.pairs;
     A.sum_slabs = p.sum_slabs; A.sum_rows = p.sum_rows; A.slabs = p.slabs; A.slab_rows = p.slab_rows;
-    A.wsum = reinterpret_cast<double *>(ws + p.off_wsum);
-    A.wsum_part = reinterpret_cast<double *>(ws + p.off_wsum_part);
-    A.sum_part = reinterpret_cast<double *>(ws + p.off_sum_part);
-    A.col_part = reinterpret_cast<double *>(ws + p.off_col_part);
-    A.tiles = reinterpret_cast<double *>(ws + p.off_tiles);
-    A.m32 = reinterpret_cast<float *>(ws + p.off_m32);
+    A.wsum = static_cast<double *>(ws_at(workspace, p.off_wsum));
+    A.wsum_part = static_cast<double *>(ws_at(workspace, p.off_wsum_part));
+    A.sum_part = static_cast<double *>(ws_at(workspace, p.off_sum_part));
+    A.col_part = static_cast<double *>(ws_at(workspace, p.off_col_part));
+    A.tiles = static_cast<double *>(ws_at(workspace, p.off_tiles));
+    A.m32 = static_cast<float *>(ws_at(workspace, p.off_m32));
     A.wsum_out = wsum_out; A.mean_out = mean_out; A.scatter_out = scatter_out;
     hipLaunchKernelGGL(moment_sums_kernel, dim3((unsigned)((C + kMomBlock - 1) / kMomBlock), (unsigned)p.sum_slabs), dim3(kMomBlock), 0, s, A);
     hipLaunchKernelGGL(moment_mean_kernel, dim3((unsigned)((p.cpad + kMomBlock - 1) / kMomBlock)), dim3(kMomBlock), 0, s, A);

@@ -313,35 +313,22 @@ __global__ __launch_bounds__(kBlock) void motion_finish_kernel(const double *__r
     rmse[k] = s0 > 0.0 ? sqrt(s1 / s0) : __builtin_nan("");
 }
 
-inline int64_t motion_pad(int64_t bytes) { return (bytes + 255) / 256 * 256; }
+}  // namespace
 
-// what the workspace holds, in this order: the masked labels, the member list's pieces (pool_layout; a partial row is 16 float64), the sums,
-// the sums of the last pass, (pm, cm) per part
-struct MotionLayout {
-    int64_t lab, pool, sums, fsum, centre, total;
-    PoolLayout P;
-};
-
+// the masked labels, the member list's pieces (pool_layout; a partial row is 16 float64), the sums, the sums of the last pass, (pm, cm) per part
 MotionLayout motion_layout(int64_t n, int64_t K, int64_t cap)
 {
     MotionLayout L;
     L.P = pool_layout(n, K, cap, 2 * kSumRow);
-    int64_t at = 0;
-    auto take = [&](int64_t bytes) {
-        const int64_t here = at;
-        at += motion_pad(bytes);
-        return here;
-    };
-    L.lab = take(4 * n);
-    L.pool = take(L.P.total);
-    L.sums = take(8 * kSumRow * K);
-    L.fsum = take(8 * kFinalRow * K);
-    L.centre = take(8 * 6 * K);
-    L.total = at;
+    Carve c;
+    L.lab = c.take(4 * n);
+    L.pool = c.take(L.P.total);
+    L.sums = c.take(8 * kSumRow * K);
+    L.fsum = c.take(8 * kFinalRow * K);
+    L.centre = c.take(8 * 6 * K);
+    L.total = c.at;
     return L;
 }
-
-}  // namespace
 
 int64_t motion_workspace_bytes(int64_t n, int64_t K, int64_t cap) { return motion_layout(n, K, std::min(cap, n)).total; }
 

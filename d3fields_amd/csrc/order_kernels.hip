@@ -84,8 +84,6 @@ constexpr float kFineCell = 0.004f;       // the coarsest fine cell: 4 mm x 512 
 constexpr int64_t kCells = 1 << 21;
 constexpr int kExactCell = 256;           // cells of more points than this are ranked in aligned pieces of this many slots
 
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 // ---- the cloud's bounding box (round 5) -----------------------------------------------------------------------------------------
 // The keys of rounds 1-4 quantised the coordinates on a FIXED 4-mm grid of 512^3 cells (2.05 m): a cloud in the reference's
 // 0.8 x 0.7 x 0.22 m workspace occupies 1.4 % of that key space, its ~30 k occupied 16-mm counting cells take ~33 points each,
@@ -245,23 +243,25 @@ __global__ __launch_bounds__(kBlock) void cell_rank_kernel(const unsigned long l
     order[s + rank] = (uint32_t)mine;
 }
 
-int64_t order_workspace_bytes(int64_t n)
+// keys | ranks | order | slots | cell counters | their scan's scratch | gate words | the partial boxes of order_prepare_kernel
+OrderLayout order_layout(int64_t n)
 {
-    if (n <= 0) return 0;
-    // keys | ranks | order | slots (8-byte (key, index) words: two segments) | cell counters + scan scratch
-    // | 256 bytes of gate words | the partial boxes of order_prepare_kernel
-    return (int64_t)(5 * align_up((size_t)n * 4, 256) + (size_t)kCells * 4 + (size_t)scan_scratch_bytes(kCells) + 256 + (size_t)kBoxParts * kBoxLanes * 4);
+    OrderLayout L;
+    Carve c;
+    L.keys = c.take(4 * n);
+    L.ranks = c.take(4 * n);
+    L.order = c.take(4 * n);
+    L.slots = c.take(4 * n);        // n 8-byte (key, index) words as TWO padded segments of 4 n bytes: pad256(8 n) is less (n = 1: 256 against 512)
+    c.take(4 * n);
+    L.table = c.take(kCells * 4);
+    L.scan = c.take(scan_scratch_bytes(kCells));
+    L.gate = c.take(256);
+    L.parts = c.take(kBoxParts * kBoxLanes * 4);
+    L.total = c.at;
+    return L;
 }
 
-int64_t order_gate_offset(int64_t n)
-{
-    return (int64_t)(5 * align_up((size_t)n * 4, 256) + (size_t)kCells * 4 + (size_t)scan_scratch_bytes(kCells));
-}
-
-uint32_t *order_gate_words(void *workspace, int64_t n)
-{
-    return reinterpret_cast<uint32_t *>(static_cast<unsigned char *>(workspace) + order_gate_offset(n));
-}
+int64_t order_workspace_bytes(int64_t n) { return n <= 0 ? 0 : order_layout(n).total; }
 
 // Fills *order_out with a pointer (inside the workspace) to n uint32 indices in Hilbert-cell order.
 // curve: 0 = Hilbert (the product's); experiments builds: bit 0 = Morton (the order of rounds 1-4), bit 1 = the three-launch scan,
@@ -271,13 +271,12 @@ hipError_t build_point_order(const float *pts, int64_t n, void *workspace, int64
 {
     *order_out = nullptr;
     if (n <= 0 || n > 0x7fffffffLL || workspace_bytes < order_workspace_bytes(n)) return hipErrorInvalidValue;
-    const size_t seg = align_up((size_t)n * 4, 256);
-    unsigned char *base = static_cast<unsigned char *>(workspace);
-    uint32_t *keys = reinterpret_cast<uint32_t *>(base), *ranks = reinterpret_cast<uint32_t *>(base + seg);
-    uint32_t *order = reinterpret_cast<uint32_t *>(base + 2 * seg);
-    unsigned long long *slots = reinterpret_cast<unsigned long long *>(base + 3 * seg);      // n 8-byte words: segments 3 and 4
-    uint32_t *table = reinterpret_cast<uint32_t *>(base + 5 * seg);
-    void *scan_scratch = base + 5 * seg + (size_t)kCells * 4;
+    const OrderLayout L = order_layout(n);
+    uint32_t *keys = static_cast<uint32_t *>(ws_at(workspace, L.keys)), *ranks = static_cast<uint32_t *>(ws_at(workspace, L.ranks));
+    uint32_t *order = static_cast<uint32_t *>(ws_at(workspace, L.order));
+    unsigned long long *slots = static_cast<unsigned long long *>(ws_at(workspace, L.slots));
+    uint32_t *table = static_cast<uint32_t *>(ws_at(workspace, L.table)), *gate = static_cast<uint32_t *>(ws_at(workspace, L.gate));
+    void *scan_scratch = ws_at(workspace, L.scan);
     const unsigned nb = (unsigned)((n + kBlock - 1) / kBlock);
     // counters: >= 2 per point (any prefix of the key is a valid coarser cell of the curve), 2^15 .. 2^20 -- clearing and scanning
     // the table must not dominate small batches, and with the grid laid over the cloud's box 2 per point already leave ~4 points
@@ -292,7 +291,7 @@ hipError_t build_point_order(const float *pts, int64_t n, void *workspace, int64
     const int status_words = (int)scan_status_words(cells);
     // ONE launch: the counters, gate and status words cleared AND the cloud's box as <= 128 partial boxes; then keys on a grid laid over
     // the box (experiments builds: bit 2 = the fixed 4-mm grid of rounds 1-4, bit 0 = Morton keys on it)
-    uint32_t *parts = (curve & 5) ? nullptr : order_gate_words(workspace, n) + 64;
+    uint32_t *parts = (curve & 5) ? nullptr : static_cast<uint32_t *>(ws_at(workspace, L.parts));
     int nparts = 0;
     if (parts) {
         nparts = (int)((n + (int64_t)kBoxBlock * 8 - 1) / ((int64_t)kBoxBlock * 8));
@@ -300,7 +299,7 @@ hipError_t build_point_order(const float *pts, int64_t n, void *workspace, int64
     }
     const int clear_blocks = (int)(cells / 4 / kBoxBlock);
     hipLaunchKernelGGL(order_prepare_kernel, dim3((unsigned)(clear_blocks + nparts)), dim3(kBoxBlock), 0, stream, table,
-                       order_gate_words(workspace, n), status, status_words, clear_blocks, pts, n, parts);
+                       gate, status, status_words, clear_blocks, pts, n, parts);
     if (curve & 1) hipLaunchKernelGGL(cell_count_kernel<true>, dim3(nb), dim3(kBlock), 0, stream, pts, n, keys, ranks, table, shift, parts, nparts);
     else hipLaunchKernelGGL(cell_count_kernel<false>, dim3(nb), dim3(kBlock), 0, stream, pts, n, keys, ranks, table, shift, parts, nparts);
     // n < 2^31 points: the counts sum to n; the look-back scan carries 30-bit values -- above 2^30 points the recursive scan
@@ -314,12 +313,6 @@ hipError_t build_point_order(const float *pts, int64_t n, void *workspace, int64
     // the finished order always sits in the same place, so that a later call can find it again (D3F_FLAG_REUSE_POINT_ORDER)
     *order_out = order;
     return hipSuccess;
-}
-
-// where build_point_order leaves the order inside a workspace of order_workspace_bytes(n)
-const uint32_t *stored_point_order(void *workspace, int64_t n)
-{
-    return reinterpret_cast<const uint32_t *>(static_cast<unsigned char *>(workspace) + 2 * align_up((size_t)n * 4, 256));
 }
 
 // ---- does the caller's order have spatial locality? ------------------------------------------------

@@ -89,9 +89,20 @@ __global__ __launch_bounds__(kBlock) void backproject_write_kernel(const Backpro
         *total = prefix + wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
 }
 
+// one count per workgroup of 256 pixels, and one word more that nothing reads
+PixelCountsLayout pixel_counts_layout(int64_t npix)
+{
+    PixelCountsLayout L;
+    Carve c;
+    L.blocks = (npix + kBlock - 1) / kBlock;
+    L.counts = c.take((L.blocks + 1) * 8, 8);
+    L.total = c.at;
+    return L;
+}
+
 hipError_t launch_backproject(const double *depth, const uint8_t *mask, int H, int W, const double *cam, const double *T,
                               const double *bounds, int64_t capacity, double *out_pts, int32_t *out_pixel, int64_t *count,
-                              int64_t *block_counts, hipStream_t s)
+                              void *workspace, hipStream_t s)
 {
     BackprojectParams P;
     P.depth = depth; P.mask = mask; P.npix = (int64_t)H * W; P.W = W;
@@ -99,7 +110,9 @@ hipError_t launch_backproject(const double *depth, const uint8_t *mask, int H, i
     for (int k = 0; k < 12; ++k) P.T[k] = T[k];
     P.crop = bounds ? 1 : 0;
     for (int k = 0; k < 3; ++k) { P.lo[k] = bounds ? bounds[2 * k] : 0.0; P.hi[k] = bounds ? bounds[2 * k + 1] : 0.0; }
-    const unsigned nb = (unsigned)((P.npix + kBlock - 1) / kBlock);
+    const PixelCountsLayout L = pixel_counts_layout(P.npix);
+    int64_t *block_counts = static_cast<int64_t *>(ws_at(workspace, L.counts));
+    const unsigned nb = (unsigned)L.blocks;
     hipLaunchKernelGGL(backproject_count_kernel, dim3(nb), dim3(kBlock), 0, s, P, block_counts);
     hipLaunchKernelGGL(backproject_write_kernel, dim3(nb), dim3(kBlock), 0, s, P, block_counts, capacity, out_pts, out_pixel, count);
     return hipGetLastError();

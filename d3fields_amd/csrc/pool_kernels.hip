@@ -430,8 +430,6 @@ __global__ __launch_bounds__(kBlock) void pool_finish_kernel(float *__restrict__
     }
 }
 
-inline int64_t pool_pad(int64_t bytes) { return (bytes + 255) / 256 * 256; }
-
 unsigned pool_grid(int64_t items)
 {
     return (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + kBlock - 1) / kBlock, 1 << 20));
@@ -449,28 +447,25 @@ int pool_levels(int64_t cap)
 PoolLayout pool_layout(int64_t n, int64_t K, int64_t cap, int64_t pitch)
 {
     PoolLayout L;
-    int64_t at = 0;
-    auto take = [&](int64_t bytes) {
-        const int64_t here = at;
-        at += pool_pad(bytes);
-        return here;
-    };
-    L.flag = take(4 * n);
-    L.flag_scan = take(scan_scratch_bytes(n));
-    for (int b = 0; b < 2; ++b) L.keys[b] = take(4 * cap), L.vals[b] = take(4 * cap);
+    Carve c;
+    L.flag = c.take(4 * n);
+    L.flag_scan = c.take(scan_scratch_bytes(n));
+    for (int b = 0; b < 2; ++b) L.keys[b] = c.take(4 * cap), L.vals[b] = c.take(4 * cap);
     L.waves_total = (cap + kSortSpan - 1) / kSortSpan;
     L.waves_total = (L.waves_total + 3) / 4 * 4;
-    L.counters = take(4 * 256 * L.waves_total);
-    L.counters_scan = take(scan_scratch_bytes(256 * L.waves_total));
-    L.plan = take(8 * pool_pad(4 * (K + 1)));
-    L.plan_scan = take(scan_scratch_bytes(K + 1));
+    L.counters = c.take(4 * 256 * L.waves_total);
+    L.counters_scan = c.take(scan_scratch_bytes(256 * L.waves_total));
+    L.first = c.take(4 * (K + 1));
+    for (int l = 0; l < 4; ++l) L.work[l] = c.take(4 * (K + 1));
+    for (int l = 0; l < 3; ++l) L.part[l] = c.take(4 * (K + 1));
+    L.plan_scan = c.take(scan_scratch_bytes(K + 1));
     // partial rows: a component writes ceil(count / 256^(l+1)) of them at level l where that is more than one, so at most
     // capacity / 256^(l+1) + (the components with more than 256^(l+1) members) <= 2 * capacity / 256^(l+1); levels 0 and 2 share buffer a
     L.rows_a = cap > kPoolChunk ? 2 * (cap >> 8) + 2 : 0;
     L.rows_b = cap > 65536 ? 2 * (cap >> 16) + 2 : 0;
-    L.rows[0] = take(4 * pitch * L.rows_a);
-    L.rows[1] = take(4 * pitch * L.rows_b);
-    L.total = at;
+    L.rows[0] = c.take(4 * pitch * L.rows_a);
+    L.rows[1] = c.take(4 * pitch * L.rows_b);
+    L.total = c.at;
     return L;
 }
 
@@ -524,11 +519,10 @@ hipError_t launch_pool_members(const int32_t *label, const uint8_t *valid, const
 
     // where every component's members, chunks and partial rows start
     const int levels = cap > 0 ? pool_levels(cap) : 0;
-    const int64_t plan_pitch = pool_pad(4 * ((int64_t)K + 1));
     PoolPlan plan;
-    plan.first = reinterpret_cast<uint32_t *>(ws + L.plan);
-    for (int l = 0; l < 4; ++l) plan.work[l] = reinterpret_cast<uint32_t *>(ws + L.plan + (1 + l) * plan_pitch);
-    for (int l = 0; l < 3; ++l) plan.part[l] = reinterpret_cast<uint32_t *>(ws + L.plan + (5 + l) * plan_pitch);
+    plan.first = reinterpret_cast<uint32_t *>(ws + L.first);
+    for (int l = 0; l < 4; ++l) plan.work[l] = reinterpret_cast<uint32_t *>(ws + L.work[l]);
+    for (int l = 0; l < 3; ++l) plan.part[l] = reinterpret_cast<uint32_t *>(ws + L.part[l]);
     hipLaunchKernelGGL(pool_prep_kernel, dim3((unsigned)(((int64_t)K + 1 + kBlock - 1) / kBlock)), block, 0, s, out_count, out_members, cap, K, levels, plan);
     e = hipGetLastError();
     if (e != hipSuccess) return e;

@@ -131,29 +131,42 @@ hipError_t launch_exclusive_scan_lookback_u32(const uint32_t *in, uint32_t *out,
     return hipGetLastError();
 }
 
-int64_t scan_scratch_bytes(int64_t n)
+// level l holds the blocks[l] workgroup sums of the level above it (level 0: of the n items); 2048^6 > 2^63 items
+ScanLayout scan_layout(int64_t n)
 {
-    int64_t total = 0;
+    ScanLayout L;
+    Carve c;
+    L.levels = 0;
     while (n > kScanPerBlock) {
         n = (n + kScanPerBlock - 1) / kScanPerBlock;
-        total += (n * 4 + 255) / 256 * 256;
+        L.blocks[L.levels] = n;
+        L.sums[L.levels++] = c.take(n * 4);
     }
-    return total + 256;
+    L.spare = c.take(256);      // unused by the scan; the point order's single-launch scan keeps its status words from offset 0 through here
+    L.total = c.at;
+    return L;
+}
+
+int64_t scan_scratch_bytes(int64_t n) { return scan_layout(n).total; }
+
+// the n items of level l: scanned per workgroup, the workgroup sums scanned by the level below (in place) and added back
+static hipError_t scan_level(const uint32_t *in, uint32_t *out, int64_t n, void *scratch, const ScanLayout &L, int l, hipStream_t s)
+{
+    uint32_t *sums = l < L.levels ? static_cast<uint32_t *>(ws_at(scratch, L.sums[l])) : nullptr;
+    const int64_t nb = sums ? L.blocks[l] : 1;
+    hipLaunchKernelGGL(scan_block_kernel, dim3((unsigned)nb), dim3(kBlock), 0, s, in, out, sums, n);
+    if (sums) {
+        hipError_t e = scan_level(sums, sums, nb, scratch, L, l + 1, s);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(scan_add_kernel, dim3((unsigned)nb), dim3(kBlock), 0, s, out, sums, n);
+    }
+    return hipGetLastError();
 }
 
 hipError_t launch_exclusive_scan_u32(const uint32_t *in, uint32_t *out, int64_t n, void *scratch, hipStream_t s)
 {
     if (n <= 0) return hipSuccess;
-    const int64_t nb = (n + kScanPerBlock - 1) / kScanPerBlock;
-    uint32_t *sums = static_cast<uint32_t *>(scratch);
-    hipLaunchKernelGGL(scan_block_kernel, dim3((unsigned)nb), dim3(kBlock), 0, s, in, out, nb > 1 ? sums : nullptr, n);
-    if (nb > 1) {
-        unsigned char *next = static_cast<unsigned char *>(scratch) + (nb * 4 + 255) / 256 * 256;
-        hipError_t e = launch_exclusive_scan_u32(sums, sums, nb, next, s);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(scan_add_kernel, dim3((unsigned)nb), dim3(kBlock), 0, s, out, sums, n);
-    }
-    return hipGetLastError();
+    return scan_level(in, out, n, scratch, scan_layout(n), 0, s);
 }
 
 }  // namespace d3f

@@ -11,6 +11,11 @@ an accumulator) passes -- and one that needs ``~0`` (the empty slot of a hash ta
     replay()     to the k-th allocation of this run the very storage the k-th allocation of the run before had -- still holding
                  what that run left there -- provided shape, dtype and device are the same; otherwise a fresh 0xFF-filled tensor.
                  "The run before" is the previous ``with`` block of the same DirtyBuffers, whatever its mode.
+    guarded()    tensors of zeros that are views into a larger buffer, with ``GUARD`` bytes of ``GUARD_BYTE`` in front of them and
+                 behind them: does an entry point write outside the bytes it asked for?  The view starts at a multiple of 256 bytes
+                 (the allocator's blocks start at multiples of 512 and GUARD is one), so the alignment rules of the C boundary hold
+                 as they do for a tensor of its own.  ``damage()`` lists, after the run, every allocation with a changed guard byte.
+                 A stray write lands in memory this allocator owns.
 
 No aliasing: every tensor a run hands out stays referenced until the run after the next begins, so the allocator underneath cannot
 give one block to two allocations of a run, and a replayed storage is handed out once per run (to the allocation with its index).
@@ -26,6 +31,10 @@ import torch
 __all__ = ["DirtyBuffers"]
 
 
+GUARD = 4096
+GUARD_BYTE = 0xA5
+
+
 class DirtyBuffers:
     def __init__(self, monkeypatch):
         self._monkeypatch = monkeypatch
@@ -36,8 +45,9 @@ class DirtyBuffers:
         self._current = None         # the tensors of the run in progress
         self.replayed = 0            # of the run in progress / the last run: allocations that got an old storage
         self.fresh = 0               # ... and those that got a new one
+        self._guards = []            # guarded(): (the whole buffer as uint8, where the view starts in it, the view's bytes) per allocation, in order
 
-    # ---- the three modes ----------------------------------------------------------------------------------------------------
+    # ---- the four modes -----------------------------------------------------------------------------------------------------
     def fill(self, byte):
         if not 0 <= int(byte) <= 0xFF:
             raise ValueError("fill byte outside 0..255")
@@ -45,6 +55,20 @@ class DirtyBuffers:
 
     def replay(self):
         return self._run(self._replayed)
+
+    def guarded(self):
+        self._guards = []
+        return self._run(self._guarded)
+
+    def damage(self):
+        """of the last guarded run: (allocation index, its bytes, "front" / "back", changed guard bytes, offset of the first from the view's start)"""
+        found = []
+        for k, (whole, start, nbytes) in enumerate(self._guards):
+            for side, first in (("front", start - GUARD), ("back", start + nbytes)):
+                bad = torch.nonzero(whole[first:first + GUARD] != GUARD_BYTE).reshape(-1)
+                if bad.numel():
+                    found.append((k, nbytes, side, int(bad.numel()), first + int(bad[0]) - start))
+        return found
 
     # ---- one run --------------------------------------------------------------------------------------------------------------
     @contextlib.contextmanager
@@ -92,6 +116,20 @@ class DirtyBuffers:
             self._bytes_of(t).fill_(byte)
         self.fresh += 1
         return t
+
+    def _guarded(self, k, t):
+        nbytes = t.untyped_storage().nbytes()
+        whole = self._real_empty(GUARD + 256 + nbytes + GUARD, dtype=torch.uint8, device=t.device)
+        start = GUARD + (-whole.data_ptr()) % 256          # (0 more on the device; a host block may start anywhere)
+        assert t.storage_offset() == 0 and start % t.element_size() == 0, "the view would not start where a tensor of its own does"
+        whole.fill_(GUARD_BYTE)
+        whole[start:start + nbytes].zero_()
+        view = self._real_empty(0, dtype=t.dtype, device=t.device).set_(whole.untyped_storage(), start // t.element_size(), t.shape, t.stride())
+        if t.requires_grad:
+            view.requires_grad_(True)
+        self._guards.append((whole, start, nbytes))
+        self.fresh += 1
+        return view
 
     def _replayed(self, k, t):
         old = self._previous[k] if k < len(self._previous) else None

@@ -1,10 +1,10 @@
 """tests/dirty_buffers.py on CPU tensors: the fills are what they claim for every dtype the wrappers allocate, replay returns the
-storages of the run before in order, a mismatch falls back to a fresh 0xFF tensor, nothing live is aliased, and the patches are gone
-when the block ends."""
+storages of the run before in order, a mismatch falls back to a fresh 0xFF tensor, nothing live is aliased, the guarded mode reports a byte
+written in front of or behind a tensor and nothing else, and the patches are gone when the block ends."""
 import pytest
 import torch
 
-from dirty_buffers import DirtyBuffers
+from dirty_buffers import GUARD, DirtyBuffers
 
 # every dtype a wrapper of d3fields_amd passes to torch.empty
 DTYPES = [torch.bool, torch.uint8, torch.int8, torch.int16, torch.uint16, torch.int32, torch.int64, torch.float16, torch.float32,
@@ -141,6 +141,41 @@ def test_nothing_live_is_aliased(monkeypatch):
         second = spans(15)                                   # ten replayed, five fresh
         assert db.replayed == 10 and db.fresh == 5
         assert second[:10] == first and disjoint(second)
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=lambda d: str(d).split(".")[1])
+def test_guarded_tensors_are_zeros_at_256_bytes_and_whole_writes_leave_no_damage(monkeypatch, dtype):
+    db = DirtyBuffers(monkeypatch)
+    with db.guarded():
+        a = torch.empty((3, 5), dtype=dtype)
+        b = torch.empty_like(a)
+        c = a.new_empty(0)
+        d = a.new_empty(1000, dtype=torch.float32, requires_grad=True)
+        for t in (a, b, c, d):
+            assert t.data_ptr() % 256 == 0 and t.is_contiguous() and not bool(raw(t.detach()).any())
+        assert d.requires_grad and (a.shape, a.dtype, c.numel()) == ((3, 5), dtype, 0)
+        raw(a).fill_(0xFF)
+        raw(b).fill_(0x17)
+        d.detach().fill_(3.0)
+    assert db.fresh == 4 and db.damage() == []
+
+
+def test_guarded_reports_a_write_in_front_and_behind(monkeypatch):
+    db = DirtyBuffers(monkeypatch)
+    with db.guarded():
+        a = torch.empty(100, dtype=torch.int32)
+        b = torch.empty(7, dtype=torch.uint8)
+        c = torch.empty(64, dtype=torch.float64)
+        whole_a, start_a, _ = db._guards[0]
+        whole_c, start_c, _ = db._guards[2]
+        whole_a[start_a + 400] = 0                      # the first byte behind a's 400
+        whole_a[start_a + 400 + GUARD - 1] = 1          # and the last of that guard
+        whole_c[start_c - 1] = 2                        # the last byte in front of c
+        b.fill_(9)
+    assert db.damage() == [(0, 400, "back", 2, 400), (2, 512, "front", 1, -1)]
+    with db.guarded():
+        torch.empty(3)
+    assert db.damage() == [], "a new guarded run starts a new list"
 
 
 def test_runs_do_not_nest(monkeypatch):

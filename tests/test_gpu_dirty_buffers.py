@@ -48,6 +48,20 @@ def compare(case, what, a, b):
                                   x.reshape(-1)[at:at + 4].tolist(), y.reshape(-1)[at:at + 4].tolist()))
 
 
+def run_case(case, db, mode, inp, keep=True):
+    with mode:
+        try:
+            out = case.run(inp)
+            torch.cuda.synchronize()
+        except RuntimeError as e:                    # a device fault poisons the process: nothing more is started on the device
+            if any(w in str(e) for w in ("HIP error", "hipError", "illegal memory access", "status -5")):
+                pytest.exit("device fault in case %r: %s" % (case.name, e), returncode=3)
+            raise
+    handed = db.fresh + db.replayed
+    got = {k: v.detach().clone() for k, v in out.items()} if keep else None        # (cloned before the next run takes the storages)
+    return got, handed
+
+
 @pytest.mark.parametrize("case", DC.ALL, ids=lambda c: c.name)
 def test_same_bytes_whatever_the_buffers_held(dev, monkeypatch, case):
     a, b = case.inputs()
@@ -55,17 +69,7 @@ def test_same_bytes_whatever_the_buffers_held(dev, monkeypatch, case):
     t0 = time.perf_counter()
 
     def run(mode, inp, keep=True):
-        with mode:
-            try:
-                out = case.run(inp)
-                torch.cuda.synchronize()
-            except RuntimeError as e:                    # a device fault poisons the process: nothing more is started on the device
-                if any(w in str(e) for w in ("HIP error", "hipError", "illegal memory access", "status -5")):
-                    pytest.exit("device fault in case %r: %s" % (case.name, e), returncode=3)
-                raise
-        handed = db.fresh + db.replayed
-        got = {k: v.detach().clone() for k, v in out.items()} if keep else None        # (cloned before the next run takes the storages)
-        return got, handed
+        return run_case(case, db, mode, inp, keep)
 
     zeros, n0 = run(db.fill(0x00), a)
     ones, n1 = run(db.fill(0xFF), a)
@@ -85,4 +89,23 @@ def test_same_bytes_whatever_the_buffers_held(dev, monkeypatch, case):
                 raise AssertionError((case.name, "the feature's own comparison fails on the %s run" % what) + e.args)
     if case.large:
         del zeros, ones, again
+        torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("case", DC.ALL, ids=lambda c: c.name)
+def test_nothing_is_written_outside_the_buffers(dev, monkeypatch, case):
+    """every buffer a view with 4 KiB of a fixed byte in front and behind (DirtyBuffers.guarded): the guards come back whole -- no entry point
+    writes outside the bytes its *_workspace_bytes function or its output's shape asked for -- and the outputs are those of the 0x00 run"""
+    a, _ = case.inputs()
+    db = DirtyBuffers(monkeypatch)
+    t0 = time.perf_counter()
+    zeros, n0 = run_case(case, db, db.fill(0x00), a)
+    guarded, n1 = run_case(case, db, db.guarded(), a)
+    damage = db.damage()
+    print("%s: %d buffers behind guards, %.2f s" % (case.name, n1, time.perf_counter() - t0))
+    assert n0 == n1 > 0, (case.name, "the runs ask for different numbers of buffers", n0, n1)
+    assert not damage, (case.name, "(allocation, its bytes, side, changed guard bytes, offset of the first from the buffer's start)", damage)
+    compare(case, "0x00 against the guarded run", zeros, guarded)
+    if case.large:
+        del zeros, guarded, db
         torch.cuda.empty_cache()
