@@ -48,6 +48,7 @@ FLOW_MAX_RADIUS = 4
 MOTION_OK, MOTION_THINNED, MOTION_TOO_FEW = 0, 1, 2
 MOTION_MAX_FITS = 8
 MOTION_SUM_DOUBLES, MOTION_POSE_DOUBLES = 16, 15
+WARP_MAX_PARTS = 4096
 KERNEL_NAME_MAX = 80
 GAUSSIAN_MAX_RADIUS = 64
 DTYPE_F32 = 0
@@ -93,6 +94,18 @@ class VolumeSet(ctypes.Structure):
 class Band(ctypes.Structure):
     """struct d3f_band"""
     _fields_ = [("slot", _vp), ("cell_band", _vp), ("n_rows", _i64)]
+
+
+class WarpSelect(ctypes.Structure):
+    """struct d3f_warp_select (host memory)"""
+    _fields_ = [("vol", Volume), ("owner", _vp), ("pose", _vp), ("K", _i32), ("reserved", _i32), ("out_source", _vp), ("out_dist", _vp), ("out_valid", _vp),
+                ("out_boxes", _vp)]
+
+
+class WarpRows(ctypes.Structure):
+    """struct d3f_warp_rows (host memory)"""
+    _fields_ = [("vol", Volume), ("band", ctypes.POINTER(Band)), ("sets", ctypes.POINTER(VolumeSet)), ("n_sets", _i32), ("K", _i32), ("source", _vp), ("pose", _vp),
+                ("voxels", _vp), ("m", _i64), ("out_sets", ctypes.POINTER(_vp)), ("out_known", _vp)]
 
 
 class Pinhole(ctypes.Structure):
@@ -169,6 +182,8 @@ SIGNATURES = {
     "d3f_part_motion_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32, _i64]),
     "d3f_part_motion": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _f64, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                        _vp, _i64, _vp]),
+    "d3f_volume_warp_select": (ctypes.c_int, [ctypes.POINTER(WarpSelect), _vp]),
+    "d3f_volume_warp_rows": (ctypes.c_int, [ctypes.POINTER(WarpRows), _vp]),
     "d3f_volume_pool_workspace_bytes":(_i64, [_i32, _i32, _i32, _i32, _i64, _i64]),
     "d3f_volume_pool": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, ctypes.POINTER(VolumeSet), _i32, ctypes.POINTER(_i32), _i64, _vp, _vp, _vp,
                                        ctypes.POINTER(_vp), _vp, _i64, _vp]),

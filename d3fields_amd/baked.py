@@ -37,6 +37,11 @@ target, the cost, a sub-voxel offset, world displacements and the forward-backwa
 trim-and-refit loop on the device (d3f_part_motion, csrc/motion_kernels.hip) -- a `PartMotions` with a rotation, a
 translation, an inlier count, an rmse and a verdict per part, and the residual and inlier volumes; the same bytes on every run.
 
+`BakedField.warp(motions, owner)` answers "where is it now?": this field as it would look after every part has moved by its rigid motion
+(d3f_volume_warp_select / d3f_volume_warp_rows, csrc/warp_kernels.hip) -- an ordinary field on the same grid, dense or
+banded as this one, with the part each voxel came from; `owners(parts, margin_voxels=)` grows the part labels by a margin so that the free side
+of a part's surface travels with it.
+
 `BakedField.travel(goals, radius=)` answers "how do I get there, and how far is it along the way": the cost-to-go field of a goal set
 through the free voxels (d3f_volume_geodesic_*, csrc/geodesic_kernels.hip) -- exact shortest lattice paths with
 integer weights, as a new field whose `dist` is the travel distance and whose `next_voxel` names the voxel to step to; `path(starts)`
@@ -409,6 +414,11 @@ class BakedField:
     peaks(values, ...) gives the spatially distinct local optima of value columns on any field; locate(descriptors, name, ...) the k best
     spatially distinct matches of reference descriptors among the rows of a set.
 
+    A WARPED field (warp()) is an ordinary dense or banded field that also has source int32 [nx, ny, nz] (0: the voxel stayed, k: it came from
+    part k, -1: nothing is known there), rows_known bool ([nx, ny, nz], or [M] on a banded field: False where the row is the fill row),
+    part_box_from and part_box_to int32 [K, 2, 3] (the inclusive boxes of each part's owner voxels and of the voxels it won; an empty box is
+    lo = INT32_MAX, hi = INT32_MIN).  They are None elsewhere.
+
     A BANDED field (to_band / Fusion.bake(band=)) holds each set as [M, C] rows of the stored voxels instead, and has
     band (the world length), slot int32 [nx, ny, nz] (-1: no row), cell_band uint8 [nx-1, ny-1, nz-1], band_voxels int32 [M]
     (ascending flat indices), band_points() and stored_fraction; its lookups add 'in_band'.  A dense field has band = None.
@@ -433,6 +443,7 @@ class BakedField:
         self.band = self.slot = self.cell_band = self.band_voxels = None
         self.d2 = self.nearest_voxel = self.sites = None      # a clearance field's (clearance()); None on every other field
         self.cost = self.next_voxel = self.free = None         # a travel field's (travel()); None on every other field
+        self.source = self.rows_known = self.part_box_from = self.part_box_to = None      # a warped field's (warp()); None on every other field
         self.cell_valid = torch.empty((nx - 1, ny - 1, nz - 1), dtype=torch.uint8, device=self.device)
         vol = self._volume()
         with torch.cuda.device(self.device):
@@ -929,6 +940,126 @@ class BakedField:
             _lib.check(self._lib.d3f_volume_flow(_lib.ptr(site_a), _lib.ptr(self.slot), set_a, _lib.ptr(site_b), _lib.ptr(other.slot), set_b, nx, ny, nz,
                                                  radius_voxels, max_cost2, _lib.ptr(target), _lib.ptr(cost), _lib.ptr(axis), _lib.current_stream_handle(dev)))
         return Flow(self.origin, self.step, target, cost, axis)
+
+    # ---- warp -----------------------------------------------------------------------------------------------------------------
+    def _check_label_volume(self, who, what, t):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != tuple(self.grid_shape):
+            raise ValueError("%s: %s must be an int32 tensor of shape %s, got %s" % (
+                who, what, tuple(self.grid_shape), "%s %s" % (t.dtype, tuple(t.shape)) if isinstance(t, torch.Tensor) else type(t).__name__))
+        if t.device != self.device:
+            raise ValueError("%s: %s is on %s, the field on %s" % (who, what, t.device, self.device))
+        return t.detach()
+
+    def _check_same_grid(self, who, what, other):
+        if tuple(other.grid_shape) != tuple(self.grid_shape) or tuple(other.origin) != self.origin or float(other.step) != self.step:
+            raise ValueError("%s: %s is of a grid %s at %s step %g, the field of %s at %s step %g" % (
+                who, what, tuple(other.grid_shape), tuple(other.origin), other.step, tuple(self.grid_shape), self.origin, self.step))
+
+    def owners(self, parts, margin_voxels=2):
+        """Which part does each voxel travel with? -> int32 [nx, ny, nz]: every voxel within margin_voxels (a Euclidean distance in voxels) of a
+        part's voxels gets the label of its nearest part voxel (among equidistant ones the transform's own choice, the same on every run), all
+        other voxels 0.  parts: a Components on this grid or an int32 label volume.  The margin is what carries the free side of a part's
+        surface along with it in warp(); margin_voxels = 0 returns the labels themselves.  One clearance(sites=, max_distance=) and one gather."""
+        if isinstance(parts, Components):
+            self._check_same_grid("owners", "parts", parts)
+            labels = parts.labels
+        else:
+            labels = parts
+        labels = self._check_label_volume("owners", "the labels", labels)
+        if isinstance(margin_voxels, bool) or not isinstance(margin_voxels, (int, float)) or not (0.0 <= float(margin_voxels) < math.inf):
+            raise ValueError("owners: margin_voxels must be a finite number >= 0, got %r" % (margin_voxels,))
+        cap = min(math.floor(float(margin_voxels) ** 2), 2 ** 31 - 2)
+        if cap < 1:
+            return labels
+        # (the cap the transform derives is floor((max_distance / step)^2): aim at cap + 1/2, which no rounding of the quotient moves across an integer)
+        c = self.clearance(sites=labels > 0, max_distance=self.step * math.sqrt(cap + 0.5))
+        near = c.nearest_voxel
+        got = labels.reshape(-1)[torch.clamp(near, min=0).long()]
+        return torch.where((near >= 0) & (c.d2 <= cap), got, torch.zeros_like(got))
+
+    def warp(self, motions, owner, which=None, return_names=None):
+        """Where is it now?  This field after every part has moved by its rigid motion (d3f_volume_warp_select / d3f_volume_warp_rows,
+        csrc/warp_kernels.hip) -> a BakedField on the same grid, dense where this one is dense, banded with the same
+        band where it is banded (select, d3f_band_mark on the new dist, then the rows of the stored voxels only: no dense row array exists).
+
+        motions       a PartMotions of this grid (Flow.motions), or a float64 [K, 15] pose tensor laid out as PartMotions.pose
+        owner         int32 [nx, ny, nz]: the part each voxel travels with (owners(parts)), or a Components whose labels are taken as they are
+        which         None, or bool [K], e.g. motions.moved(min_shift=0.5 * field.step): the parts not selected stay put and are not resampled
+        return_names  the sets the result holds (None: every set of this field)
+        A part without a pose (a NaN row) does not move.  Per destination voxel the candidates are the voxel itself, if it is valid and its
+        owner does not move, and every moving part whose inverse motion puts the voxel next to one of the part's own voxels; the smallest
+        signed distance wins, ties go to the background, then to the lower part.  A voxel a part has left is unknown (not valid): what was
+        behind the part was never observed.  Rows are copied (background) or blended from eight corner rows (moved) in float32 without fused
+        operations.  The result also has source, rows_known, part_box_from, part_box_to (see the class).  No host read on a dense field, the
+        one of d3f_band_mark on a banded one.  Not differentiable."""
+        if isinstance(motions, PartMotions):
+            self._check_same_grid("warp", "motions", motions)
+            pose = motions.pose
+        elif isinstance(motions, torch.Tensor):
+            pose = motions
+        else:
+            raise ValueError("warp: motions must be a PartMotions or a float64 [K, %d] pose tensor, got %r" % (_lib.MOTION_POSE_DOUBLES, type(motions).__name__))
+        if pose.dtype != torch.float64 or pose.dim() != 2 or pose.shape[1] != _lib.MOTION_POSE_DOUBLES:
+            raise ValueError("warp: the poses must be a float64 [K, %d] tensor, got %s %s" % (_lib.MOTION_POSE_DOUBLES, pose.dtype, tuple(pose.shape)))
+        K = pose.shape[0]
+        if K > _lib.WARP_MAX_PARTS:
+            raise ValueError("warp: %d parts, at most %d: select the movers with which= and compact the labels" % (K, _lib.WARP_MAX_PARTS))
+        if pose.device != self.device:
+            raise ValueError("warp: the poses are on %s, the field on %s" % (pose.device, self.device))
+        if isinstance(owner, Components):
+            self._check_same_grid("warp", "owner", owner)
+            if owner.count != K:
+                raise ValueError("warp: owner has %d parts, there are %d poses" % (owner.count, K))
+            owner = owner.labels
+        owner = self._check_label_volume("warp", "owner", owner)
+        if which is not None:
+            if not isinstance(which, torch.Tensor) or which.dtype != torch.bool or tuple(which.shape) != (K,):
+                raise ValueError("warp: which must be a bool [%d] tensor, one entry per pose" % K)
+            if which.device != self.device:
+                raise ValueError("warp: which is on %s, the field on %s" % (which.device, self.device))
+        names = self._names(return_names)
+        dev = self.device
+        if dev.type != "cuda":
+            raise RuntimeError("warp: the field must live on the ROCm device; there is no CPU path")
+        nx, ny, nz = self.grid_shape
+        n = nx * ny * nz
+        pose = pose.detach().contiguous()
+        if which is not None:
+            pose = torch.where(which[:, None], pose, torch.full_like(pose, math.nan))
+        owner = owner.contiguous()
+        source = torch.empty((nx, ny, nz), dtype=torch.int32, device=dev)
+        dist = torch.empty((nx, ny, nz), dtype=torch.float32, device=dev)
+        valid = torch.empty((nx, ny, nz), dtype=torch.uint8, device=dev)
+        boxes = torch.empty((K, 12), dtype=torch.int32, device=dev)
+        sel = _lib.WarpSelect(self._volume(), _lib.ptr(owner), _lib.ptr(pose) if K else None, K, 0, _lib.ptr(source), _lib.ptr(dist), _lib.ptr(valid),
+                              _lib.ptr(boxes) if K else None)
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.d3f_volume_warp_select(ctypes.byref(sel), _lib.current_stream_handle(dev)))
+        moved = type(self)(self.origin, self.step, dist, valid.view(torch.bool), {}, {}, boundaries=self.boundaries, axes=self._axes)
+        if self.band is None:
+            mark, voxels, m = None, None, n
+        else:
+            mark = moved._mark(self.band)
+            voxels, m = mark[2], mark[2].shape[0]
+        known = torch.empty(m, dtype=torch.uint8, device=dev)
+        rows = {k: torch.empty((m, self._channels(k)), dtype=torch.float32, device=dev) for k in names}
+        if m > 0:
+            outs = (ctypes.c_void_p * max(len(names), 1))(*[rows[k].data_ptr() for k in names])
+            band = None if self.band is None else self._band_struct()
+            args = _lib.WarpRows(self._volume(), None if band is None else ctypes.pointer(band), self._set_array(names), len(names), K, _lib.ptr(source),
+                                 _lib.ptr(pose) if K else None, _lib.ptr(voxels), m, outs, _lib.ptr(known))
+            with torch.cuda.device(dev):
+                _lib.check(self._lib.d3f_volume_warp_rows(ctypes.byref(args), _lib.current_stream_handle(dev)))
+        fills = {k: self._fills[k] for k in names}
+        if self.band is None:
+            moved._sets, moved._fills = {k: rows[k].view(nx, ny, nz, -1) for k in names}, fills
+            moved.rows_known = known.view(torch.bool).view(nx, ny, nz)
+        else:
+            moved = moved._banded(self.band, mark, rows, fills)
+            moved.rows_known = known.view(torch.bool)
+        moved.source = source
+        moved.part_box_from, moved.part_box_to = boxes[:, 0:6].reshape(K, 2, 3), boxes[:, 6:12].reshape(K, 2, 3)
+        return moved
 
     def components(self, iso=0.0, unknown="free", connectivity=26, min_voxels=1, sites=None, links=None):
         """The connected components of the occupied voxels (d3f_volume_components) -> Components.

@@ -1095,6 +1095,99 @@ int d3f_part_motion(const int32_t *label, int32_t K, int32_t nx, int32_t ny, int
     return e == hipSuccess ? D3F_OK : hip_fail(e, "part_motion launch");
 }
 
+// ---- a baked field moved by the rigid motions of its parts (warp_kernels.hip) ----
+// the parts of both calls: K, then the pose rows
+static int check_warp_parts(const char *who, int32_t K)
+{
+    if (K < 0) return fail(D3F_ERR_INVALID_ARG, "%s: K=%d is negative", who, K);
+    if (K > D3F_WARP_MAX_PARTS) return fail(D3F_ERR_BAD_SHAPE, "%s: K=%d exceeds D3F_WARP_MAX_PARTS=%d", who, K, D3F_WARP_MAX_PARTS);
+    return D3F_OK;
+}
+
+int d3f_volume_warp_select(const d3f_warp_select *args, void *stream)
+{
+    const char *who = "volume_warp_select";
+    if (!args) return fail(D3F_ERR_INVALID_ARG, "%s: args is NULL", who);
+    const d3f_volume *vol = &args->vol;
+    if (const int rc = check_volume(who, vol)) return rc;
+    if (const int rc = check_warp_parts(who, args->K)) return rc;
+    if (!vol->dist || !vol->valid || !vol->cell_valid || !args->owner) return fail(D3F_ERR_INVALID_ARG, "%s: vol.dist / vol.valid / vol.cell_valid / owner must be non-NULL", who);
+    if (args->K > 0 && (!args->pose || !args->out_boxes)) return fail(D3F_ERR_INVALID_ARG, "%s: pose / out_boxes must be non-NULL with K=%d", who, args->K);
+    if (!args->out_source || !args->out_dist || !args->out_valid) return fail(D3F_ERR_INVALID_ARG, "%s: out_source / out_dist / out_valid must be non-NULL", who);
+    if (!aligned(vol->dist, 4) || !aligned(args->owner, 4) || !aligned(args->pose, 8) || !aligned(args->out_source, 4) || !aligned(args->out_dist, 4) ||
+        !aligned(args->out_boxes, 4))
+        return fail(D3F_ERR_BAD_LAYOUT, "%s: vol.dist / owner / pose / out_source / out_dist / out_boxes must be aligned to their element size", who);
+    d3f::WarpSelectArgs A;
+    A.dist = vol->dist;
+    A.valid = vol->valid;
+    A.cell_valid = vol->cell_valid;
+    A.owner = args->owner;
+    A.pose = args->pose;
+    A.nx = vol->nx; A.ny = vol->ny; A.nz = vol->nz; A.K = args->K;
+    A.out_source = args->out_source;
+    A.out_dist = args->out_dist;
+    A.out_valid = args->out_valid;
+    A.out_boxes = args->out_boxes;
+    hipError_t e = d3f::launch_warp_select(A, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_warp_select launch");
+}
+
+int d3f_volume_warp_rows(const d3f_warp_rows *args, void *stream)
+{
+    const char *who = "volume_warp_rows";
+    if (!args) return fail(D3F_ERR_INVALID_ARG, "%s: args is NULL", who);
+    const d3f_volume *vol = &args->vol;
+    const d3f_band *band = args->band;
+    if (const int rc = check_volume(who, vol)) return rc;
+    if (band && (band->n_rows < 0 || band->n_rows > 0x7fffffffLL))
+        return fail(D3F_ERR_BAD_SHAPE, "%s: band->n_rows=%lld outside [0, 2^31 - 1]", who, (long long)band->n_rows);
+    if (const int rc = check_warp_parts(who, args->K)) return rc;
+    const int64_t n = (int64_t)vol->nx * vol->ny * vol->nz;
+    if (args->m < 0) return fail(D3F_ERR_INVALID_ARG, "%s: m=%lld is negative", who, (long long)args->m);
+    if (!args->voxels && args->m != n) return fail(D3F_ERR_INVALID_ARG, "%s: m=%lld with voxels NULL, must be the voxel count %lld", who, (long long)args->m, (long long)n);
+    const int32_t n_sets = args->n_sets;
+    if (n_sets < 0 || n_sets > D3F_MAX_MAPS) return fail(D3F_ERR_BAD_SHAPE, "%s: n_sets=%d outside [0,%d]", who, n_sets, D3F_MAX_MAPS);
+    if (n_sets > 0 && !args->sets) return fail(D3F_ERR_INVALID_ARG, "%s: sets is NULL with n_sets=%d", who, n_sets);
+    for (int s = 0; s < n_sets; ++s)
+        if (const int rc = check_set_shape(who, s, args->sets[s])) return rc;
+    if (args->m == 0) return D3F_OK;
+    const bool empty = band && band->n_rows == 0;
+    if (!args->source || !args->out_known || (args->K > 0 && !args->pose) || (n_sets > 0 && !args->out_sets))
+        return fail(D3F_ERR_INVALID_ARG, "%s: source / out_known / pose (with K > 0) / out_sets must be non-NULL", who);
+    if (band && !empty && (!band->slot || !band->cell_band)) return fail(D3F_ERR_INVALID_ARG, "%s: band->slot / band->cell_band must be non-NULL with n_rows > 0", who);
+    if (!aligned(args->source, 4) || !aligned(args->pose, 8) || !aligned(args->voxels, 4) || (band && !empty && !aligned(band->slot, 4)))
+        return fail(D3F_ERR_BAD_LAYOUT, "%s: source / pose / voxels / band->slot must be aligned to their element size", who);
+    d3f::WarpRowsArgs A;
+    for (int s = 0; s < n_sets; ++s) {
+        const d3f_volume_set &set = args->sets[s];
+        if (!set.data && !empty) return fail(D3F_ERR_INVALID_ARG, "%s: set %d: data is NULL", who, s);
+        if (const int rc = check_set_layout(who, s, set)) return rc;
+        if (!aligned(set.fill, 4)) return fail(D3F_ERR_BAD_LAYOUT, "%s: set %d: fill must be 4-byte aligned", who, s);
+        if (!args->out_sets[s]) return fail(D3F_ERR_INVALID_ARG, "%s: out_sets[%d] is NULL", who, s);
+        if (!aligned(args->out_sets[s], 4)) return fail(D3F_ERR_BAD_LAYOUT, "%s: out_sets[%d] must be 4-byte aligned", who, s);
+        d3f::VolSet &S = A.sets[s];
+        S.data = set.data;
+        S.fill = set.fill;
+        S.out = static_cast<float *>(args->out_sets[s]);
+        S.grad = nullptr;
+        S.stride = set.stride_voxel;
+        S.C = set.C;
+        S.vec = set_reads_vectors(set) && aligned(args->out_sets[s], 16) ? 1 : 0;
+    }
+    A.source = args->source;
+    A.pose = args->pose;
+    A.voxels = args->voxels;
+    A.m = args->m;
+    A.nx = vol->nx; A.ny = vol->ny; A.nz = vol->nz; A.K = args->K;
+    A.banded = band != nullptr;
+    A.slot = band && !empty ? band->slot : nullptr;
+    A.cell_band = band && !empty ? band->cell_band : nullptr;
+    A.n_sets = n_sets;
+    A.out_known = args->out_known;
+    hipError_t e = d3f::launch_warp_rows(A, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_warp_rows launch");
+}
+
 // ---- cost-to-go through free space (geodesic_kernels.hip) ----
 static int check_geo_weights(const char *who, int32_t connectivity, const int32_t *w)
 {

@@ -351,6 +351,34 @@ MotionLayout motion_layout(int64_t n, int64_t K, int64_t cap);
 int64_t motion_workspace_bytes(int64_t n, int64_t K, int64_t cap);          // cap clamped to n, then motion_layout(n, K, cap).total
 hipError_t launch_part_motion(const MotionArgs &A, hipStream_t s);
 
+// warp_kernels.hip: a baked field moved by the rigid motions of its parts
+struct WarpSelectArgs {
+    const float *dist;
+    const uint8_t *valid, *cell_valid;
+    const int32_t *owner;
+    const double *pose;          // [K, 15] on the device
+    int32_t nx, ny, nz, K;
+    int32_t *out_source;
+    float *out_dist;
+    uint8_t *out_valid;
+    int32_t *out_boxes;          // [K, 12]
+};
+struct WarpRowsArgs {
+    const int32_t *source;
+    const double *pose;
+    const int32_t *voxels;       // or nullptr: every voxel in flat order (m = the voxel count)
+    int64_t m;
+    int32_t nx, ny, nz, K;
+    bool banded;
+    const int32_t *slot;         // banded: nullptr with no stored voxel
+    const uint8_t *cell_band;
+    int32_t n_sets;
+    VolSet sets[D3F_MAX_MAPS];   // data, fill, out, stride, C, vec
+    uint8_t *out_known;
+};
+hipError_t launch_warp_select(const WarpSelectArgs &A, hipStream_t s);
+hipError_t launch_warp_rows(const WarpRowsArgs &A, hipStream_t s);
+
 // geodesic_kernels.hip: cost-to-go through free space, exact shortest paths on the lattice; w: host int32[3]
 struct GeoLayout { int64_t header, flags, list, total; int64_t tiles; };
 GeoLayout geodesic_layout(int nx, int ny, int nz);

@@ -944,6 +944,76 @@ int d3f_part_motion(const int32_t *label, int32_t K, int32_t nx, int32_t ny, int
                     double *out_pose, int32_t *out_inliers, double *out_rmse, int32_t *out_status, int32_t *out_fits, double *out_residual2,
                     uint8_t *out_inlier, double *out_sums, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* (still ABI 16: symbols added -- two entry points, two HOST argument structs and one constant; no earlier struct or entry point changes and
+ * D3F_ABI_VERSION stays 16; a client detects the feature by the symbols.)  Where is it now?  A baked field moved by the rigid motions of its parts
+ * (csrc/warp_kernels.hip): per destination voxel who wins, then each stored row gathered once.
+ * Coordinates are voxel index units, the flat index is v = (x*ny + y)*nz + z.  No operation below is fused; every float equals the NumPy
+ * restatement (tests/warp_cases.py) byte for byte.
+ *   source field  vol: nx, ny, nz, dist, valid, cell_valid as d3f_volume_sample takes them (origin and step are not read);
+ *   owner         int32 [nx,ny,nz];  K in 0..D3F_WARP_MAX_PARTS;  pose float64 [K,15] ON THE DEVICE, a row as d3f_part_motion writes it: R row-major,
+ *                 src, dst with q = R (p - src) + dst.  R is trusted to be a rotation: its transpose is used as its inverse.  For any other matrix
+ *                 the result is unspecified, but every access stays in bounds.
+ *   moving        part k (1..K) moves iff all 15 entries of row k-1 are finite; a voxel is moving when its owner is a moving part.  Owner values
+ *                 outside 1..K and the voxels of parts that do not move are BACKGROUND: they stay where they are.
+ *   inverse map   of destination voxel q under part k, float64, one rounding per operation:  u = q - dst;
+ *                 p_i = ((R_0i*u_0 + R_1i*u_1) + R_2i*u_2) + src_i;  inside: 0 <= p_a <= n_a - 1 on the three axes (NaN is not inside);
+ *                 i_a = min(floor(p_a), n_a - 2);  t_a = float32(p_a - i_a);  the nearest corner is i_a + (t_a > 0.5f).
+ *   candidate k   exists when p is inside, cell_valid[i] is set, owner[nearest corner] == k and the interpolated distance is not NaN.
+ *   interpolation the weights w(dx,dy,dz) of d3f_volume_sample (products left to right); acc = w0*v0, then acc = acc + w_c*v_c for c = 1..7 in that
+ *                 sampler's corner order, each product and each sum rounded to float32 (NOT the fused chain of d3f_volume_sample).
+ *   candidate 0   the background: the voxel itself with dist[q], when valid[q], q is not moving and dist[q] is not NaN.  A voxel a moving part has
+ *                 left has no background: what was behind the part was never observed.
+ *   winner        candidates in the order 0, 1, ..., K; a later one replaces the best only if its distance is strictly smaller: the union of the
+ *                 moved solids (the minimum of signed distances), ties to the lower index.
+ * d3f_volume_warp_select writes, completely: out_source int32 [nx,ny,nz] (0 background, k part k, -1 none); out_dist float32 (1e3 where the source
+ * is -1); out_valid uint8 (source >= 0); out_boxes int32 [K,12], per part {lo xyz, hi xyz} of its owner == k voxels, then {lo xyz, hi xyz} of the
+ * destination voxels it won, inclusive; an empty box is lo = INT32_MAX, hi = INT32_MIN.  K == 0: pose and out_boxes may be NULL.
+ * Three launches on `stream` (the boxes' init, the owner boxes, one workgroup per tile of 4 x 8 x 8 destination voxels that culls the parts 64 per
+ * wave step against the owner boxes -- exactly: the map is affine -- and walks the survivors in ascending order).  Integer atomic min / max for the
+ * boxes only; no float atomic, no workspace, no allocation, no synchronisation; two runs give identical bytes.
+ * d3f_volume_warp_rows produces the rows of m listed destination voxels (voxels int32 [m], any order, duplicates allowed; NULL: every voxel in flat
+ * order, m must be nx*ny*nz; an entry outside the volume gets fill rows) from `source` as select wrote it, for n_sets in 0..D3F_MAX_MAPS sets:
+ *   source -1     the set's fill row (NULL: zeros); out_known = 0;
+ *   source 0      the stored row of q, copied.  Banded (band != NULL): the row slot[q]; slot[q] < 0: fill, out_known = 0;
+ *   source k      p, i, t recomputed by the same expressions, then the same unfused chain over the eight corner rows per channel.  Banded: only when
+ *                 cell_band[i] is set, rows through slot; otherwise fill, out_known = 0.  (A source value outside -1..K, or an image that is not
+ *                 inside, is answered with fill rows.)
+ * out_sets[s]: float32 [m, sets[s].C], C-contiguous; out_known one byte per listed voxel.  vol gives the extents only (no array of it is read).
+ * Banded with n_rows == 0: slot, cell_band and every data may be NULL, nothing of the band is read.  m == 0: D3F_OK, nothing is read.  The 16-byte
+ * vector / scalar rule, the boundary between <= 16 and wider channel counts (one lane / sixteen lanes per voxel) and stride_voxel >= C are as in
+ * d3f_volume_sample.  One launch; no atomics.
+ * Status errors, nothing launched: a NULL struct, NULL owner / out_source / out_dist / out_valid / source / out_known, NULL pose or out_boxes with
+ * K > 0, K < 0, m < 0, voxels NULL with m != nx*ny*nz, NULL sets / out_sets / an out_sets entry / a set's data (D3F_ERR_INVALID_ARG); an extent below
+ * 2, more than 2^31 - 1 voxels, K > D3F_WARP_MAX_PARTS, n_sets or a C out of range (D3F_ERR_BAD_SHAPE); stride_voxel < C, a pointer not aligned to
+ * its element (D3F_ERR_BAD_LAYOUT). */
+#define D3F_WARP_MAX_PARTS 4096
+typedef struct d3f_warp_select {
+    d3f_volume vol;
+    const int32_t *owner;
+    const double *pose;
+    int32_t K;
+    int32_t reserved;          /* 0 */
+    int32_t *out_source;
+    float *out_dist;
+    uint8_t *out_valid;
+    int32_t *out_boxes;
+} d3f_warp_select;
+typedef struct d3f_warp_rows {
+    d3f_volume vol;
+    const d3f_band *band;      /* NULL: a dense source */
+    const d3f_volume_set *sets;
+    int32_t n_sets;
+    int32_t K;
+    const int32_t *source;
+    const double *pose;
+    const int32_t *voxels;
+    int64_t m;
+    void *const *out_sets;
+    uint8_t *out_known;
+} d3f_warp_rows;
+int d3f_volume_warp_select(const d3f_warp_select *args, void *stream);
+int d3f_volume_warp_rows(const d3f_warp_rows *args, void *stream);
+
 /* (ABI 12) The first surface a ray meets in a baked volume: a fixed-step march through `dist` with one linear interpolation at the
  * sign change.  Everything in fp32.  Ray i is p(t) = o + t*d; d need not be unit.
  *   once per ray: go_a = (o_a - origin_a) / h, gd_a = d_a / h (IEEE divisions), len = sqrtf(fma(d_z, d_z, fma(d_y, d_y, d_x*d_x)));
