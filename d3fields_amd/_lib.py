@@ -5,7 +5,10 @@ an error status, an exception is raised.  Nothing in this package computes the f
 the CPU or through torch ops.
 """
 import ctypes
+import functools
 import os
+
+import torch
 
 from . import build as _build
 
@@ -257,6 +260,20 @@ SIGNATURES = {
     "d3f_softmax_apply": (ctypes.c_int, [_vp, _i64, _i64, _f32, _vp, _vp]),
 }
 
+# the entry points whose declaration ends in `void *stream` (names without their d3f_ prefix): on() fills that argument in
+STREAMED = frozenset("d3f_" + n for n in """
+    eval map_check map_check_many project_maps row_moments eval_grid eval_lattice lattice_probe grid_shell mesh_count mesh_extract volume_gaussian
+    volume_cell_valid volume_sample volume_sample_backward band_mark band_sample band_sample_backward volume_edt volume_components volume_components_linked
+    volume_links volume_flow part_motion volume_warp_select volume_warp_rows volume_pool volume_geodesic_init volume_geodesic_relax volume_geodesic_finish
+    volume_follow volume_segments path_shorten volume_peaks volume_align_centroid volume_align_accumulate volume_align_step pose_consensus_score
+    pose_consensus_select pose_refit volume_raycast farthest_point_sampling backproject_view pcd_nearest pcd_to_index vox_idx_iou erode compose_labels
+    voxel_downsample mask_gate nonzero_pixels fps_pixels eval_backward eval_dist_backward eval_dist onehot2instance instance2onehot similarity_to_target
+    pairwise_similarity pairwise_similarity_topk topk_smallest topk_merge pairwise_softmax_local point_order_locality points_probe rigid_transform
+    track_loss_grad track_step track_run rigid_update softmax_merge softmax_apply
+""".split())
+# the others that return a status; everything else returns a value
+STATUS = STREAMED | {"d3f_eval_plan_query", "d3f_eval_plan_query_lattice"}
+
 _lib = None
 
 
@@ -308,5 +325,60 @@ def ptr(t):
 
 
 def current_stream_handle(device):
-    import torch
     return _vp(torch.cuda.current_stream(device).cuda_stream)
+
+
+class on:
+    """Calls into the library on one device, on its current stream:
+
+        with _lib.on(dev) as q:
+            ws, ws_bytes = q.workspace("d3f_volume_edt_workspace_bytes", nx, ny, nz)
+            q.d3f_volume_edt(site, nx, ny, nz, step, max_d2, d2, nearest, dist, ws, ws_bytes)
+
+    Entering sets the device and reads its current stream once; every call in the block shares that stream, and the entry points in
+    STREAMED receive it as their last argument.  A tensor goes in as its address, a Structure by reference, everything else (None, ctypes
+    arrays and pointers, numbers, host addresses) as it is.  A tensor that is not on the device is refused before anything is launched;
+    converting and checking the arguments touches no GPU state.  A status other than OK raises D3FError."""
+
+    def __init__(self, device, lib=None):
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.lib = load() if lib is None else lib
+
+    def __enter__(self):
+        self._guard = torch.cuda.device(self.device)
+        self._guard.__enter__()
+        self.stream = current_stream_handle(self.device)
+        return self
+
+    def __exit__(self, *exc):
+        return self._guard.__exit__(*exc)
+
+    def __getattr__(self, name):
+        if name not in SIGNATURES:
+            raise AttributeError(name)
+        return functools.partial(self._call, name)
+
+    def _call(self, name, *args):
+        conv = []
+        for a in args:
+            if isinstance(a, torch.Tensor):
+                if not a.is_cuda or a.device != self.device:     # (host memory goes in as a ctypes array or an address, never as a tensor)
+                    raise RuntimeError("%s: argument %d is a tensor on %s; this call runs on %s" % (name, len(conv), a.device, self.device))
+                a = _vp(a.data_ptr())
+            elif isinstance(a, ctypes.Structure):
+                a = ctypes.byref(a)
+            conv.append(a)
+        if name in STREAMED:
+            conv.append(self.stream)
+        out = getattr(self.lib, name)(*conv)
+        if name in STATUS:
+            return check(out)
+        return out
+
+    def workspace(self, size_fn, *args):
+        """(uint8 tensor on the device, the byte count size_fn(*args) gave): at least 16 bytes are allocated, so that the address is never
+        NULL -- the library refuses a NULL workspace even where it needs no bytes"""
+        nbytes = int(self._call(size_fn, *args))
+        return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.device), nbytes

@@ -22,8 +22,6 @@ deletion list more than once and then takes its successor with it; an empty-vs-e
 tests/golden/align_v3_*.npz hold the reference's instances and label images for synthetic detections (CPU restatement:
 oracle/np_assoc.py, never imported here).
 """
-import ctypes
-
 import numpy as np
 import torch
 
@@ -134,7 +132,6 @@ def _device_tensor(x, dev):
 
 def paint_label_images(fusion, instances):
     """-> curr_obs_torch['mask'] = (V,H,W) uint8 device tensor: per view, detection idx[view] of instance k painted with k."""
-    lib = _lib.load()
     dev = torch.device(fusion.device)
     obs = fusion.curr_obs_torch
     out = torch.empty((fusion.num_cam, fusion.H, fusion.W), dtype=torch.uint8, device=dev)      # (d3f_compose_labels writes every pixel of every view)
@@ -147,9 +144,8 @@ def paint_label_images(fusion, instances):
             if view in inst["idx"]:
                 owner[inst["idx"][view]] = k
         owner_d = torch.from_numpy(owner).to(dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.d3f_compose_labels(_lib.ptr(dets), ctypes.c_int32(dets.shape[0]), dets.shape[1], _lib.ptr(owner_d),
-                                              _lib.ptr(out[view]), _lib.current_stream_handle(dev)))
+        with _lib.on(dev) as q:
+            q.d3f_compose_labels(dets, dets.shape[0], dets.shape[1], owner_d, out[view])
     obs["mask"] = out
     return out
 

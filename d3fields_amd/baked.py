@@ -301,7 +301,6 @@ class Flow:
             raise ValueError("motions: this flow was computed with refine=False; pass refined=False")
         if not dev.type == "cuda":
             raise RuntimeError("motions: the flow must live on the ROCm device; there is no CPU path")
-        lib = _lib.load()
         labels = labels.contiguous()
         target = self.target.contiguous()
         offset = self.offset.contiguous() if refined else None
@@ -324,13 +323,10 @@ class Flow:
             passes = (labels > 0) & (target >= 0)
             capacity = int((passes if keep is None else passes & keep).sum())
             members = torch.empty(1, dtype=torch.int64, device=dev)
-            ws_bytes = int(lib.d3f_part_motion_workspace_bytes(nx, ny, nz, K, capacity))
-            ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-            with torch.cuda.device(dev):
-                _lib.check(lib.d3f_part_motion(_lib.ptr(labels), K, nx, ny, nz, _lib.ptr(keep8), _lib.ptr(target), _lib.ptr(offset), _lib.ptr(ref), fits, tau2,
-                                               min_pairs, capacity, _lib.ptr(members), _lib.ptr(pairs), _lib.ptr(pose), _lib.ptr(inliers), _lib.ptr(rmse),
-                                               _lib.ptr(status), _lib.ptr(done), _lib.ptr(res2), _lib.ptr(inlier), None, _lib.ptr(ws), ws_bytes,
-                                               _lib.current_stream_handle(dev)))
+            with _lib.on(dev) as q:
+                ws, ws_bytes = q.workspace("d3f_part_motion_workspace_bytes", nx, ny, nz, K, capacity)
+                q.d3f_part_motion(labels, K, nx, ny, nz, keep8, target, offset, ref, fits, tau2, min_pairs, capacity, members, pairs, pose, inliers, rmse, status,
+                                  done, res2, inlier, None, ws, ws_bytes)
         return PartMotions(self.origin, self.step, pose, pairs, inliers, done, rmse, status, res2, inlier.view(torch.bool))
 
 
@@ -445,9 +441,8 @@ class BakedField:
         self.cost = self.next_voxel = self.free = None         # a travel field's (travel()); None on every other field
         self.source = self.rows_known = self.part_box_from = self.part_box_to = None      # a warped field's (warp()); None on every other field
         self.cell_valid = torch.empty((nx - 1, ny - 1, nz - 1), dtype=torch.uint8, device=self.device)
-        vol = self._volume()
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.d3f_volume_cell_valid(ctypes.byref(vol), _lib.ptr(self.cell_valid), _lib.current_stream_handle(self.device)))
+        with self._on() as q:
+            q.d3f_volume_cell_valid(self._volume(), self.cell_valid)
 
     # ---- construction ---------------------------------------------------------------------------------------------------------
     @classmethod
@@ -540,19 +535,17 @@ class BakedField:
         cell_band = torch.empty((nx - 1, ny - 1, nz - 1), dtype=torch.uint8, device=dev)
         slot = torch.empty((nx, ny, nz), dtype=torch.int32, device=dev)
         count = torch.empty(1, dtype=torch.int64, device=dev)        # (d3f_band_mark always writes it)
-        ws_bytes = int(self._lib.d3f_band_workspace_bytes(nx, ny, nz))
-        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
         vol = self._volume()
         capacity = min(n, max(1 << 12, n // 8))
-        while True:
-            voxels = torch.empty(capacity, dtype=torch.int32, device=dev)
-            with torch.cuda.device(dev):
-                _lib.check(self._lib.d3f_band_mark(ctypes.byref(vol), float(band), _lib.ptr(cell_band), _lib.ptr(slot), _lib.ptr(voxels), capacity,
-                                                   _lib.ptr(count), _lib.ptr(ws), ws_bytes, _lib.current_stream_handle(dev)))
-            found = int(count.item())
-            if found <= capacity:
-                break
-            capacity = found
+        with self._on() as q:
+            ws, ws_bytes = q.workspace("d3f_band_workspace_bytes", nx, ny, nz)
+            while True:
+                voxels = torch.empty(capacity, dtype=torch.int32, device=dev)
+                q.d3f_band_mark(vol, float(band), cell_band, slot, voxels, capacity, count, ws, ws_bytes)
+                found = int(count.item())
+                if found <= capacity:
+                    break
+                capacity = found
         return cell_band, slot, voxels[:found].clone() if found < capacity else voxels
 
     def _voxel_centres(self, voxels):
@@ -624,6 +617,9 @@ class BakedField:
         f = self._fills[name]
         return torch.zeros(self._channels(name), dtype=torch.float32, device=self.device) if f is None else f
 
+    def _on(self):
+        return _lib.on(self.device, self._lib)
+
     def _volume(self):
         nx, ny, nz = self.grid_shape
         return _lib.Volume(nx, ny, nz, (ctypes.c_float * 3)(*self.origin), self.step, 0, _lib.ptr(self.dist), _lib.ptr(self.valid),
@@ -635,15 +631,6 @@ class BakedField:
             t = self._sets[k]
             arr[s] = _lib.VolumeSet(t.data_ptr(), t.shape[-1], 0, t.stride(-2), _lib.ptr(self._fills[k]))      # dense: the voxel stride; banded: the row stride
         return arr
-
-    def _check_query(self, pts):
-        assert type(pts) == torch.Tensor
-        assert len(pts.shape) == 2
-        assert pts.shape[1] == 3
-        if not pts.is_cuda or pts.device != self.device:
-            raise RuntimeError("BakedField.eval: pts must be on %s (where the volume lives); there is no CPU path" % self.device)
-        if pts.dtype != torch.float32:
-            raise TypeError("BakedField.eval: pts must be float32, got %s" % pts.dtype)
 
     def _names(self, return_names):
         names = self.names() if return_names is None else list(return_names)
@@ -664,23 +651,19 @@ class BakedField:
         for s, k in enumerate(names):
             out[k] = torch.empty((n, self._channels(k)), dtype=torch.float32, device=dev)
             outs[s] = out[k].data_ptr()
-        vol = self._volume()
-        with torch.cuda.device(dev):
+        with self._on() as q:
             if self.band is None:
-                _lib.check(self._lib.d3f_volume_sample(ctypes.byref(vol), _lib.ptr(pts_c), n, self._set_array(names), len(names), _lib.ptr(out["dist"]),
-                                                       _lib.ptr(out["valid_mask"]), outs, _lib.current_stream_handle(dev)))
+                q.d3f_volume_sample(self._volume(), pts_c, n, self._set_array(names), len(names), out["dist"], out["valid_mask"], outs)
             else:
-                band = self._band_struct()
-                _lib.check(self._lib.d3f_band_sample(ctypes.byref(vol), ctypes.byref(band), _lib.ptr(pts_c), n, self._set_array(names), len(names),
-                                                     _lib.ptr(out["dist"]), _lib.ptr(out["valid_mask"]), _lib.ptr(out["in_band"]), outs,
-                                                     _lib.current_stream_handle(dev)))
+                q.d3f_band_sample(self._volume(), self._band_struct(), pts_c, n, self._set_array(names), len(names), out["dist"], out["valid_mask"],
+                                  out["in_band"], outs)
         return out
 
     def backward(self, pts, grad_dist=None, grad_sets=None):
         """grad_pts [N,3] = d(sum grad_dist * dist + sum over names of grad * row) / d pts (d3f_volume_sample_backward);
         grad_sets: {name: [N,C] or None}.  Banded (d3f_band_sample_backward): the dist term at every valid point, a set's term
         only where 'in_band'."""
-        self._check_query(pts)
+        _check_points(pts, self.device, "BakedField.eval")
         pts_c = pts.detach().contiguous()
         dev, n = self.device, pts_c.shape[0]
         grad_sets = {k: g for k, g in (grad_sets or {}).items() if g is not None}
@@ -699,15 +682,11 @@ class BakedField:
             if tuple(gd.shape) != (n,) or gd.device != dev:
                 raise ValueError("backward: grad_dist must be [%d] on %s" % (n, dev))
         grad_pts = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        vol = self._volume()
-        with torch.cuda.device(dev):
+        with self._on() as q:
             if self.band is None:
-                _lib.check(self._lib.d3f_volume_sample_backward(ctypes.byref(vol), _lib.ptr(pts_c), n, self._set_array(names), len(names), _lib.ptr(gd),
-                                                                grads, _lib.ptr(grad_pts), _lib.current_stream_handle(dev)))
+                q.d3f_volume_sample_backward(self._volume(), pts_c, n, self._set_array(names), len(names), gd, grads, grad_pts)
             else:
-                band = self._band_struct()
-                _lib.check(self._lib.d3f_band_sample_backward(ctypes.byref(vol), ctypes.byref(band), _lib.ptr(pts_c), n, self._set_array(names), len(names),
-                                                              _lib.ptr(gd), grads, _lib.ptr(grad_pts), _lib.current_stream_handle(dev)))
+                q.d3f_band_sample_backward(self._volume(), self._band_struct(), pts_c, n, self._set_array(names), len(names), gd, grads, grad_pts)
         return grad_pts
 
     def eval(self, pts, return_names=None):
@@ -715,7 +694,7 @@ class BakedField:
         interpolated in the volume.  Not valid (outside, a NaN coordinate, a cell with an invalid corner): dist 1e3, the fill row.
         A banded field adds 'in_band' [N] bool after 'valid_mask' (valid and the point's cell is kept): rows are the dense field's
         where it is set and the fill row elsewhere; dist and valid_mask never depend on the band."""
-        self._check_query(pts)
+        _check_points(pts, self.device, "BakedField.eval")
         names = self._names(return_names)
         if pts.requires_grad and torch.is_grad_enabled():
             res = _BakedQueryFn.apply(pts, self, tuple(names))
@@ -737,11 +716,9 @@ class BakedField:
         d2 = torch.empty((nx, ny, nz), dtype=torch.int32, device=dev)
         nearest = torch.empty((nx, ny, nz), dtype=torch.int32, device=dev)
         dist = torch.empty((nx, ny, nz), dtype=torch.float32, device=dev)
-        ws_bytes = int(self._lib.d3f_volume_edt_workspace_bytes(nx, ny, nz))
-        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(self._lib.d3f_volume_edt(_lib.ptr(site), nx, ny, nz, self.step, int(max_d2), _lib.ptr(d2), _lib.ptr(nearest), _lib.ptr(dist),
-                                                _lib.ptr(ws), ws_bytes, _lib.current_stream_handle(dev)))
+        with self._on() as q:
+            ws, ws_bytes = q.workspace("d3f_volume_edt_workspace_bytes", nx, ny, nz)
+            q.d3f_volume_edt(site, nx, ny, nz, self.step, int(max_d2), d2, nearest, dist, ws, ws_bytes)
         return d2, nearest, dist
 
     def _site_mask(self, who, iso, unknown, sites):
@@ -781,28 +758,26 @@ class BakedField:
         site = mask.contiguous().view(torch.uint8)
         labels = torch.empty((nx, ny, nz), dtype=torch.int32, device=dev)
         count = torch.empty(2, dtype=torch.int32, device=dev)
-        ws_bytes = int(self._lib.d3f_volume_components_workspace_bytes(nx, ny, nz))
-        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+        with self._on() as q:
+            ws, ws_bytes = q.workspace("d3f_volume_components_workspace_bytes", nx, ny, nz)
 
-        def launch(stats, capacity):
-            tail = (nx, ny, nz, connectivity, min_voxels, _lib.ptr(labels), _lib.ptr(count), _lib.ptr(stats), capacity, _lib.ptr(ws), ws_bytes,
-                    _lib.current_stream_handle(dev))
-            with torch.cuda.device(dev):
+            def launch(stats, capacity):
+                tail = (nx, ny, nz, connectivity, min_voxels, labels, count, stats, capacity, ws, ws_bytes)
                 if links is None:
-                    _lib.check(self._lib.d3f_volume_components(_lib.ptr(site), *tail))
+                    q.d3f_volume_components(site, *tail)
                 else:
-                    _lib.check(self._lib.d3f_volume_components_linked(_lib.ptr(site), _lib.ptr(links), *tail))
-            return count.tolist()
+                    q.d3f_volume_components_linked(site, links, *tail)
+                return count.tolist()
 
-        if not want_stats:
-            kept, found = launch(None, 0)
-            return labels, kept, found, None
-        capacity = min(nx * ny * nz, self._STATS_ROWS)
-        stats = torch.empty((capacity, 8), dtype=torch.int32, device=dev)
-        kept, found = launch(stats, capacity)
-        if kept > capacity:
-            stats = torch.empty((kept, 8), dtype=torch.int32, device=dev)
-            launch(stats, kept)
+            if not want_stats:
+                kept, found = launch(None, 0)
+                return labels, kept, found, None
+            capacity = min(nx * ny * nz, self._STATS_ROWS)
+            stats = torch.empty((capacity, 8), dtype=torch.int32, device=dev)
+            kept, found = launch(stats, capacity)
+            if kept > capacity:
+                stats = torch.empty((kept, 8), dtype=torch.int32, device=dev)
+                launch(stats, kept)
         return labels, kept, found, stats[:kept].clone() if kept < stats.shape[0] else stats
 
     def _check_links(self, who, links):
@@ -853,9 +828,8 @@ class BakedField:
         out = torch.empty((nx, ny, nz), dtype=torch.uint16, device=dev)
         site = members.contiguous().view(torch.uint8)
         sets = self._set_array([name])
-        with torch.cuda.device(dev):
-            _lib.check(self._lib.d3f_volume_links(_lib.ptr(site), None, _lib.ptr(self.slot), nx, ny, nz, sets, rule, threshold, connectivity, _lib.ptr(out),
-                                                  _lib.current_stream_handle(dev)))
+        with self._on() as q:
+            q.d3f_volume_links(site, None, self.slot, nx, ny, nz, sets, rule, threshold, connectivity, out)
         return out
 
     def links(self, name, rule="l2", tau=None, cos=None, iso=0.0, sites=None, connectivity=26):
@@ -936,9 +910,8 @@ class BakedField:
         axis = torch.empty((nx, ny, nz, 6), dtype=torch.float32, device=dev) if refine else None
         site_a, site_b = members_a.contiguous().view(torch.uint8), members_b.contiguous().view(torch.uint8)
         set_a, set_b = self._set_array([name]), other._set_array([name])
-        with torch.cuda.device(dev):
-            _lib.check(self._lib.d3f_volume_flow(_lib.ptr(site_a), _lib.ptr(self.slot), set_a, _lib.ptr(site_b), _lib.ptr(other.slot), set_b, nx, ny, nz,
-                                                 radius_voxels, max_cost2, _lib.ptr(target), _lib.ptr(cost), _lib.ptr(axis), _lib.current_stream_handle(dev)))
+        with self._on() as q:
+            q.d3f_volume_flow(site_a, self.slot, set_a, site_b, other.slot, set_b, nx, ny, nz, radius_voxels, max_cost2, target, cost, axis)
         return Flow(self.origin, self.step, target, cost, axis)
 
     # ---- warp -----------------------------------------------------------------------------------------------------------------
@@ -1033,8 +1006,8 @@ class BakedField:
         boxes = torch.empty((K, 12), dtype=torch.int32, device=dev)
         sel = _lib.WarpSelect(self._volume(), _lib.ptr(owner), _lib.ptr(pose) if K else None, K, 0, _lib.ptr(source), _lib.ptr(dist), _lib.ptr(valid),
                               _lib.ptr(boxes) if K else None)
-        with torch.cuda.device(dev):
-            _lib.check(self._lib.d3f_volume_warp_select(ctypes.byref(sel), _lib.current_stream_handle(dev)))
+        with self._on() as q:
+            q.d3f_volume_warp_select(sel)
         moved = type(self)(self.origin, self.step, dist, valid.view(torch.bool), {}, {}, boundaries=self.boundaries, axes=self._axes)
         if self.band is None:
             mark, voxels, m = None, None, n
@@ -1048,8 +1021,8 @@ class BakedField:
             band = None if self.band is None else self._band_struct()
             args = _lib.WarpRows(self._volume(), None if band is None else ctypes.pointer(band), self._set_array(names), len(names), K, _lib.ptr(source),
                                  _lib.ptr(pose) if K else None, _lib.ptr(voxels), m, outs, _lib.ptr(known))
-            with torch.cuda.device(dev):
-                _lib.check(self._lib.d3f_volume_warp_rows(ctypes.byref(args), _lib.current_stream_handle(dev)))
+            with self._on() as q:
+                q.d3f_volume_warp_rows(args)
         fills = {k: self._fills[k] for k in names}
         if self.band is None:
             moved._sets, moved._fills = {k: rows[k].view(nx, ny, nz, -1) for k in names}, fills
@@ -1141,14 +1114,12 @@ class BakedField:
         capacity = int((labels > 0).sum())
         members = torch.empty(1, dtype=torch.int64, device=dev)
         mean_channels = sum(self._channels(k) for k, m, _ in call if m == _lib.POOL_MEAN)
-        ws_bytes = int(self._lib.d3f_volume_pool_workspace_bytes(nx, ny, nz, K, capacity, mean_channels))
-        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
         valid = self.valid.contiguous().view(torch.uint8)
-        with torch.cuda.device(dev):
+        with self._on() as q:
+            ws, ws_bytes = q.workspace("d3f_volume_pool_workspace_bytes", nx, ny, nz, K, capacity, mean_channels)
             if K > 0:                                                    # (no component: every output is empty, there is nothing to point at)
-                _lib.check(self._lib.d3f_volume_pool(_lib.ptr(labels), nx, ny, nz, K, _lib.ptr(valid), _lib.ptr(self.slot), sets, len(call), modes, capacity,
-                                                     _lib.ptr(members), _lib.ptr(out["count"]), _lib.ptr(out["moments"]), rows, _lib.ptr(ws), ws_bytes,
-                                                     _lib.current_stream_handle(dev)))
+                q.d3f_volume_pool(labels, nx, ny, nz, K, valid, self.slot, sets, len(call), modes, capacity, members, out["count"], out["moments"], rows, ws,
+                                  ws_bytes)
         if no_rows:
             for k in names:
                 out[k] = self.fill_row(k).expand(K, -1).contiguous()
@@ -1212,7 +1183,7 @@ class BakedField:
         Plain torch indexing: not a hot path."""
         if self.nearest_voxel is None:
             raise ValueError("nearest_site: this is not a clearance field; BakedField.clearance() makes one")
-        self._check_query(pts)
+        _check_points(pts, self.device, "BakedField.eval")
         inside, flat = _voxel_of(pts, self.origin, self.step, self.grid_shape)
         voxel = torch.where(inside, self.nearest_voxel.view(-1)[flat].long(), torch.full_like(flat, -1))
         ok = voxel >= 0
@@ -1307,25 +1278,20 @@ class BakedField:
         nxt = torch.empty((nx, ny, nz), dtype=torch.int32, device=dev)
         dist = torch.empty((nx, ny, nz), dtype=torch.float32, device=dev)
         pending = torch.empty(1, dtype=torch.int32, device=dev)
-        ws_bytes = int(self._lib.d3f_volume_geodesic_workspace_bytes(nx, ny, nz))
-        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
         warr = (ctypes.c_int32 * 3)(*w)
-        with torch.cuda.device(dev):
-            stream = _lib.current_stream_handle(dev)
-            _lib.check(self._lib.d3f_volume_geodesic_init(_lib.ptr(site), nx, ny, nz, _lib.ptr(seeds), seeds.shape[0], _lib.ptr(cost), _lib.ptr(ws),
-                                                          ws_bytes, stream))
+        with self._on() as q:
+            ws, ws_bytes = q.workspace("d3f_volume_geodesic_workspace_bytes", nx, ny, nz)
+            q.d3f_volume_geodesic_init(site, nx, ny, nz, seeds, seeds.shape[0], cost, ws, ws_bytes)
             rounds, total = self._TRAVEL_FIRST_ROUNDS, 0
             while True:
-                _lib.check(self._lib.d3f_volume_geodesic_relax(_lib.ptr(site), _lib.ptr(penalty), nx, ny, nz, connectivity, warr, max_cost, rounds,
-                                                               _lib.ptr(cost), _lib.ptr(pending), _lib.ptr(ws), ws_bytes, stream))
+                q.d3f_volume_geodesic_relax(site, penalty, nx, ny, nz, connectivity, warr, max_cost, rounds, cost, pending, ws, ws_bytes)
                 total += rounds
                 if int(pending.item()) == 0:
                     break
                 if total > n:      # after k rounds every voxel whose cheapest path has at most k moves is final: never reached
                     raise RuntimeError("travel: the relaxation did not settle within %d rounds" % total)
                 rounds = min(2 * rounds, self._TRAVEL_MAX_ROUNDS)
-            _lib.check(self._lib.d3f_volume_geodesic_finish(_lib.ptr(site), _lib.ptr(penalty), nx, ny, nz, connectivity, warr, self.step, _lib.ptr(cost),
-                                                            _lib.ptr(nxt), _lib.ptr(dist), stream))
+            q.d3f_volume_geodesic_finish(site, penalty, nx, ny, nz, connectivity, warr, self.step, cost, nxt, dist)
         t = type(self)(self.origin, self.step, dist, cost != 2 ** 31 - 1, {}, {}, boundaries=self.boundaries, axes=self._axes)
         t.cost, t.next_voxel, t.free = cost, nxt, mask
         return t
@@ -1351,9 +1317,8 @@ class BakedField:
         voxels = torch.empty((N, max_steps), dtype=torch.int32, device=dev)
         length = torch.empty(N, dtype=torch.int32, device=dev)
         reached = torch.empty(N, dtype=torch.bool, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(self._lib.d3f_volume_follow(_lib.ptr(self.next_voxel), nx * ny * nz, _lib.ptr(s), N, max_steps, _lib.ptr(voxels), _lib.ptr(length),
-                                                   _lib.ptr(reached), _lib.current_stream_handle(dev)))
+        with self._on() as q:
+            q.d3f_volume_follow(self.next_voxel, nx * ny * nz, s, N, max_steps, voxels, length, reached)
         flat = voxels.view(-1)
         centres = self._voxel_centres(torch.clamp(flat, min=0))
         points = torch.where((flat >= 0)[:, None], centres, torch.full_like(centres, float("nan"))).view(N, max_steps, 3)
@@ -1418,11 +1383,9 @@ class BakedField:
         min_d2 = torch.empty(N, dtype=torch.int32, device=dev) if value is not None else None
         min_voxel = torch.empty(N, dtype=torch.int32, device=dev) if value is not None else None
         flags = _lib.SEGMENT_CUT_CORNERS if cut_corners else 0
-        with torch.cuda.device(dev):
-            if N > 0:                                  # (an empty tensor has no address: nothing to ask)
-                _lib.check(self._lib.d3f_volume_segments(_lib.ptr(mask.view(torch.uint8)), _lib.ptr(value), nx, ny, nz, _lib.ptr(va), _lib.ptr(vb), N, flags,
-                                                         _lib.ptr(clear), _lib.ptr(last), _lib.ptr(blocked), _lib.ptr(min_d2), _lib.ptr(min_voxel),
-                                                         _lib.current_stream_handle(dev)))
+        if N > 0:                                      # (an empty tensor has no address: nothing to ask)
+            with self._on() as q:
+                q.d3f_volume_segments(mask.view(torch.uint8), value, nx, ny, nz, va, vb, N, flags, clear, last, blocked, min_d2, min_voxel)
         out = {"clear": clear, "last_voxel": last, "blocked_voxel": blocked, "points": self._points_or_nan(last)}
         if value is not None:
             world = (torch.sqrt(min_d2.double()) * self.step).float()
@@ -1488,10 +1451,9 @@ class BakedField:
         index = torch.empty((N, L), dtype=torch.int32, device=dev)
         count = torch.empty(N, dtype=torch.int32, device=dev)
         flags = _lib.SEGMENT_CUT_CORNERS if cut_corners else 0
-        with torch.cuda.device(dev):
-            if N > 0:
-                _lib.check(self._lib.d3f_path_shorten(_lib.ptr(mask.view(torch.uint8)), nx, ny, nz, _lib.ptr(rows), _lib.ptr(length), N, L, max_span, flags,
-                                                      _lib.ptr(index), _lib.ptr(voxels), _lib.ptr(count), _lib.current_stream_handle(dev)))
+        if N > 0:
+            with self._on() as q:
+                q.d3f_path_shorten(mask.view(torch.uint8), nx, ny, nz, rows, length, N, L, max_span, flags, index, voxels, count)
         at = torch.arange(L, device=dev)[None, :]
         return {"voxels": voxels, "index": index, "length": count, "reached": paths["reached"], "points": self._points_or_nan(voxels),
                 "distance": self._row_lengths(voxels, at < count[:, None]) * self.step,
@@ -1558,13 +1520,10 @@ class BakedField:
             idx = torch.full((k, K), -1, dtype=torch.int64, device=dev)
             val = torch.full((k, K), float("inf"), dtype=torch.float32, device=dev)
         if M > 0:                                      # (an empty tensor has no address: nothing to ask)
-            ws_bytes = int(self._lib.d3f_pairwise_topk_workspace_bytes(M, K))
-            ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-            with torch.cuda.device(dev):
-                stream = _lib.current_stream_handle(dev)
-                _lib.check(self._lib.d3f_volume_peaks(_lib.ptr(slot), _lib.ptr(mask), nx, ny, nz, _lib.ptr(work), M, K, K, r, threshold, _lib.ptr(sup), K,
-                                                      _lib.ptr(count), None, 0, stream))
-                _lib.check(self._lib.d3f_topk_smallest(_lib.ptr(sup), M, K, k, _lib.ptr(idx), _lib.ptr(val), _lib.ptr(ws), ws_bytes, stream))
+            with self._on() as q:
+                ws, ws_bytes = q.workspace("d3f_pairwise_topk_workspace_bytes", M, K)
+                q.d3f_volume_peaks(slot, mask, nx, ny, nz, work, M, K, K, r, threshold, sup, K, count, None, 0)
+                q.d3f_topk_smallest(sup, M, K, k, idx, val, ws, ws_bytes)
         idx, val = idx.t().contiguous(), val.t().contiguous()
         hit = (idx >= 0) & (val < float("inf"))       # fewer than k peaks: the list goes on with rows that hold +Inf (or, with M < k, none)
         row = torch.where(hit, idx, torch.zeros_like(idx))
@@ -1702,9 +1661,8 @@ class BakedField:
             Kc = min(per_chunk, K - q0)
             dist = torch.empty((M, Kc), dtype=torch.float32, device=dev)
             if M > 0 and Kc > 0:
-                with torch.cuda.device(dev):
-                    _lib.check(self._lib.d3f_pairwise_similarity(_lib.ptr(rows), _lib.ptr(tgt[q0:q0 + Kc]), M, Kc, C, 1.0, code, _lib.SIM_DIST, _lib.ptr(dist),
-                                                                 None, None, 0, _lib.current_stream_handle(dev)))
+                with self._on() as q:
+                    q.d3f_pairwise_similarity(rows, tgt[q0:q0 + Kc], M, Kc, C, 1.0, code, _lib.SIM_DIST, dist, None, None, 0)
             parts.append(self._peaks_rows(dist, banded, r, k, thr, mask, True))
         voxel, value, count, offset = (torch.cat([p[i] for p in parts], dim=0) for i in range(4))
         return self._peaks_result("distance", voxel, value, count, offset, False)
@@ -1740,13 +1698,12 @@ class BakedField:
                 raise ValueError("%s: %s must be finite and >= 0, got %r" % (who, k, v))
         # (d3f_volume_align_centroid writes every row, zeros where an instance has no weighted finite point; it is not called without points)
         centroid = (torch.empty if I > 0 and n > 0 else torch.zeros)((I, 3), dtype=torch.float32, device=self.device)
-        if I > 0 and n > 0:
-            with torch.cuda.device(self.device):
-                _lib.check(self._lib.d3f_volume_align_centroid(_lib.ptr(pts), _lib.ptr(wt), I, n, _lib.ptr(centroid), _lib.current_stream_handle(self.device)))
-        ws_bytes = int(self._lib.d3f_volume_align_workspace_bytes(I, n))
-        ws = torch.empty(max(ws_bytes, 8) // 8, dtype=torch.float64, device=self.device)
-        return {"I": I, "n": n, "pts": pts, "names": names, "targets": tg, "dist_targets": dt, "weights": wt, "terms": terms, "centroid": centroid, "ws": ws,
-                "ws_bytes": ws_bytes}
+        with self._on() as q:
+            if I > 0 and n > 0:
+                q.d3f_volume_align_centroid(pts, wt, I, n, centroid)
+            ws, ws_bytes = q.workspace("d3f_volume_align_workspace_bytes", I, n)
+        return {"I": I, "n": n, "pts": pts, "names": names, "targets": tg, "dist_targets": dt, "weights": wt, "terms": terms, "centroid": centroid,
+                "ws": ws.view(torch.float64), "ws_bytes": ws_bytes}          # (the kernels keep rows of doubles there)
 
     def _align_pose(self, who, I, rot, trans):
         """[I, 12] float32: the kernels' R (the TRANSPOSE of the row-vector `rot`) row-major, then t"""
@@ -1756,16 +1713,12 @@ class BakedField:
         return torch.cat((rot.transpose(1, 2).reshape(I, 9), trans), dim=1).contiguous()
 
     def _align_accumulate(self, prob, pose, skip, out):
-        dev = self.device
-        vol = self._volume()
-        band = None if self.band is None else ctypes.byref(self._band_struct())
+        band = None if self.band is None else self._band_struct()
         sets = self._set_array(prob["names"]) if prob["names"] else None
         t = prob["terms"]
-        with torch.cuda.device(dev):
-            _lib.check(self._lib.d3f_volume_align_accumulate(ctypes.byref(vol), band, sets, _lib.ptr(prob["pts"]), _lib.ptr(prob["weights"]), _lib.ptr(prob["targets"]),
-                                                             _lib.ptr(prob["dist_targets"]), _lib.ptr(pose), _lib.ptr(prob["centroid"]), _lib.ptr(skip), prob["I"],
-                                                             prob["n"], t["dist_weight"], t["feat_weight"], t["outside"], _lib.ptr(out), _lib.ptr(prob["ws"]),
-                                                             prob["ws_bytes"], _lib.current_stream_handle(dev)))
+        with self._on() as q:
+            q.d3f_volume_align_accumulate(self._volume(), band, sets, prob["pts"], prob["weights"], prob["targets"], prob["dist_targets"], pose, prob["centroid"], skip,
+                                          prob["I"], prob["n"], t["dist_weight"], t["feat_weight"], t["outside"], out, prob["ws"], prob["ws_bytes"])
 
     def normal_equations(self, points, rot, trans, name=None, targets=None, dist_targets=None, weights=None, dist_weight=1.0, feat_weight=1.0, outside=None):
         """The Gauss-Newton normal equations of aligning point sets to this field at given poses (d3f_volume_align_accumulate,
@@ -1850,9 +1803,8 @@ class BakedField:
             out = torch.empty((I, _lib.ALIGN_ROW_DOUBLES), dtype=torch.float64, device=dev)
             for it in range(iters + 1):
                 self._align_accumulate(prob, pose, skip, None)
-                with torch.cuda.device(dev):
-                    _lib.check(self._lib.d3f_volume_align_step(_lib.ptr(state), _lib.ptr(prob["ws"]), prob["ws_bytes"], I, n, _lib.ptr(out), it, iters, rot_tol,
-                                                               trans_tol, _lib.ptr(pose), _lib.ptr(skip), _lib.ptr(history), _lib.current_stream_handle(dev)))
+                with self._on() as q:
+                    q.d3f_volume_align_step(state, prob["ws"], prob["ws_bytes"], I, n, out, it, iters, rot_tol, trans_tol, pose, skip, history)
         else:
             history = torch.zeros((I, iters + 1), dtype=torch.float64, device=dev)
             state[:, 29] = _lib.ALIGN_NO_GRADIENT          # no point at all: nothing to align to
@@ -1935,11 +1887,8 @@ class BakedField:
         hit = torch.empty(n, dtype=torch.bool, device=dev)
         pts = torch.empty((n, 3), dtype=torch.float32, device=dev)
         cnt = torch.empty(n, dtype=torch.int32, device=dev) if samples else None
-        vol = self._volume()
-        with torch.cuda.device(dev):
-            _lib.check(self._lib.d3f_volume_raycast(ctypes.byref(vol), _lib.ptr(origins), _lib.ptr(dirs), n, None if camera is None else ctypes.byref(camera),
-                                                    step, float(t_near), float(t_far), _lib.ptr(t), _lib.ptr(hit), _lib.ptr(pts), _lib.ptr(cnt),
-                                                    _lib.current_stream_handle(dev)))
+        with self._on() as q:
+            q.d3f_volume_raycast(self._volume(), origins, dirs, n, camera, step, float(t_near), float(t_far), t, hit, pts, cnt)
         return t, hit, pts, cnt
 
     def _at_hits(self, out, pts, names, normals):

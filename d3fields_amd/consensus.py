@@ -147,7 +147,6 @@ def consensus_poses(model_pts, candidates, tau, n_poses=8, min_inliers=4, shared
     if not tau2 > 0.0:
         raise ValueError("%s: tau = %r squares to zero in float32" % (who, tau))
 
-    lib = _lib.load()
     if n_trip > 0:                                  # (the select kernel writes every rank, the ones that do not exist as -1 / NaN)
         hyp, inl = torch.empty(H, dtype=torch.int32, device=dev), torch.empty(H, dtype=torch.int32, device=dev)
         asg = torch.empty((H, _lib.CONSENSUS_MAX_POINTS), dtype=torch.int8, device=dev)
@@ -159,23 +158,19 @@ def consensus_poses(model_pts, candidates, tau, n_poses=8, min_inliers=4, shared
         pose = torch.full((H, 12), float("nan"), dtype=torch.float32, device=dev)
     stats = torch.empty(4, dtype=torch.int32, device=dev) if n_trip > 0 else torch.zeros(4, dtype=torch.int32, device=dev)      # (select writes all four)
     terms = (tau2, side_tol, min_side, min_sin)
-    with torch.cuda.device(dev):
-        stream = _lib.current_stream_handle(dev)
+    with _lib.on(dev) as q:
         if n_trip > 0:
-            ws_bytes = int(lib.d3f_pose_consensus_workspace_bytes(M, k, n_trip, max_survivors))
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            ws, ws_bytes = q.workspace("d3f_pose_consensus_workspace_bytes", M, k, n_trip, max_survivors)
             count = torch.empty(T, dtype=torch.uint8, device=dev)
-            _lib.check(lib.d3f_pose_consensus_score(_lib.ptr(p), _lib.ptr(c), M, k, _lib.ptr(trip_dev), table.ctypes.data, n_trip, *terms, _lib.ptr(count), None, None,
-                                                    _lib.ptr(ws), ws_bytes, stream))
-            _lib.check(lib.d3f_pose_consensus_select(_lib.ptr(p), _lib.ptr(c), M, k, _lib.ptr(trip_dev), n_trip, *terms, _lib.ptr(count), min_inliers, shared,
-                                                     max_survivors, H, _lib.ptr(hyp), _lib.ptr(inl), _lib.ptr(asg), _lib.ptr(pose), _lib.ptr(stats), _lib.ptr(ws),
-                                                     ws_bytes, stream))
+            q.d3f_pose_consensus_score(p, c, M, k, trip_dev, table.ctypes.data, n_trip, *terms, count, None, None, ws, ws_bytes)
+            q.d3f_pose_consensus_select(p, c, M, k, trip_dev, n_trip, *terms, count, min_inliers, shared, max_survivors, H, hyp, inl, asg, pose, stats, ws,
+                                        ws_bytes)
         out = _result(hyp, inl, asg, pose, stats, trip_dev, M, k)
         if refit:
             rpose = torch.empty((H, 12), dtype=torch.float32, device=dev)          # (one wave per rank writes all three, NaN / -1 without three pairs)
             rmse = torch.empty(H, dtype=torch.float64, device=dev)
             rinl = torch.empty(H, dtype=torch.int32, device=dev)
-            _lib.check(lib.d3f_pose_refit(_lib.ptr(p), _lib.ptr(c), M, k, _lib.ptr(asg), H, tau2, _lib.ptr(rpose), _lib.ptr(rmse), _lib.ptr(rinl), stream))
+            q.d3f_pose_refit(p, c, M, k, asg, H, tau2, rpose, rmse, rinl)
             out.update({"refit_rot": rpose[:, :9].reshape(H, 3, 3).transpose(1, 2).contiguous(), "refit_trans": rpose[:, 9:].contiguous(), "rmse": rmse,
                         "refit_inliers": rinl})
     return out

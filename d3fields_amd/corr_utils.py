@@ -27,11 +27,6 @@ def _need_cuda(t, what):
         raise RuntimeError("%s must be on the ROCm device; there is no CPU path" % what)
 
 
-def _workspace(rows, cols, dev):
-    nbytes = _lib.load().d3f_softmax_workspace_bytes(rows, cols)
-    return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev), nbytes
-
-
 def _to_target(src, tgt, scale, dist_type, mode, channel_axis):
     """src [B, ...] with channels on `channel_axis` (1 or -1) against one target [C]."""
     code = _dist_code(dist_type)
@@ -51,13 +46,9 @@ def _to_target(src, tgt, scale, dist_type, mode, channel_axis):
         sb, si, sc = inner * C, C, 1
         oshape = tuple(src.shape[:-1])
     out = torch.empty(oshape, dtype=torch.float32, device=dev)
-    ws, ws_bytes = (None, 0)
-    if mode == _lib.SIM_SOFTMAX_DIM0:
-        ws, ws_bytes = _workspace(B, inner, dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().d3f_similarity_to_target(
-            _lib.ptr(src), B, inner, C, sb, si, sc, _lib.ptr(tgt), float(scale), code, mode, _lib.ptr(out),
-            _lib.ptr(ws), ws_bytes, _lib.current_stream_handle(dev)))
+    with _lib.on(dev) as q:
+        ws, ws_bytes = q.workspace("d3f_softmax_workspace_bytes", B, inner) if mode == _lib.SIM_SOFTMAX_DIM0 else (None, 0)
+        q.d3f_similarity_to_target(src, B, inner, C, sb, si, sc, tgt, float(scale), code, mode, out, ws, ws_bytes)
     return out
 
 
@@ -101,13 +92,9 @@ def _pairwise(src, tgt, scale, dist_type, mode, want_argmax):
     B2 = tgt.shape[0]
     out = torch.empty((B1, B2), dtype=torch.float32, device=dev)
     am = torch.empty(B2, dtype=torch.int64, device=dev) if want_argmax else None
-    ws, ws_bytes = (None, 0)
-    if mode == _lib.SIM_SOFTMAX_DIM0 or want_argmax:
-        ws, ws_bytes = _workspace(B1, B2, dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().d3f_pairwise_similarity(
-            _lib.ptr(src), _lib.ptr(tgt), B1, B2, C, float(scale), code, mode, _lib.ptr(out), _lib.ptr(am),
-            _lib.ptr(ws), ws_bytes, _lib.current_stream_handle(dev)))
+    with _lib.on(dev) as q:
+        ws, ws_bytes = q.workspace("d3f_softmax_workspace_bytes", B1, B2) if mode == _lib.SIM_SOFTMAX_DIM0 or want_argmax else (None, 0)
+        q.d3f_pairwise_similarity(src, tgt, B1, B2, C, float(scale), code, mode, out, am, ws, ws_bytes)
     return out, am
 
 
@@ -150,14 +137,10 @@ def knn_descriptors(src_feat_map, tgt_feats, k, scale=1.0, dist_type="l2"):
     tgt = tgt_feats.to(device=dev, dtype=torch.float32).contiguous()
     B1, C = src.shape
     B2 = tgt.shape[0]
-    lib = _lib.load()
     out = torch.empty((B1, B2), dtype=torch.float32, device=dev)
     idx = torch.empty((int(k), B2), dtype=torch.int64, device=dev)
     val = torch.empty((int(k), B2), dtype=torch.float32, device=dev)
-    ws_bytes = lib.d3f_pairwise_topk_workspace_bytes(B1, B2)
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.d3f_pairwise_similarity_topk(_lib.ptr(src), _lib.ptr(tgt), B1, B2, C, float(scale), code,
-                                                    _lib.SIM_SOFTMAX_DIM0, int(k), _lib.ptr(out), _lib.ptr(idx), _lib.ptr(val),
-                                                    _lib.ptr(ws), ws_bytes, _lib.current_stream_handle(dev)))
+    with _lib.on(dev) as q:
+        ws, ws_bytes = q.workspace("d3f_pairwise_topk_workspace_bytes", B1, B2)
+        q.d3f_pairwise_similarity_topk(src, tgt, B1, B2, C, float(scale), code, _lib.SIM_SOFTMAX_DIM0, int(k), out, idx, val, ws, ws_bytes)
     return out, idx, val

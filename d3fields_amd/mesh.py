@@ -31,13 +31,10 @@ def gaussian_filter(vol, shape, sigma=1.0, truncate=4.0):
     """scipy.ndimage.gaussian_filter(vol.reshape(shape), sigma, mode='reflect', truncate=truncate) in fp32 on the device
     (d3f_volume_gaussian); returns a new flat tensor."""
     v, nx, ny, nz = _volume(vol, shape)
-    lib = _lib.load()
     out = torch.empty_like(v)
-    ws_bytes = int(lib.d3f_volume_gaussian_workspace_bytes(nx, ny, nz))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=v.device)
-    with torch.cuda.device(v.device):
-        _lib.check(lib.d3f_volume_gaussian(_lib.ptr(v), _lib.ptr(out), nx, ny, nz, float(sigma), float(truncate), _lib.ptr(ws), ws_bytes,
-                                           _lib.current_stream_handle(v.device)))
+    with _lib.on(v.device) as q:
+        ws, ws_bytes = q.workspace("d3f_volume_gaussian_workspace_bytes", nx, ny, nz)
+        q.d3f_volume_gaussian(v, out, nx, ny, nz, float(sigma), float(truncate), ws, ws_bytes)
     return out
 
 
@@ -49,18 +46,15 @@ def marching_cubes(vol, shape, iso=0.0, valid=None, count_first=False, capacitie
     the call is repeated once with the exact counts, as grid_shell does."""
     v, nx, ny, nz = _volume(vol, shape)
     dev = v.device
-    lib = _lib.load()
     if valid is not None:
         if valid.device != dev or valid.numel() != v.numel() or valid.dtype not in (torch.bool, torch.uint8):
             raise RuntimeError("valid must be a bool / uint8 tensor of the volume's size on %s" % dev)
         valid = valid.contiguous().view(-1)
-    ws_bytes = int(lib.d3f_mesh_workspace_bytes(nx, ny, nz))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
     counts = torch.empty(2, dtype=torch.int64, device=dev)       # (both calls write both counts)
-    stream = _lib.current_stream_handle(dev)
-    with torch.cuda.device(dev):
+    with _lib.on(dev) as q:
+        ws, ws_bytes = q.workspace("d3f_mesh_workspace_bytes", nx, ny, nz)
         if count_first:
-            _lib.check(lib.d3f_mesh_count(_lib.ptr(v), _lib.ptr(valid), nx, ny, nz, float(iso), _lib.ptr(counts), _lib.ptr(ws), ws_bytes, stream))
+            q.d3f_mesh_count(v, valid, nx, ny, nz, float(iso), counts, ws, ws_bytes)
             cap_v, cap_t = (int(c) for c in counts.tolist())
         elif capacities is not None:
             cap_v, cap_t = (int(c) for c in capacities)
@@ -71,8 +65,7 @@ def marching_cubes(vol, shape, iso=0.0, valid=None, count_first=False, capacitie
             keys = torch.empty(cap_v, dtype=torch.int64, device=dev)
             t = torch.empty(cap_v, dtype=torch.float32, device=dev)
             tris = torch.empty((cap_t, 3), dtype=torch.int32, device=dev)
-            _lib.check(lib.d3f_mesh_extract(_lib.ptr(v), _lib.ptr(valid), nx, ny, nz, float(iso), cap_v, cap_t, _lib.ptr(keys), _lib.ptr(t),
-                                            _lib.ptr(tris), _lib.ptr(counts), _lib.ptr(ws), ws_bytes, stream))
+            q.d3f_mesh_extract(v, valid, nx, ny, nz, float(iso), cap_v, cap_t, keys, t, tris, counts, ws, ws_bytes)
             nv, nt = (int(c) for c in counts.tolist())
             if nv <= cap_v and nt <= cap_t:
                 break

@@ -78,16 +78,12 @@ def row_moments(rows, weights=None):
     M, C, w = _as_rows(rows, weights, "row_moments")
     if not rows.is_cuda:
         return _row_moments_host(rows, M, C, w)
-    lib = _lib.load()
     flat, stride = _flat_rows(rows, M, C)
-    dev = rows.device
-    out = torch.empty(1 + C + C * C, dtype=torch.float64, device=dev)
-    nbytes = int(lib.d3f_row_moments_workspace_bytes(M, C))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.d3f_row_moments(_lib.ptr(flat), _lib.DTYPE_F16 if flat.dtype == torch.float16 else _lib.DTYPE_F32, M, C, stride,
-                                       _lib.ptr(w), _lib.ptr(out[0:1]), _lib.ptr(out[1:1 + C]), _lib.ptr(out[1 + C:]), _lib.ptr(ws), nbytes,
-                                       _lib.current_stream_handle(dev)))
+    out = torch.empty(1 + C + C * C, dtype=torch.float64, device=rows.device)
+    with _lib.on(rows.device) as q:
+        ws, nbytes = q.workspace("d3f_row_moments_workspace_bytes", M, C)
+        q.d3f_row_moments(flat, _lib.DTYPE_F16 if flat.dtype == torch.float16 else _lib.DTYPE_F32, M, C, stride, w, out[0:1], out[1:1 + C], out[1 + C:],
+                          ws, nbytes)
     return out[0], out[1:1 + C], out[1 + C:].view(C, C)
 
 

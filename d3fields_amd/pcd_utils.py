@@ -31,7 +31,6 @@ def _dbl(values):
 def _backproject(depth, mask, cam_params, cam_to_world, bounds, dev):
     """One view -> (points [n,3] float64 tensor, pixel index [n] int32 tensor), ascending pixel order.  depth / mask: numpy
     arrays, or DEVICE tensors (depth any float dtype, mask uint8 / bool) that are used in place."""
-    lib = _lib.load()
     H, W = depth.shape
     if isinstance(depth, torch.Tensor):
         d = depth.to(device=dev, dtype=torch.float64).contiguous()
@@ -47,11 +46,10 @@ def _backproject(depth, mask, cam_params, cam_to_world, bounds, dev):
     pts = torch.empty((cap, 3), dtype=torch.float64, device=dev)
     pix = torch.empty(cap, dtype=torch.int32, device=dev)
     cnt = torch.empty(1, dtype=torch.int64, device=dev)          # (written by the call: H, W >= 1)
-    ws = torch.empty(lib.d3f_backproject_workspace_bytes(H, W), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.d3f_backproject_view(_lib.ptr(d), _lib.ptr(m), H, W, _dbl(cam_params), _dbl(np.asarray(cam_to_world).reshape(-1)),
-                                            _dbl(bounds) if bounds is not None else None, cap, _lib.ptr(pts), _lib.ptr(pix),
-                                            _lib.ptr(cnt), _lib.ptr(ws), _lib.current_stream_handle(dev)))
+    with _lib.on(dev) as q:
+        ws, _ = q.workspace("d3f_backproject_workspace_bytes", H, W)
+        q.d3f_backproject_view(d, m, H, W, _dbl(cam_params), _dbl(np.asarray(cam_to_world).reshape(-1)), _dbl(bounds) if bounds is not None else None, cap,
+                               pts, pix, cnt, ws)
     n = int(cnt.item())
     return pts[:n], pix[:n]
 
@@ -105,17 +103,14 @@ def voxel_downsample(pcd, voxel_size, pcd_color=None):
     if n == 0:
         return (pts_np, np.zeros((0, 3))) if pcd_color is not None else pts_np
     dev = _device()
-    lib = _lib.load()
     pts = torch.from_numpy(pts_np).to(dev)
     col = torch.from_numpy(np.ascontiguousarray(pcd_color, dtype=np.float64).reshape(-1, 3)).to(dev) if pcd_color is not None else None
     out_p = torch.empty((n, 3), dtype=torch.float64, device=dev)
     out_c = torch.empty((n, 3), dtype=torch.float64, device=dev) if col is not None else None
     cnt = torch.empty(1, dtype=torch.int64, device=dev)          # (written by the call, also for n == 0)
-    ws_bytes = lib.d3f_voxel_downsample_workspace_bytes(n)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.d3f_voxel_downsample(_lib.ptr(pts), _lib.ptr(col), n, float(voxel_size), _lib.ptr(out_p), _lib.ptr(out_c),
-                                            _lib.ptr(cnt), _lib.ptr(ws), ws_bytes, _lib.current_stream_handle(dev)))
+    with _lib.on(dev) as q:
+        ws, ws_bytes = q.workspace("d3f_voxel_downsample_workspace_bytes", n)
+        q.d3f_voxel_downsample(pts, col, n, float(voxel_size), out_p, out_c, cnt, ws, ws_bytes)
     v = int(cnt.item())
     if pcd_color is not None:
         return out_p[:v].cpu().numpy(), out_c[:v].cpu().numpy()
@@ -151,12 +146,10 @@ def aggr_point_cloud_from_data(colors, depths, Ks, poses, downsample=True, masks
 
 
 def _nearest(a, b, dev):
-    lib = _lib.load()
     md = torch.empty(a.shape[0], dtype=torch.float64, device=dev)
     am = torch.empty(a.shape[0], dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.d3f_pcd_nearest(_lib.ptr(a), a.shape[0], _lib.ptr(b), b.shape[0], _lib.ptr(md), _lib.ptr(am),
-                                       _lib.current_stream_handle(dev)))
+    with _lib.on(dev) as q:
+        q.d3f_pcd_nearest(a, a.shape[0], b, b.shape[0], md, am)
     return md, am
 
 
@@ -197,9 +190,8 @@ def init_low_level_memory(lower_bound, higher_bound, voxel_size, voxel_num):
         n = flat.shape[0]
         idx = torch.empty(n, dtype=torch.int32, device=dev)
         vox = torch.empty((n, 3), dtype=torch.int32, device=dev) if want_voxels else None
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().d3f_pcd_to_index(_lib.ptr(flat), n, _dbl(lower), vs, (ctypes.c_int32 * 3)(*[int(v) for v in num]),
-                                                    _lib.ptr(idx), _lib.ptr(vox), _lib.current_stream_handle(dev)))
+        with _lib.on(dev) as q:
+            q.d3f_pcd_to_index(flat, n, _dbl(lower), vs, (ctypes.c_int32 * 3)(*[int(v) for v in num]), idx, vox)
         if want_voxels:
             return vox.cpu().numpy().reshape(lead + (3,))
         return idx.cpu().numpy().reshape(lead)
@@ -240,13 +232,10 @@ def vox_idx_iou(vox_idx_1, vox_idx_2):
     dev = _device()
     a = torch.from_numpy(np.ascontiguousarray(np.asarray(vox_idx_1).reshape(-1), dtype=np.int32)).to(dev)
     b = torch.from_numpy(np.ascontiguousarray(np.asarray(vox_idx_2).reshape(-1), dtype=np.int32)).to(dev)
-    lib = _lib.load()
-    ws_bytes = lib.d3f_vox_iou_workspace_bytes(a.numel(), b.numel())
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     counts = torch.empty(2, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.d3f_vox_idx_iou(_lib.ptr(a), a.numel(), _lib.ptr(b), b.numel(), _lib.ptr(counts), _lib.ptr(ws), ws_bytes,
-                                       _lib.current_stream_handle(dev)))
+    with _lib.on(dev) as q:
+        ws, ws_bytes = q.workspace("d3f_vox_iou_workspace_bytes", a.numel(), b.numel())
+        q.d3f_vox_idx_iou(a, a.numel(), b, b.numel(), counts, ws, ws_bytes)
     inter, union = (int(v) for v in counts.tolist())
     return inter / union, a.numel() / union, b.numel() / union
 
@@ -265,9 +254,8 @@ def erode(image, kernel, iterations=1):
     dev = _device()
     src = torch.from_numpy(img).to(dev)
     dst = torch.empty_like(src)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().d3f_erode(_lib.ptr(src), img.shape[0], img.shape[1], kernel.shape[0], kernel.shape[1],
-                                         _lib.ptr(dst), _lib.current_stream_handle(dev)))
+    with _lib.on(dev) as q:
+        q.d3f_erode(src, img.shape[0], img.shape[1], kernel.shape[0], kernel.shape[1], dst)
     return dst.cpu().numpy()
 
 
@@ -286,10 +274,9 @@ def fps_pixels(pixel_idx, particle_num, init_idx=-1):
     pts = torch.from_numpy(pix.astype(np.int32)).to(dev)
     idx = torch.empty(k, dtype=torch.int64, device=dev)
     maxd = torch.empty(1, dtype=torch.float64, device=dev)
-    ws = torch.empty(_lib.load().d3f_fps_pixels_workspace_bytes(n), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().d3f_fps_pixels(_lib.ptr(pts), n, k, start, _lib.ptr(idx), _lib.ptr(maxd), _lib.ptr(ws),
-                                              _lib.current_stream_handle(dev)))
+    with _lib.on(dev) as q:
+        ws, _ = q.workspace("d3f_fps_pixels_workspace_bytes", n)
+        q.d3f_fps_pixels(pts, n, k, start, idx, maxd, ws)
     sel = idx.cpu().numpy()
     return pix[sel], sel.tolist(), float(maxd.item())
 
@@ -302,7 +289,6 @@ def masked_pixel_fps(mask_channel, depth, particle_num, depth_lo=0.0, depth_hi=1
     draws its start with np.random.randint(count), so the count has to reach the host first) and the result --
     (sel_idx [k,2] int64 rows/cols, sel_depth [k] float32) as numpy arrays.  Raises like fps_np's assert when the eroded
     mask is empty."""
-    lib = _lib.load()
     dev = mask_channel.device
     H, W = int(depth.shape[0]), int(depth.shape[1])
     assert mask_channel.shape == (H, W)
@@ -315,20 +301,18 @@ def masked_pixel_fps(mask_channel, depth, particle_num, depth_lo=0.0, depth_hi=1
     eroded = torch.empty_like(gated)
     rc = torch.empty((H * W, 2), dtype=torch.int32, device=dev)
     count = torch.empty(1, dtype=torch.int64, device=dev)
-    ws = torch.empty(lib.d3f_backproject_workspace_bytes(H, W), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        st = _lib.current_stream_handle(dev)
-        _lib.check(lib.d3f_mask_gate(_lib.ptr(mask_channel), mask_channel.stride(0), mask_channel.stride(1), _lib.ptr(depth), H, W,
-                                     float(depth_lo), float(depth_hi), _lib.ptr(gated), st))
-        _lib.check(lib.d3f_erode(_lib.ptr(gated), H, W, int(kernel[0]), int(kernel[1]), _lib.ptr(eroded), st))
-        _lib.check(lib.d3f_nonzero_pixels(_lib.ptr(eroded), H, W, H * W, _lib.ptr(rc), _lib.ptr(count), _lib.ptr(ws), st))
+    with _lib.on(dev) as q:
+        ws, _ = q.workspace("d3f_backproject_workspace_bytes", H, W)
+        q.d3f_mask_gate(mask_channel, mask_channel.stride(0), mask_channel.stride(1), depth, H, W, float(depth_lo), float(depth_hi), gated)
+        q.d3f_erode(gated, H, W, int(kernel[0]), int(kernel[1]), eroded)
+        q.d3f_nonzero_pixels(eroded, H, W, H * W, rc, count, ws)
         n = int(count.item())                                   # the one sync: np.random.randint(n) needs it
         assert n > 0, "fps_np asserts a non-empty point set (the eroded instance mask is empty)"
         start = int(np.random.randint(n)) if init_idx == -1 else int(init_idx)
         k = int(particle_num)
         idx = torch.empty(k, dtype=torch.int64, device=dev)
-        dist_ws = torch.empty(lib.d3f_fps_pixels_workspace_bytes(n), dtype=torch.uint8, device=dev)
-        _lib.check(lib.d3f_fps_pixels(_lib.ptr(rc), n, k, start, _lib.ptr(idx), None, _lib.ptr(dist_ws), st))
+        dist_ws, _ = q.workspace("d3f_fps_pixels_workspace_bytes", n)
+        q.d3f_fps_pixels(rc, n, k, start, idx, None, dist_ws)
         sel = rc[idx].to(torch.int64)                            # [k,2] rows, cols
         sel_depth = depth[sel[:, 0], sel[:, 1]]
         return sel.cpu().numpy(), sel_depth.cpu().numpy()

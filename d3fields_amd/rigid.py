@@ -10,7 +10,11 @@ replayed (`use_graph=True`): same kernels, same order, one host call per iterati
 pytorch3d (reference env pins 0.7.5, env.yaml:14) is neither available on ROCm images nor needed:
 the two functions the reference calls are a dozen lines each and are restated below.
 """
+import ctypes
+
 import torch
+
+from . import _lib
 
 __all__ = ["so3_exp_map", "rigid_transform", "track_rigid", "RigidTracker"]
 
@@ -141,7 +145,6 @@ class RigidTracker:
             self.single = (bool(single_launch) and feats.dtype == torch.float32 and C % 4 == 0 and C <= 512 and fusion.num_cam <= 8 and
                            feats.stride(3) == 1 and all(feats.stride(d) % 4 == 0 for d in (0, 1, 2)) and feats.data_ptr() % 16 == 0)
             if self.single:
-                from . import _lib
                 self.loss3 = torch.zeros(3, device=dev)
                 self.scratch = torch.zeros(_lib.load().d3f_track_step_scratch_bytes(num_inst, n) // 4, device=dev)
                 # loop_launch: all `iters` steps in ONE launch (d3f_track_run; the steps wait for one another inside the
@@ -176,42 +179,31 @@ class RigidTracker:
     def _fused_iteration(self, iters=1):
         """transform -> d3f_eval -> loss gradients -> d3f_eval_backward -> chain rule + Adam: five launches, no autograd
         (single: one launch per step, d3f_track_step, or one for `iters` steps, d3f_track_run)."""
-        from . import _lib
-        import ctypes
-        lib, dev = _lib.load(), self.last.device
+        dev = self.last.device
         I, n, N = self.num_inst, self.n, self.num_inst * self.n
         st = self.state
         m, v, step, norms, loss = st[:I * 6], st[I * 6:I * 12], st[I * 12:I * 13], st[I * 13:I * 13 + 2], st[I * 13 + 2:I * 13 + 4]
         if self.single:
-            with torch.cuda.device(dev), torch.no_grad():
-                stream = _lib.current_stream_handle(dev)
+            with _lib.on(dev) as q, torch.no_grad():
                 views, keep, V = self.shadow._views(dev)
                 fm = self.shadow.curr_obs_torch["dino_feats"]
                 cm = _lib.ChannelMap(fm.data_ptr(), fm.shape[1], fm.shape[2], fm.shape[3], _lib.DTYPE_F32, fm.stride(0), fm.stride(1), fm.stride(2))
                 state = _lib.TrackState(_lib.ptr(self.t_params), _lib.ptr(self.log_r), _lib.ptr(m), _lib.ptr(v), _lib.ptr(step),
                                         _lib.ptr(self.pts), _lib.ptr(self.loss3), _lib.ptr(self.scratch))
+                terms = (float(self.shadow.mu), DIST_W, REG_W, self.lr, 0.9, 0.999, 1e-8)
                 if iters == 1:
-                    _lib.check(lib.d3f_track_step(ctypes.byref(views), ctypes.byref(cm), _lib.ptr(self.last), I, n, _lib.ptr(self.src),
-                                                  float(self.shadow.mu), DIST_W, REG_W, self.lr, 0.9, 0.999, 1e-8, ctypes.byref(state), stream))
+                    q.d3f_track_step(views, cm, self.last, I, n, self.src, *terms, state)
                 else:
-                    _lib.check(lib.d3f_track_run(ctypes.byref(views), ctypes.byref(cm), _lib.ptr(self.last), I, n, _lib.ptr(self.src),
-                                                 float(self.shadow.mu), DIST_W, REG_W, self.lr, 0.9, 0.999, 1e-8, int(iters),
-                                                 ctypes.byref(state), stream))
+                    q.d3f_track_run(views, cm, self.last, I, n, self.src, *terms, int(iters), state)
             return self.pts, self.loss3.sum()
         assert iters == 1
-        with torch.cuda.device(dev), torch.no_grad():
-            stream = _lib.current_stream_handle(dev)
-            _lib.check(lib.d3f_rigid_transform(_lib.ptr(self.last), I, n, _lib.ptr(self.t_params), _lib.ptr(self.log_r),
-                                               _lib.ptr(self.pts), _lib.ptr(norms), stream))
+        with _lib.on(dev) as q, torch.no_grad():
+            q.d3f_rigid_transform(self.last, I, n, self.t_params, self.log_r, self.pts, norms)
             out, saved = self.shadow._launch(self.pts, ["dino_feats"], False, "eval")
             saved = saved[:5] + ((self.words.data_ptr(), [self.words.data_ptr() + 4]),)
-            _lib.check(lib.d3f_track_loss_grad(_lib.ptr(out["dino_feats"]), _lib.ptr(self.src), _lib.ptr(out["dist"]),
-                                               _lib.ptr(out["valid_mask"]), N, self.src.shape[1], DIST_W, _lib.ptr(self.grad_feats),
-                                               _lib.ptr(self.grad_dist), _lib.ptr(loss), stream))
+            q.d3f_track_loss_grad(out["dino_feats"], self.src, out["dist"], out["valid_mask"], N, self.src.shape[1], DIST_W, self.grad_feats, self.grad_dist, loss)
             grad_pts = self.shadow._backward(saved, self.grad_dist, [self.grad_feats])
-            _lib.check(lib.d3f_rigid_update(_lib.ptr(self.last), I, n, _lib.ptr(grad_pts), _lib.ptr(self.t_params), _lib.ptr(self.log_r),
-                                            _lib.ptr(m), _lib.ptr(v), _lib.ptr(step), _lib.ptr(norms), REG_W, self.lr, 0.9, 0.999, 1e-8,
-                                            stream))
+            q.d3f_rigid_update(self.last, I, n, grad_pts, self.t_params, self.log_r, m, v, step, norms, REG_W, self.lr, 0.9, 0.999, 1e-8)
         # total loss of this step as the reference forms it: feature + distance + regulariser (norms are pre-update)
         return self.pts, loss[0] + loss[1] + REG_W * (norms[0] + norms[1])
 
@@ -226,8 +218,6 @@ class RigidTracker:
         single-launch step has no strict form).  Runs on the current stream, ahead of the replay that reads the words."""
         if not self.fused or self.single:
             return
-        from . import _lib
-        import ctypes
         dev = self.last.device
         obs = self.shadow.curr_obs_torch
         d, fm = obs["depth"], obs["dino_feats"]
@@ -240,8 +230,8 @@ class RigidTracker:
                             _lib.DTYPE_F16 if fm.dtype == torch.float16 else _lib.DTYPE_F32, fm.stride(0), fm.stride(1), fm.stride(2)))
         views = (ctypes.c_int32 * 2)(d.shape[0], fm.shape[0])
         words = (ctypes.c_void_p * 2)(self.words.data_ptr(), self.words.data_ptr() + 4)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().d3f_map_check_many(descs, views, 2, words, 0, _lib.current_stream_handle(dev)))
+        with _lib.on(dev) as q:
+            q.d3f_map_check_many(descs, views, 2, words, 0)
 
     def run(self, fusion, src_feats, last_match_pts):
         dev = self.last.device
@@ -277,7 +267,6 @@ class RigidTracker:
             # the scratch.  One host sync per frame -- the caller (Fusion.rigid_tracking) copies the keypoints to the host right
             # away anyway -- reads that word: a stall repeats the frame with one launch per step, which cannot stall, and the
             # tracker stays on that form; a NaN that came out of the DATA (no sentinel) is the caller's result as it is.
-            from . import _lib
             I, n = self.last.shape[0], self.last.shape[1]
             word = int(_lib.load().d3f_track_stall_word(I, n))
             if int(self.scratch.view(torch.int32)[word].item()) == _lib.TRACK_STALL_SENTINEL:

@@ -14,6 +14,8 @@ cubes, fusion.py:1313-1330) should gather keys=('dist','valid_mask') and leave f
 import torch
 import torch.distributed as dist
 
+from . import _lib
+
 __all__ = ["shard_bounds", "shard_points", "all_gather_field", "gather_bytes", "sharded_eval", "broadcast_observation",
            "sharded_similarity_multi", "sharded_knn_descriptors"]
 
@@ -198,39 +200,30 @@ class _HipSoftmaxKernels:
 
     @staticmethod
     def local(src, tgt, scale, dist_code, row_offset):
-        from . import _lib
-        from .corr_utils import _workspace
         dev = src.device
         B1, C = src.shape
         B2 = tgt.shape[0]
         out = torch.empty((B1, B2), dtype=torch.float32, device=dev)
         stats = torch.empty((B2, 16), dtype=torch.uint8, device=dev)
-        ws, ws_bytes = _workspace(B1, B2, dev) if B1 > 0 else (None, 0)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().d3f_pairwise_softmax_local(
-                _lib.ptr(src), _lib.ptr(tgt), B1, B2, C, float(scale), dist_code, int(row_offset), _lib.ptr(out),
-                _lib.ptr(stats), _lib.ptr(ws), ws_bytes, _lib.current_stream_handle(dev)))
+        with _lib.on(dev) as q:
+            ws, ws_bytes = q.workspace("d3f_softmax_workspace_bytes", B1, B2) if B1 > 0 else (None, 0)
+            q.d3f_pairwise_softmax_local(src, tgt, B1, B2, C, float(scale), dist_code, int(row_offset), out, stats, ws, ws_bytes)
         return out, stats
 
     @staticmethod
     def merge(parts):
-        from . import _lib
         dev = parts.device
         P, B2 = parts.shape[0], parts.shape[1]
         merged = torch.empty((B2, 16), dtype=torch.uint8, device=dev)
         am = torch.empty(B2, dtype=torch.int64, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().d3f_softmax_merge(_lib.ptr(parts), P, B2, _lib.ptr(merged), _lib.ptr(am),
-                                                     _lib.current_stream_handle(dev)))
+        with _lib.on(dev) as q:
+            q.d3f_softmax_merge(parts, P, B2, merged, am)
         return merged, am
 
     @staticmethod
     def apply(out, scale, merged):
-        from . import _lib
-        dev = out.device
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().d3f_softmax_apply(_lib.ptr(out), out.shape[0], out.shape[1], float(scale),
-                                                     _lib.ptr(merged), _lib.current_stream_handle(dev)))
+        with _lib.on(out.device) as q:
+            q.d3f_softmax_apply(out, out.shape[0], out.shape[1], float(scale), merged)
         return out
 
 
@@ -239,29 +232,23 @@ class _HipTopkKernels:
 
     @staticmethod
     def local_topk(dist_local, k):
-        from . import _lib
-        lib = _lib.load()
         dev = dist_local.device
         rows, cols = dist_local.shape
         idx = torch.empty((k, cols), dtype=torch.int64, device=dev)
         val = torch.empty((k, cols), dtype=torch.float32, device=dev)
-        ws_bytes = lib.d3f_pairwise_topk_workspace_bytes(rows, cols)
-        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.d3f_topk_smallest(_lib.ptr(dist_local), rows, cols, k, _lib.ptr(idx), _lib.ptr(val), _lib.ptr(ws), ws_bytes,
-                                             _lib.current_stream_handle(dev)))
+        with _lib.on(dev) as q:
+            ws, ws_bytes = q.workspace("d3f_pairwise_topk_workspace_bytes", rows, cols)
+            q.d3f_topk_smallest(dist_local, rows, cols, k, idx, val, ws, ws_bytes)
         return idx, val
 
     @staticmethod
     def merge_topk(parts_idx, parts_val, k):
-        from . import _lib
         dev = parts_idx.device
         P, _, cols = parts_idx.shape
         idx = torch.empty((k, cols), dtype=torch.int64, device=dev)
         val = torch.empty((k, cols), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().d3f_topk_merge(_lib.ptr(parts_idx), _lib.ptr(parts_val), P, k, cols, _lib.ptr(idx), _lib.ptr(val),
-                                                  _lib.current_stream_handle(dev)))
+        with _lib.on(dev) as q:
+            q.d3f_topk_merge(parts_idx, parts_val, P, k, cols, idx, val)
         return idx, val
 
 

@@ -28,6 +28,55 @@ def test_every_declared_symbol_is_exported_and_bound():
     assert sorted(_lib.SIGNATURES) == names
 
 
+_C_KINDS = {"int": "int32_t", "int32_t": "int32_t", "uint32_t": "uint32_t", "int64_t": "int64_t", "float": "float", "double": "double", "void": "void"}
+_CTYPES_KINDS = {ctypes.c_int: "int32_t", ctypes.c_int32: "int32_t", ctypes.c_uint32: "uint32_t", ctypes.c_int64: "int64_t", ctypes.c_float: "float",
+                 ctypes.c_double: "double", ctypes.c_void_p: "pointer", ctypes.c_char_p: "pointer", None: "void"}
+
+
+def _c_kind(text):
+    """'const float *pts' -> 'pointer', 'int64_t n' -> 'int64_t'; also a return type, which has no name behind it"""
+    if "*" in text or "[" in text:
+        return "pointer"
+    words = [w for w in text.split() if w != "const"]
+    return _C_KINDS[words[0]]
+
+
+def _ctypes_kind(t):
+    if isinstance(t, type) and issubclass(t, ctypes._Pointer):
+        return "pointer"
+    return _CTYPES_KINDS[t]
+
+
+def declared_signatures():
+    """name -> (return kind, [parameter kinds], the last parameter is `void *stream`) of every declaration of the header"""
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    src = re.sub(r"//[^\n]*", "", src)
+    out = {}
+    for ret, name, params in re.findall(r"^((?:const\s+)?\w+[\s\*]+)(d3f_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src, flags=re.M):
+        params = [" ".join(p.split()) for p in params.split(",")]
+        if params == ["void"]:
+            params = []
+        assert name not in out, "%s is declared twice" % name
+        out[name] = (_c_kind(ret), [_c_kind(p) for p in params], bool(params) and params[-1] == "void *stream")
+    return out
+
+
+def test_signatures_match_header_parameters():
+    """Every SIGNATURES entry against its declaration, parameter by parameter: pointer, int32_t, uint32_t, int64_t, float or double, the
+    return kind likewise, and a stream filled in by _lib.on() exactly where the declaration ends in `void *stream`."""
+    declared = declared_signatures()
+    assert sorted(declared) == sorted(_lib.SIGNATURES) == declared_functions()
+    for name, (res, args) in _lib.SIGNATURES.items():
+        ret, params, streamed = declared[name]
+        assert _ctypes_kind(res) == ret, "%s returns %s in the header" % (name, ret)
+        assert [_ctypes_kind(a) for a in args] == params, name
+        assert (name in _lib.STREAMED) == streamed, name
+    assert len(_lib.SIGNATURES) == 106 and len(_lib.STREAMED) == 72     # (as counted by hand: a parser that skips declarations fails here)
+    # the entry points on() checks the status of: the streamed ones, and the others that return `int` and take arguments
+    assert _lib.STATUS == _lib.STREAMED | {n for n, (ret, params, _) in declared.items() if ret == "int32_t" and params and n not in _lib.STREAMED}
+    assert all(declared[n][0] == "int32_t" for n in _lib.STATUS)
+
+
 def test_version_and_constants_match_header():
     lib = _lib.load()
     hdr = open(HEADER).read()

@@ -729,3 +729,56 @@ def test_repr_example_runs(dev, capsys):
     assert f.curr_obs_torch == {} and f.mask_producer is None
     with pytest.raises(RuntimeError):
         f.batch_eval(torch.zeros(4, 3, device=dev), return_names=[])
+
+
+def test_call_context_launches_on_the_current_stream(dev):
+    """_lib.on(dev): inside torch.cuda.stream(side) the library receives side's handle as its stream argument (and none for a size
+    function), and the result is the one of the same entry point called through the raw ABI."""
+    from d3fields_amd import _lib
+    lib = _lib.load()
+    calls = []
+
+    class Recording:
+        def __getattr__(self, name):
+            fn = getattr(lib, name)
+
+            def call(*args):
+                calls.append((name, args))
+                return fn(*args)
+            return call
+
+    nx = ny = nz = 4
+    site = torch.zeros((nx, ny, nz), dtype=torch.uint8, device=dev)
+    site[1, 2, 3] = 1
+    cap = 2 ** 31 - 2
+
+    def buffers():
+        return (torch.empty((nx, ny, nz), dtype=torch.int32, device=dev), torch.empty((nx, ny, nz), dtype=torch.int32, device=dev),
+                torch.empty((nx, ny, nz), dtype=torch.float32, device=dev))
+
+    got, want = buffers(), buffers()
+    side = torch.cuda.Stream(device=dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        with _lib.on(dev, Recording()) as q:
+            ws, ws_bytes = q.workspace("d3f_volume_edt_workspace_bytes", nx, ny, nz)
+            q.d3f_volume_edt(site, nx, ny, nz, 0.5, cap, *got, ws, ws_bytes)
+    side.synchronize()
+    (size_name, size_args), (name, args) = calls
+    assert (size_name, size_args) == ("d3f_volume_edt_workspace_bytes", (nx, ny, nz))
+    assert name == "d3f_volume_edt" and len(args) == 12 and args[-1].value == side.cuda_stream != torch.cuda.current_stream(dev).cuda_stream
+    assert args[0].value == site.data_ptr() and args[-2] == ws_bytes == lib.d3f_volume_edt_workspace_bytes(nx, ny, nz)
+    assert ws.numel() == max(ws_bytes, 16) and ws.device == dev
+
+    raw_ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.d3f_volume_edt(_lib.ptr(site), nx, ny, nz, 0.5, cap, *[_lib.ptr(t) for t in want], _lib.ptr(raw_ws), ws_bytes,
+                                      _lib.current_stream_handle(dev)))
+    torch.cuda.synchronize(dev)
+    for a, b in zip(got, want):
+        assert torch.equal(a, b)
+    i, j, k = np.meshgrid(np.arange(nx), np.arange(ny), np.arange(nz), indexing="ij")
+    assert np.array_equal(cpu(got[0]), (i - 1) ** 2 + (j - 2) ** 2 + (k - 3) ** 2)
+    with pytest.raises(RuntimeError, match="d3f_volume_edt: argument 0"):
+        with _lib.on(dev) as q:
+            q.d3f_volume_edt(site.cpu(), nx, ny, nz, 0.5, cap, *got, ws, ws_bytes)
