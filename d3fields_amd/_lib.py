@@ -22,6 +22,8 @@ FLAG_UNORDERED_POINTS = 2
 FLAG_REFERENCE_ROUNDING = 4
 FLAG_REUSE_POINT_ORDER = 8
 FLAG_LOCAL_POINTS = 128
+# D3F_PLAN_*: the planner's thresholds (csrc/d3f_plan.h defines its own from the same macros) that decide whether those two flags are honoured
+PLAN_SMALL_BATCH, PLAN_WINDOW_CLOUD_MIN, PLAN_CACHE_RESIDENT_BYTES, PLAN_INFINITY_CACHE_BYTES = 65536, 262144, 64 << 20, 256 << 20
 PROBE_WORDS = 40
 TUNE_XCD_REMAP, TUNE_NO_REORDER, TUNE_FORCE_REORDER = 1 << 12, 1 << 13, 1 << 14
 TUNE_DIRECT_GATHER = 1 << 4
@@ -76,6 +78,24 @@ class ChannelMap(ctypes.Structure):
     """struct d3f_channel_map"""
     _fields_ = [("data", _vp), ("fh", _i32), ("fw", _i32), ("C", _i32), ("dtype", _i32),
                 ("stride_v", _i64), ("stride_y", _i64), ("stride_x", _i64), ("nonfinite", _vp)]
+
+
+def channel_map(t, nonfinite=None):
+    """The d3f_channel_map of a (V,h,w,C) tensor, or of a (V,H,W) depth tensor as a map of one float32 channel; `nonfinite`: the address
+    of its d3f_map_check word.  Describes the tensor as it is: whether the library can read that is readable_layout(t)."""
+    if t.dim() == 3:
+        return ChannelMap(t.data_ptr(), t.shape[1], t.shape[2], 1, DTYPE_F32, t.stride(0), t.stride(1), max(t.stride(2), 1), nonfinite)
+    return ChannelMap(t.data_ptr(), t.shape[1], t.shape[2], t.shape[3], DTYPE_F16 if t.dtype == torch.float16 else DTYPE_F32,
+                      t.stride(0), t.stride(1), t.stride(2), nonfinite)
+
+
+def readable_layout(t):
+    """Can the library read `t` where it lies?  A map: float32 or float16, channels adjacent, texels >= C apart in x; depth: float32; no negative stride."""
+    if t.dim() == 3:
+        ok = t.dtype == torch.float32 and t.stride(2) >= 1
+    else:
+        ok = t.dtype in (torch.float32, torch.float16) and t.stride(3) == 1 and t.stride(2) >= t.shape[3]
+    return ok and min(t.stride()) >= 0
 
 
 class Grid(ctypes.Structure):

@@ -43,12 +43,13 @@
 //                       LOCAL (D3F_FLAG_LOCAL_POINTS) keeps that order -- five ordering launches of ~5 us each do not pay around a
 //                       90-120 us query (the 71 k surface points of vis_repr.py:97-103 in flat-index order)
 //  kBeyondLlcBytes      maps beyond this in CALLER order without scratch: 64-point tiles at 2 workgroups per CU
-constexpr int64_t kSmallBatch = 65536;
-constexpr int64_t kWindowCloudMin = 262144;
-constexpr int64_t kCacheResidentBytes = 64LL << 20;
+// (the four that decide whether a caller's point-order flags are honoured are public, include/d3fields_hip.h: the shim sets the flags by them)
+constexpr int64_t kSmallBatch = D3F_PLAN_SMALL_BATCH;
+constexpr int64_t kWindowCloudMin = D3F_PLAN_WINDOW_CLOUD_MIN;
+constexpr int64_t kCacheResidentBytes = D3F_PLAN_CACHE_RESIDENT_BYTES;
 constexpr int64_t kBatchedLoadBytes = 128LL << 20;
 constexpr int64_t kBeyondLlcBytes = 512LL << 20;
-constexpr int64_t kInfinityCacheBytes = 256LL << 20;
+constexpr int64_t kInfinityCacheBytes = D3F_PLAN_INFINITY_CACHE_BYTES;
 
 
 // ---- tuning knobs ----------------------------------------------------------------------------------------------------------------

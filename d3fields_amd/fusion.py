@@ -10,6 +10,7 @@ module never downloads or builds them.
 There is no CPU or torch-op fallback: query points must live on the ROCm device and the
 shared library must load, otherwise an exception is raised.
 """
+import collections
 import ctypes
 import weakref
 
@@ -140,13 +141,23 @@ def onehot2instance(one_hot_mask):
     raise NotImplementedError
 
 
+class _LaunchRecord(collections.namedtuple("_LaunchRecord", "pts depth K pose maps depth_word map_words")):
+    """What a forward launch read, for its backward: the contiguous points and view tensors, the map tensors it gathered from (the contiguous
+    copy where one was made: held here, it stays alive) and the addresses of the finiteness words (None: no word, the strict form)."""
+    __slots__ = ()
+
+    def views(self):
+        d = self.depth
+        return _lib.Views(d.shape[0], d.shape[1], d.shape[2], _lib.ptr(d), _lib.ptr(self.K), _lib.ptr(self.pose), self.depth_word)
+
+
 class _FieldQueryFn(torch.autograd.Function):
     """Fusion.eval as an autograd node: forward = d3f_eval, backward = d3f_eval_backward (both HIP)."""
 
     @staticmethod
     def forward(ctx, pts, fusion, names):
-        outputs, saved = fusion._launch(pts.detach(), names, False, "eval")
-        ctx.fusion, ctx.saved = fusion, saved
+        outputs, ctx.saved = fusion._launch(pts.detach(), names, False, "eval")
+        ctx.fusion = fusion
         ctx.mark_non_differentiable(outputs["valid_mask"])
         return (outputs["dist"], outputs["valid_mask"]) + tuple(outputs[k] for k in names)
 
@@ -160,22 +171,19 @@ class _DistQueryFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pts, fusion):
-        outputs, _ = fusion._launch(pts.detach(), (), False, "eval_dist")
-        views, keep, _ = fusion._views(pts.device)
-        ctx.fusion, ctx.saved = fusion, (pts.detach().contiguous(), keep)
+        outputs, ctx.saved = fusion._launch(pts.detach(), (), False, "eval_dist")
+        ctx.fusion = fusion
         ctx.mark_non_differentiable(outputs["valid_mask"])
         return outputs["dist"], outputs["valid_mask"]
 
     @staticmethod
     def backward(ctx, grad_dist, _grad_valid):
-        pts_c, keep = ctx.saved
-        dev = pts_c.device
-        n, V = pts_c.shape[0], keep[0].shape[0]
-        views = _lib.Views(V, keep[0].shape[1], keep[0].shape[2], _lib.ptr(keep[0]), _lib.ptr(keep[1]), _lib.ptr(keep[2]))
+        rec = ctx.saved
+        dev, n = rec.pts.device, rec.pts.shape[0]
         grad_pts = torch.empty((n, 3), dtype=torch.float32, device=dev)
         gd = grad_dist.to(torch.float32).contiguous()
         with _lib.on(dev, ctx.fusion._lib) as q:
-            q.d3f_eval_dist_backward(views, pts_c, n, gd, grad_pts)
+            q.d3f_eval_dist_backward(rec.views(), rec.pts, n, gd, grad_pts)
         return grad_pts, None
 
 
@@ -386,14 +394,12 @@ class Fusion:
         hit = self._projected.get(name)
         if hit is not None and hit[0]() is src and hit[1] == sig:
             return hit[2]
-        m = src if (src.stride(3) == 1 and src.stride(2) >= src.shape[3] and min(src.stride()) >= 0) else src.contiguous()
+        m = src if _lib.readable_layout(src) else src.contiguous()
         W, _ = self._head_on(name, dev)
         out = torch.empty(tuple(src.shape[:3]) + (p["k"],), dtype=torch.float32, device=dev)
-        desc = _lib.ChannelMap(m.data_ptr(), m.shape[1], m.shape[2], m.shape[3], _lib.DTYPE_F16 if m.dtype == torch.float16 else _lib.DTYPE_F32,
-                               m.stride(0), m.stride(1), m.stride(2), None)
         with _lib.on(dev, self._lib) as q:
             # (addresses, not tensors: W and out were made on `dev` just above, and the host tests drive this method with host tensors)
-            q.d3f_project_maps(desc, m.shape[0], _lib.ptr(W), p["k"], _lib.ptr(out))
+            q.d3f_project_maps(_lib.channel_map(m), m.shape[0], _lib.ptr(W), p["k"], _lib.ptr(out))
         self._projected[name] = (weakref.ref(src), sig, out)
         return out
 
@@ -480,17 +486,9 @@ class Fusion:
         # a `return None` used to leave it behind, pointing at a slot that was already handed on)
         self._finite_cache.pop(key, None)
         src = t if checked is None else checked
-        if src.dim() == 3:                      # depth (V,H,W): a one-channel map
-            desc = _lib.ChannelMap(src.data_ptr(), src.shape[1], src.shape[2], 1, _lib.DTYPE_F32, src.stride(0), src.stride(1),
-                                   max(src.stride(2), 1), None)
-            ok = src.dtype == torch.float32 and src.stride(2) >= 1
-        else:
-            desc = _lib.ChannelMap(src.data_ptr(), src.shape[1], src.shape[2], src.shape[3],
-                                   _lib.DTYPE_F16 if src.dtype == torch.float16 else _lib.DTYPE_F32,
-                                   src.stride(0), src.stride(1), src.stride(2), None)
-            ok = src.dtype in (torch.float32, torch.float16) and src.stride(3) == 1 and src.stride(2) >= src.shape[3]
-        if not ok or min(src.stride()) < 0:
+        if not _lib.readable_layout(src):
             return None
+        desc = _lib.channel_map(src)            # (depth (V,H,W) as a one-channel map)
         # the slot, taken only now that the descriptor is valid: the next one of the ring that no LIVE cached verdict owns.  A
         # wrap never zeroes the ring (that also cleared the words of tensors the SAME query had already resolved as
         # cache hits -- a cached non-finite depth read as finite -- and of queries still in flight on other streams): once the
@@ -510,13 +508,11 @@ class Fusion:
         addr = self._words.data_ptr() + 4 * slot
         cacheable = checked is None and not torch.cuda.is_current_stream_capturing()
         if batch is not None:
-            import weakref
             batch.append([desc, int(src.shape[0]), addr, src, (key, weakref.ref(t), sig) if cacheable else None])
             return addr
         with torch.cuda.device(dev):
             _lib.check(self._lib.d3f_map_check(ctypes.byref(desc), src.shape[0], ctypes.c_void_p(addr), _lib.current_stream_handle(dev)))
         if cacheable:
-            import weakref
             ev = torch.cuda.Event()
             ev.record(stream)
             self._finite_cache[key] = (weakref.ref(t), sig, stream.cuda_stream, ev)
@@ -738,139 +734,137 @@ class Fusion:
             return out
         return self._launch(pts, return_names, return_inter, mode)[0]
 
+    def _bind_maps(self, names, dev, n, want_inter):
+        """The maps of `names` bound to a query of `n` points, -> (descriptors, output addresses, '_inter' addresses or None, the tensors read,
+        outputs by name, depth's word, the queued checks; a plain tuple: this is the hot path): looked up (KeyError for unknown names, like the reference),
+        validated, copied where the channels are not adjacent (a NEW tensor on every call: checked every call, never cached), outputs
+        allocated, descriptors filled in.  Finiteness: device words d3f_map_check writes when a tensor is new (no host sync), keyed on the
+        caller's tensor objects, the checks queued for ONE _flush_checks; _finite_override (RigidTracker) replaces them by a fixed flag."""
+        if len(names) > _lib.MAX_MAPS:
+            raise ValueError("at most %d return_names per call" % _lib.MAX_MAPS)
+        V = self.curr_obs_torch["depth"].shape[0]
+        descs = (_lib.ChannelMap * max(len(names), 1))()
+        fused = (ctypes.c_void_p * max(len(names), 1))()
+        inter = (ctypes.c_void_p * max(len(names), 1))() if want_inter else None
+        words = self._finite_override is None and bool(names)
+        checks, used, outputs = [], [], {}
+        depth_word = self._finite_word("depth", self.curr_obs_torch["depth"], batch=checks) if words else None
+        for s, k in enumerate(names):
+            m = self._query_map(k, dev)
+            if not isinstance(m, torch.Tensor) or m.dim() != 4 or m.shape[0] != V:
+                raise ValueError("curr_obs_torch[%r] must be a (V,h,w,C) tensor" % k)
+            if m.device != dev or m.dtype not in (torch.float32, torch.float16):
+                raise RuntimeError("curr_obs_torch[%r] must be float32 or float16 on %s" % (k, dev))
+            m_caller = m
+            if m.stride(3) != 1:
+                m = m.contiguous()
+            word = self._finite_word(k, m_caller, None if m is m_caller else m, batch=checks) if words else None
+            used.append(m)
+            C = m.shape[3]
+            o = outputs[k] = torch.empty((n, C), dtype=torch.float32, device=dev)
+            descs[s] = _lib.channel_map(m, word)
+            fused[s] = o.data_ptr()
+            if want_inter:
+                it = outputs[k + "_inter"] = torch.empty((V, n, C), dtype=torch.float32, device=dev)
+                inter[s] = it.data_ptr()
+        return descs, fused, inter, used, outputs, depth_word, checks
+
+    def _point_order(self, pts_c, n, views, descs, used, want_inter, stream, flags):
+        """In which order the library walks the points: (lattice dims or None, flags, workspace or None, workspace bytes).  Dims: the tensor
+        is create_init_grid's lattice, for d3f_eval_lattice (no scratch).  Else the flags carry the locality verdict where the planner
+        honours it (_lib.PLAN_*: its own thresholds) and the workspace is the Hilbert order's scratch (the cached one under
+        FLAG_REUSE_POINT_ORDER for the same tensor on the same stream) or, without maps, the distance-only pass's."""
+        lib, dev, n_maps = self._lib, pts_c.device, len(used)
+        ws, ws_bytes, dims, hinted_unordered = None, 0, None, None
+        if self.reorder_points and n_maps and n >= _lib.PLAN_SMALL_BATCH and not torch.cuda.is_current_stream_capturing():
+            if self.async_probes and not self.cache_point_order:
+                # no per-tensor cache: probes run asynchronously, the launch follows the last finished verdict
+                dims, hinted_unordered = self._order_hint(pts_c, stream)
+                if not self.detect_lattice:
+                    dims = None
+            elif self.detect_lattice:
+                dims = self._lattice_dims(pts_c, stream)
+        if dims is not None:
+            # a regular grid: closed-form brick walk on large maps / column runs on patch-resolution maps; no scratch
+            return dims, flags, None, 0
+        if self.reorder_points and n_maps and n >= _lib.PLAN_SMALL_BATCH:
+            map_bytes = sum(m.numel() * m.element_size() for m in used)
+            small = map_bytes <= _lib.PLAN_CACHE_RESIDENT_BYTES
+            # the verdict of the locality probe matters in two places: small maps are reordered only for an UNORDERED cloud, and
+            # a small cloud (below the window kernel's minimum) on maps inside the Infinity Cache keeps a LOCAL caller order
+            # (the 71 k surface points of vis_repr.py:97-103 in flat-index order: five ordering launches around a 120-us query)
+            keep_local = (not small) and n < _lib.PLAN_WINDOW_CLOUD_MIN and map_bytes <= _lib.PLAN_INFINITY_CACHE_BYTES
+            if (small or keep_local) and self.detect_point_order:
+                unordered = hinted_unordered if hinted_unordered is not None else self._is_unordered(pts_c, stream)
+                if small and unordered:
+                    flags |= _lib.FLAG_UNORDERED_POINTS     # larger maps are walked in Hilbert order anyway
+                if keep_local and not unordered:
+                    flags |= _lib.FLAG_LOCAL_POINTS
+            ws_bytes = lib.d3f_eval_workspace_bytes(n)
+            sig = (pts_c.data_ptr(), pts_c._version, n, int(stream.value or 0))   # per stream: the order is written asynchronously
+            held = self._order_ws if self.cache_point_order else None
+            plan = None
+            if self.cache_point_order:
+                plan = _lib.EvalPlan()
+                _lib.check(lib.d3f_eval_plan_query(ctypes.byref(views), n, descs, n_maps, flags, 1, 1 if want_inter else 0,
+                                                   ctypes.byref(plan)))
+            if held is not None and held[0] == sig and held[2] and plan.reorder:
+                ws = held[1]                                            # same points as last time: the order is still there
+                flags |= _lib.FLAG_REUSE_POINT_ORDER
+            else:
+                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)   # torch's caching allocator: no hipMalloc per call
+                if self.cache_point_order:
+                    self._order_ws = (sig, ws, bool(plan.reorder))      # filled by this call iff the library reorders
+        if not n_maps:
+            # the distance-only pass over a big batch looks the depth pixels up in a tiled copy (d3f_eval_dist_workspace_bytes: 0 below 2^22 points)
+            ws_bytes = int(lib.d3f_eval_dist_workspace_bytes(ctypes.byref(views), n)) if self.reorder_points else 0
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+        return None, flags, ws, ws_bytes
+
     def _launch(self, pts, return_names, return_inter, mode):
-        """Enqueues the forward kernel; returns (outputs, tensors the launch read)."""
+        """Enqueues the forward kernel; returns (outputs, the _LaunchRecord of what the launch read)."""
         # The forward query path, from _finite_word to here, calls the library by hand and not through _lib.on(): it is what the benchmark
-        # times, it sets the device and reads the stream once for all its calls already, and the host tests drive it with a fake self._lib.
-        dev = pts.device
-        lib = self._lib
-        n = pts.shape[0]
+        # times, and the host tests drive it on host tensors with a fake self._lib.
+        dev, lib, n = pts.device, self._lib, pts.shape[0]
         pts_c = pts.detach().contiguous()
         views, keep, V = self._views(dev)
-        dist = torch.empty(n, dtype=torch.float32, device=dev)
-        valid = torch.empty(n, dtype=torch.bool, device=dev)
-        outputs = {"dist": dist, "valid_mask": valid}
+        dist, valid = torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.bool, device=dev)
+        outputs, used, words = {"dist": dist, "valid_mask": valid}, (), []
         with torch.cuda.device(dev):
             stream = _lib.current_stream_handle(dev)
             if mode == "eval_dist":
                 _lib.check(lib.d3f_eval_dist(ctypes.byref(views), _lib.ptr(pts_c), n, _lib.ptr(dist), _lib.ptr(valid), stream))
-                return outputs, None
-            names = list(return_names)
-            if len(names) > _lib.MAX_MAPS:
-                raise ValueError("at most %d return_names per call" % _lib.MAX_MAPS)
-            maps = (_lib.ChannelMap * max(len(names), 1))()
-            fused = (ctypes.c_void_p * max(len(names), 1))()
-            inter = (ctypes.c_void_p * max(len(names), 1))()
-            # finiteness of depth and maps: device words written by d3f_map_check when a tensor is new (no host sync), keyed
-            # on the caller's tensor objects; _finite_override (RigidTracker's private observation) replaces them by a fixed flag
-            words = self._finite_override is None and bool(names)
-            checks = []                                    # new tensors of this query: ONE d3f_map_check_many below
-            if words:
-                views.depth_nonfinite = self._finite_word("depth", self.curr_obs_torch["depth"], batch=checks)
-            used_maps = []
-            for s, k in enumerate(names):
-                m = self._query_map(k, dev)                # KeyError for unknown names, like the reference
-                if not isinstance(m, torch.Tensor) or m.dim() != 4 or m.shape[0] != V:
-                    raise ValueError("curr_obs_torch[%r] must be a (V,h,w,C) tensor" % k)
-                if m.device != dev or m.dtype not in (torch.float32, torch.float16):
-                    raise RuntimeError("curr_obs_torch[%r] must be float32 or float16 on %s" % (k, dev))
-                m_caller = m
-                if m.stride(3) != 1:                           # a NEW tensor on every call: checked every call, never cached
-                    m = m.contiguous()
-                    keep.append(m)
-                word = self._finite_word(k, m_caller, None if m is m_caller else m, batch=checks) if words else None
-                used_maps.append(m)
-                C = m.shape[3]
-                o = torch.empty((n, C), dtype=torch.float32, device=dev)
-                outputs[k] = o
-                maps[s] = _lib.ChannelMap(m.data_ptr(), m.shape[1], m.shape[2], C,
-                                          _lib.DTYPE_F16 if m.dtype == torch.float16 else _lib.DTYPE_F32,
-                                          m.stride(0), m.stride(1), m.stride(2), word)
-                fused[s] = o.data_ptr()
-                if return_inter:
-                    it = torch.empty((V, n, C), dtype=torch.float32, device=dev)
-                    outputs[k + "_inter"] = it
-                    inter[s] = it.data_ptr()
-            self._flush_checks(checks, dev)
-            flags = self._query_flags()
-            ws, ws_bytes = None, 0
-            dims, hinted_unordered = None, None
-            if self.reorder_points and names and n >= 65536 and not torch.cuda.is_current_stream_capturing():
-                if self.async_probes and not self.cache_point_order:
-                    # no per-tensor cache: probes run asynchronously, the launch follows the last finished verdict
-                    dims, hinted_unordered = self._order_hint(pts_c, stream)
-                    if not self.detect_lattice:
-                        dims = None
-                elif self.detect_lattice:
-                    dims = self._lattice_dims(pts_c, stream)
-            if dims is not None:
-                # a regular grid: closed-form brick walk on large maps / column runs on patch-resolution maps; no scratch
+            else:
+                names = list(return_names)
+                descs, fused, inter, used, named, views.depth_nonfinite, checks = self._bind_maps(names, dev, n, return_inter)
+                outputs.update(named)
+                self._flush_checks(checks, dev)
+                dims, flags, ws, ws_bytes = self._point_order(pts_c, n, views, descs, used, return_inter, stream, self._query_flags())
                 if self.record_plans:
-                    self._record_plan(views, n, maps, len(names), flags, False, return_inter, dims)
-                _lib.check(lib.d3f_eval_lattice(ctypes.byref(views), _lib.ptr(pts_c), dims[0], dims[1], dims[2], maps, len(names),
-                                                self.mu, flags, _lib.ptr(dist), _lib.ptr(valid), fused,
-                                                inter if return_inter else None, stream))
-                self._subtract_offsets(outputs, names, dev, return_inter)
-                return outputs, (pts_c, keep[0], keep[1], keep[2], used_maps, (views.depth_nonfinite, [maps[s].nonfinite for s in range(len(names))]))
-            if self.reorder_points and names and n >= 65536:
-                map_bytes = sum(m.numel() * m.element_size() for m in used_maps)
-                small = map_bytes <= (64 << 20)
-                # the verdict of the locality probe matters in two places: small maps are reordered only for an UNORDERED cloud, and
-                # a small cloud (below the window kernel's 262 144 points) on maps inside the Infinity Cache keeps a LOCAL caller order
-                # (the 71 k surface points of vis_repr.py:97-103 in flat-index order: five ordering launches around a 120-us query)
-                keep_local = (not small) and n < 262144 and map_bytes <= (256 << 20)
-                if (small or keep_local) and self.detect_point_order:
-                    unordered = hinted_unordered if hinted_unordered is not None else self._is_unordered(pts_c, stream)
-                    if small and unordered:
-                        flags |= _lib.FLAG_UNORDERED_POINTS     # larger maps are walked in Hilbert order anyway
-                    if keep_local and not unordered:
-                        flags |= _lib.FLAG_LOCAL_POINTS
-                ws_bytes = lib.d3f_eval_workspace_bytes(n)
-                sig = (pts_c.data_ptr(), pts_c._version, n, int(stream.value or 0))   # per stream: the order is written asynchronously
-                held = self._order_ws if self.cache_point_order else None
-                plan = None
-                if self.cache_point_order:
-                    plan = _lib.EvalPlan()
-                    _lib.check(lib.d3f_eval_plan_query(ctypes.byref(views), n, maps, len(names), flags, 1, 1 if return_inter else 0,
-                                                       ctypes.byref(plan)))
-                if held is not None and held[0] == sig and held[2] and plan.reorder:
-                    ws = held[1]                                            # same points as last time: the order is still there
-                    flags |= _lib.FLAG_REUSE_POINT_ORDER
+                    self._record_plan(views, n, descs, len(names), flags, ws is not None, return_inter, dims)
+                if dims is not None:
+                    _lib.check(lib.d3f_eval_lattice(ctypes.byref(views), _lib.ptr(pts_c), dims[0], dims[1], dims[2], descs, len(names),
+                                                    self.mu, flags, _lib.ptr(dist), _lib.ptr(valid), fused, inter, stream))
                 else:
-                    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)   # torch's caching allocator: no hipMalloc per call
-                    if self.cache_point_order:
-                        self._order_ws = (sig, ws, bool(plan.reorder))      # filled by this call iff the library reorders
-            if not names:
-                # the distance-only pass over a big batch looks the depth pixels up in a tiled copy (d3f_eval_dist_workspace_bytes: 0 below 2^22 points)
-                ws_bytes = int(lib.d3f_eval_dist_workspace_bytes(ctypes.byref(views), n)) if self.reorder_points else 0
-                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
-            if self.record_plans:
-                self._record_plan(views, n, maps, len(names), flags, ws is not None, return_inter, None)
-            self._last_ws, self._last_ws_n = ws, n
-            _lib.check(lib.d3f_eval(ctypes.byref(views), _lib.ptr(pts_c), n, maps, len(names), self.mu, flags,
-                                    _lib.ptr(dist), _lib.ptr(valid), fused, inter if return_inter else None,
-                                    _lib.ptr(ws), ws_bytes, stream))
-            self._subtract_offsets(outputs, names, dev, return_inter)
-        return outputs, (pts_c, keep[0], keep[1], keep[2], used_maps, (views.depth_nonfinite, [maps[s].nonfinite for s in range(len(names))]))
+                    self._last_ws, self._last_ws_n = ws, n
+                    _lib.check(lib.d3f_eval(ctypes.byref(views), _lib.ptr(pts_c), n, descs, len(names), self.mu, flags,
+                                            _lib.ptr(dist), _lib.ptr(valid), fused, inter, _lib.ptr(ws), ws_bytes, stream))
+                self._subtract_offsets(outputs, names, dev, return_inter)
+                words = [descs[s].nonfinite for s in range(len(names))]
+        return outputs, _LaunchRecord(pts_c, keep[0], keep[1], keep[2], used, views.depth_nonfinite, words)
 
-    def _backward(self, saved, grad_dist, grad_fused):
-        """d3f_eval_backward on the tensors the forward launch read, with the forward's finiteness words (a point takes the
-        strict form where they say non-finite, or where a tensor has none).  The words are read when the backward RUNS: a
-        ring slot is handed on only _WORD_SLOTS checks later, so a backward that follows more than that many new-tensor
-        checks after its forward may read another tensor's verdict (and miss a NaN the reference would propagate)."""
-        pts_c, depth, K, pose, used_maps, (depth_word, map_words) = saved
-        dev = pts_c.device
-        n, V = pts_c.shape[0], depth.shape[0]
-        views = _lib.Views(V, depth.shape[1], depth.shape[2], _lib.ptr(depth), _lib.ptr(K), _lib.ptr(pose), depth_word)
+    def _backward(self, rec, grad_dist, grad_fused):
+        """d3f_eval_backward on what the forward launch read (its _LaunchRecord), with the forward's finiteness words (a point takes the strict
+        form where they say non-finite, or where a tensor has none).  The words are read when the backward RUNS: a ring slot is handed on only
+        _WORD_SLOTS checks later, so a backward more than that many new-tensor checks after its forward may read another tensor's verdict."""
+        dev = rec.pts.device
+        n, nm = rec.pts.shape[0], len(rec.maps)
         grad_pts = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        nm = len(used_maps)
         maps = (_lib.ChannelMap * max(nm, 1))()
         gptr = (ctypes.c_void_p * max(nm, 1))()
         hold = []
-        for s, m in enumerate(used_maps):
-            maps[s] = _lib.ChannelMap(m.data_ptr(), m.shape[1], m.shape[2], m.shape[3],
-                                      _lib.DTYPE_F16 if m.dtype == torch.float16 else _lib.DTYPE_F32,
-                                      m.stride(0), m.stride(1), m.stride(2), map_words[s])
+        for s, m in enumerate(rec.maps):
+            maps[s] = _lib.channel_map(m, rec.map_words[s])
             g = grad_fused[s]
             if g is not None:
                 g = g.to(torch.float32).contiguous()
@@ -878,7 +872,7 @@ class Fusion:
                 gptr[s] = g.data_ptr()
         gd = grad_dist.to(torch.float32).contiguous() if grad_dist is not None else None
         with _lib.on(dev, self._lib) as q:
-            q.d3f_eval_backward(views, pts_c, n, maps, nm, self.mu, gd, gptr, grad_pts)
+            q.d3f_eval_backward(rec.views(), rec.pts, n, maps, nm, self.mu, gd, gptr, grad_pts)
         return grad_pts
 
     def eval(self, pts, return_names=["dino_feats", "mask"], return_inter=False):
@@ -921,28 +915,11 @@ class Fusion:
         dist = torch.empty(n, dtype=torch.float32, device=dev)
         valid = torch.empty(n, dtype=torch.bool, device=dev)
         out = {"dist": dist, "valid_mask": valid, "grid_shape": torch.Size([grid.nx, grid.ny, grid.nz])}
-        maps = (_lib.ChannelMap * max(len(names), 1))()
-        fused = (ctypes.c_void_p * max(len(names), 1))()
-        words = self._finite_override is None and bool(names)
-        if words:
-            views.depth_nonfinite = self._finite_word("depth", self.curr_obs_torch["depth"])
-        for s, k in enumerate(names):
-            m = self._query_map(k, dev)
-            if m.device != dev or m.dtype not in (torch.float32, torch.float16):
-                raise RuntimeError("curr_obs_torch[%r] must be float32 or float16 on %s" % (k, dev))
-            m_caller = m
-            if m.stride(3) != 1:
-                m = m.contiguous()
-                keep.append(m)
-            word = self._finite_word(k, m_caller, None if m is m_caller else m) if words else None
-            out[k] = torch.empty((n, m.shape[3]), dtype=torch.float32, device=dev)
-            maps[s] = _lib.ChannelMap(m.data_ptr(), m.shape[1], m.shape[2], m.shape[3],
-                                      _lib.DTYPE_F16 if m.dtype == torch.float16 else _lib.DTYPE_F32,
-                                      m.stride(0), m.stride(1), m.stride(2), word)
-            fused[s] = out[k].data_ptr()
-        flags = self._query_flags()
-        with _lib.on(dev, self._lib) as q:
-            q.d3f_eval_grid(views, grid, maps, len(names), self.mu, flags, dist, valid, fused)
+        descs, fused, _, used, named, views.depth_nonfinite, checks = self._bind_maps(names, dev, n, False)
+        out.update(named)
+        self._flush_checks(checks, dev)
+        with _lib.on(dev, self._lib) as q:               # (`used` holds the contiguous copies until the function returns)
+            q.d3f_eval_grid(views, grid, descs, len(names), self.mu, self._query_flags(), dist, valid, fused)
             self._subtract_offsets(out, names, dev)
         return out
 

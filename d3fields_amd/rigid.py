@@ -186,8 +186,7 @@ class RigidTracker:
         if self.single:
             with _lib.on(dev) as q, torch.no_grad():
                 views, keep, V = self.shadow._views(dev)
-                fm = self.shadow.curr_obs_torch["dino_feats"]
-                cm = _lib.ChannelMap(fm.data_ptr(), fm.shape[1], fm.shape[2], fm.shape[3], _lib.DTYPE_F32, fm.stride(0), fm.stride(1), fm.stride(2))
+                cm = _lib.channel_map(self.shadow.curr_obs_torch["dino_feats"])      # (float32: self.single says so)
                 state = _lib.TrackState(_lib.ptr(self.t_params), _lib.ptr(self.log_r), _lib.ptr(m), _lib.ptr(v), _lib.ptr(step),
                                         _lib.ptr(self.pts), _lib.ptr(self.loss3), _lib.ptr(self.scratch))
                 terms = (float(self.shadow.mu), DIST_W, REG_W, self.lr, 0.9, 0.999, 1e-8)
@@ -200,7 +199,7 @@ class RigidTracker:
         with _lib.on(dev) as q, torch.no_grad():
             q.d3f_rigid_transform(self.last, I, n, self.t_params, self.log_r, self.pts, norms)
             out, saved = self.shadow._launch(self.pts, ["dino_feats"], False, "eval")
-            saved = saved[:5] + ((self.words.data_ptr(), [self.words.data_ptr() + 4]),)
+            saved = saved._replace(depth_word=self.words.data_ptr(), map_words=[self.words.data_ptr() + 4])
             q.d3f_track_loss_grad(out["dino_feats"], self.src, out["dist"], out["valid_mask"], N, self.src.shape[1], DIST_W, self.grad_feats, self.grad_dist, loss)
             grad_pts = self.shadow._backward(saved, self.grad_dist, [self.grad_feats])
             q.d3f_rigid_update(self.last, I, n, grad_pts, self.t_params, self.log_r, m, v, step, norms, REG_W, self.lr, 0.9, 0.999, 1e-8)
@@ -221,13 +220,10 @@ class RigidTracker:
         dev = self.last.device
         obs = self.shadow.curr_obs_torch
         d, fm = obs["depth"], obs["dino_feats"]
-        if fm.stride(3) != 1 or d.stride(2) != 1:
+        if not (_lib.readable_layout(fm) and _lib.readable_layout(d)):
             self.words.fill_(1)                 # not a layout d3f_map_check reads: the strict form (same results)
             return
-        descs = (_lib.ChannelMap * 2)(
-            _lib.ChannelMap(d.data_ptr(), d.shape[1], d.shape[2], 1, _lib.DTYPE_F32, d.stride(0), d.stride(1), d.stride(2)),
-            _lib.ChannelMap(fm.data_ptr(), fm.shape[1], fm.shape[2], fm.shape[3],
-                            _lib.DTYPE_F16 if fm.dtype == torch.float16 else _lib.DTYPE_F32, fm.stride(0), fm.stride(1), fm.stride(2)))
+        descs = (_lib.ChannelMap * 2)(_lib.channel_map(d), _lib.channel_map(fm))
         views = (ctypes.c_int32 * 2)(d.shape[0], fm.shape[0])
         words = (ctypes.c_void_p * 2)(self.words.data_ptr(), self.words.data_ptr() + 4)
         with _lib.on(dev) as q:

@@ -67,15 +67,23 @@ extern "C" {
                                           (1e-5 relative is the contract, ~2e-7 measured).  'dist', 'valid_mask', thin     \
                                           maps (instance masks, colours) and '<k>_inter' are in the reference's order and  \
                                           bit-exact either way.  Slower: the direct gather, no view skipping.              */
+/* The planner's thresholds that the two point-order flags below refer to (csrc/d3f_plan.h defines its constants from them; a caller
+ * that sets the flags only where they are honoured compares against the same numbers).  Points, and bytes of all requested maps together. */
+#define D3F_PLAN_SMALL_BATCH 65536                /* fewer points: caller order, neither flag is looked at                      */
+#define D3F_PLAN_WINDOW_CLOUD_MIN 262144          /* a cloud of at least this many points is always walked in Hilbert order    */
+#define D3F_PLAN_CACHE_RESIDENT_BYTES 67108864    /* 64 MiB: maps up to this size are "small" (caller order by default)        */
+#define D3F_PLAN_INFINITY_CACHE_BYTES 268435456   /* 256 MiB: maps up to this size fit the Infinity Cache                      */
 #define D3F_FLAG_UNORDERED_POINTS 2u /* the caller's point order has no spatial locality (shuffled or \
                                         uniformly random cloud; see d3f_point_order_locality): walk the \
-                                        points in Hilbert order even when the maps are small.  Performance \
-                                        only -- results never depend on it.                              */
+                                        points in Hilbert order even when the maps are small (at most   \
+                                        D3F_PLAN_CACHE_RESIDENT_BYTES; of at least D3F_PLAN_SMALL_BATCH \
+                                        points).  Performance only -- results never depend on it.       */
 #define D3F_FLAG_LOCAL_POINTS 128u /* (ABI 6) the caller's point order HAS spatial locality (d3f_points_probe: the mean step between \
                                       consecutive points is a small fraction of the cloud's extent -- a mesh, a scan, the surface    \
-                                      points of a lattice in flat-index order): a cloud too small for the window kernel (< 262 144   \
-                                      points) on maps that fit the Infinity Cache (<= 256 MiB) keeps the caller's order -- the      \
-                                      Hilbert sort (five launches) costs more than it saves there.  Performance only.            */
+                                      points of a lattice in flat-index order): a cloud too small for the window kernel (fewer than  \
+                                      D3F_PLAN_WINDOW_CLOUD_MIN points) on maps that fit the Infinity Cache (at most                 \
+                                      D3F_PLAN_INFINITY_CACHE_BYTES) keeps the caller's order -- the Hilbert sort (five launches)    \
+                                      costs more than it saves there.  Performance only.                                            */
 #define D3F_FLAG_REUSE_POINT_ORDER 8u /* `workspace` still holds the point order that an earlier d3f_eval call wrote  \
                                          for the SAME pts / n (a static grid queried every frame): do not rebuild it   \
                                          (~0.12 ms per 1 M points).  Any permutation of 0..n-1 gives the same results; \

@@ -85,8 +85,17 @@ def test_version_and_constants_match_header():
     for name, val in [("D3F_ERR_INVALID_ARG", _lib.ERR_INVALID_ARG), ("D3F_ERR_BAD_SHAPE", _lib.ERR_BAD_SHAPE),
                       ("D3F_ERR_BAD_DTYPE", _lib.ERR_BAD_DTYPE), ("D3F_ERR_BAD_LAYOUT", _lib.ERR_BAD_LAYOUT),
                       ("D3F_ERR_HIP", _lib.ERR_HIP), ("D3F_ERR_WORKSPACE", _lib.ERR_WORKSPACE),
-                      ("D3F_MAX_VIEWS", _lib.MAX_VIEWS), ("D3F_MAX_MAPS", _lib.MAX_MAPS)]:
+                      ("D3F_MAX_VIEWS", _lib.MAX_VIEWS), ("D3F_MAX_MAPS", _lib.MAX_MAPS),
+                      ("D3F_PLAN_SMALL_BATCH", _lib.PLAN_SMALL_BATCH), ("D3F_PLAN_WINDOW_CLOUD_MIN", _lib.PLAN_WINDOW_CLOUD_MIN),
+                      ("D3F_PLAN_CACHE_RESIDENT_BYTES", _lib.PLAN_CACHE_RESIDENT_BYTES),
+                      ("D3F_PLAN_INFINITY_CACHE_BYTES", _lib.PLAN_INFINITY_CACHE_BYTES)]:
         assert int(re.search(r"#define %s \(?(-?\d+)\)?" % name, hdr).group(1)) == val, name
+    # the planner's own constants are those macros (test_plan_table pins what the planner does with them), and the flags' text cites them
+    plan = open(os.path.join(ROOT, "d3fields_amd", "csrc", "d3f_plan.h")).read()
+    for const, macro in [("kSmallBatch", "D3F_PLAN_SMALL_BATCH"), ("kWindowCloudMin", "D3F_PLAN_WINDOW_CLOUD_MIN"),
+                         ("kCacheResidentBytes", "D3F_PLAN_CACHE_RESIDENT_BYTES"), ("kInfinityCacheBytes", "D3F_PLAN_INFINITY_CACHE_BYTES")]:
+        assert re.search(r"constexpr int64_t %s = %s;" % (const, macro), plan), const
+        assert re.search(r"#define D3F_FLAG_(UNORDERED|LOCAL)_POINTS [^*]*\*[^/]*%s\b" % macro, hdr), macro
 
 
 def test_struct_layouts_match_header():

@@ -782,3 +782,52 @@ def test_call_context_launches_on_the_current_stream(dev):
     with pytest.raises(RuntimeError, match="d3f_volume_edt: argument 0"):
         with _lib.on(dev) as q:
             q.d3f_volume_edt(site.cpu(), nx, ny, nz, 0.5, cap, *got, ws, ws_bytes)
+
+
+def _grid_query_scene():
+    """2 views of 24 x 32, a 12 x 10 x 9 grid, a channel-strided fp32 map and a contiguous fp16 map, one NaN in view 1's depth (host tensors)"""
+    from d3fields_amd import create_init_grid, synth
+    sc = synth.make_scene(2, 24, 32, "smooth")
+    sc["depth"][1, 12, 16] = float("nan")
+    maps = {"colors5": synth.random_map(2, 6, 8, 10, seed=5)[..., ::2], "dino_feats": synth.random_map(2, 3, 4, 8, seed=6).half()}
+    box = dict(x_lower=-0.18, x_upper=0.175, y_lower=-0.15, y_upper=0.145, z_lower=-0.22, z_upper=0.045)
+    pts, shape = create_init_grid(box, 0.03)
+    assert tuple(shape) == (12, 10, 9) and maps["colors5"].stride(3) == 2 and maps["colors5"].shape == (2, 6, 8, 5)
+    return sc, maps, box, pts
+
+
+def test_eval_grid_binds_and_checks_like_batch_eval(dev):
+    """eval_grid binds its maps and flushes their finiteness checks through the code of the point query: on a channel-strided fp32 map, a
+    half map and a depth image with one NaN it returns what batch_eval returns on the materialised grid, NaN for NaN; the NaN is seen by
+    the device-side check, and no longer once it is overwritten in place."""
+    from d3fields_amd import Fusion
+    from oracle import field_ref as R
+    sc, maps, box, pts = _grid_query_scene()
+    names = list(maps)
+    # float64 on the CPU: the NaN reaches some voxels (through 0 * NaN, whether or not view 1 is valid there) and not all
+    vals, _ = R.field64(sc, pts, 24, 32, 0.02, [maps[k].contiguous() for k in names])
+    lost = torch.isnan(vals[0]).any(1)
+    assert 0 < int(lost.sum()) < pts.shape[0] and torch.equal(lost, torch.isnan(vals[1]).any(1))
+    f = Fusion(num_cam=2, device=str(dev))
+    f.curr_obs_torch = {k: v.to(dev) for k, v in sc.items()}
+    wide = torch.empty(2, 6, 8, 10, device=dev).copy_(maps["colors5"]._base)
+    f.curr_obs_torch.update({"colors5": wide[..., ::2], "dino_feats": maps["dino_feats"].to(dev)})
+    f.H, f.W = 24, 32
+    with torch.no_grad():
+        a = f.eval_grid(box, 0.03, return_names=names)
+        assert not f.maps_are_finite()
+        b = f.batch_eval(pts.to(dev), return_names=names)
+    assert tuple(a["grid_shape"]) == (12, 10, 9) and torch.equal(a["valid_mask"], b["valid_mask"])
+    for k in ["dist"] + names:
+        nan = torch.isnan(a[k])
+        assert torch.equal(nan, torch.isnan(b[k])) and torch.equal(a[k][~nan], b[k][~nan]), k
+        assert bool(torch.isfinite(a[k][~nan]).all()), k
+    for k in names:                                          # the rows the float64 reference loses, and no others
+        assert torch.equal(torch.isnan(a[k]).any(1).cpu(), lost) and torch.equal(torch.isnan(a[k]).any(1), torch.isnan(a[k]).all(1)), k
+    assert torch.equal(torch.isnan(a["dist"]).cpu(), lost)
+    f.curr_obs_torch["depth"][1, 12, 16] = 1.0               # in place: the tensor's version moves on, the next query checks it again
+    with torch.no_grad():
+        c = f.eval_grid(box, 0.03, return_names=names)
+        d = f.batch_eval(pts.to(dev), return_names=names)
+    assert f.maps_are_finite() and not any(bool(torch.isnan(c[k]).any()) for k in ["dist"] + names)
+    assert all(torch.equal(c[k], d[k]) for k in ["dist", "valid_mask"] + names)
