@@ -194,6 +194,8 @@ hipError_t launch_fps(const float *pts, int64_t n, int k, int64_t init_idx, int6
                       void *workspace, hipStream_t s);
 struct FpsLayout { int64_t dist, maxima, total; };
 FpsLayout fps_layout(int64_t n, int dist_bytes);            // dist_bytes: 4 (d3f_farthest_point_sampling) or 8 (d3f_fps_pixels)
+constexpr int kFpsMaxBlocks = 256;                          // entries per round parity of fps_layout's `maxima`: one per workgroup of a round
+int64_t fps_blocks(int64_t n);                              // workgroups of one round, 1..kFpsMaxBlocks (tests/layout_check.cpp holds it to the table)
 
 // mesh_kernels.hip
 struct MeshLayout { int64_t voff, toff, scan, total; int64_t blocks; };

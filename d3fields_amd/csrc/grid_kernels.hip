@@ -261,11 +261,11 @@ struct FpsMax {
     long long i;
 };
 
-constexpr int kFpsMaxBlocks = 256;
-
 int64_t fps_blocks(int64_t n)
 {
-    const int64_t per = n / kFpsMaxBlocks > 1024 ? (n + kFpsMaxBlocks - 1) / kFpsMaxBlocks : 1024;     // >= 1024 points per workgroup
+    // >= 1024 points per workgroup, and never fewer than ceil(n / kFpsMaxBlocks): at most kFpsMaxBlocks workgroups, one entry of `maxima` each.
+    // (The floor n / kFpsMaxBlocks in its place left 1024 points per workgroup to n = 256 * 1024 + 1 .. 256 * 1025 - 1: 257 workgroups.)
+    const int64_t fill = (n + kFpsMaxBlocks - 1) / kFpsMaxBlocks, per = fill > 1024 ? fill : 1024;
     return (n + per - 1) / per;
 }
 

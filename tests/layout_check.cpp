@@ -1,6 +1,7 @@
 // layout_check.cpp -- a stand-alone host program: every workspace layout function of csrc/ over the argument table of tests/workspace_args.py.
 // For every row the public size function accepts, the layout's regions must start at 0, follow each other in the order of the struct, end at or
-// before `total`, and `total` must be what the size function returns.  Meant to be built with the host side under AddressSanitizer and
+// before `total`, and `total` must be what the size function returns; a round of farthest point sampling must not launch more workgroups
+// (fps_blocks) than its table of maxima has entries per round parity.  Meant to be built with the host side under AddressSanitizer and
 // UndefinedBehaviorSanitizer (the level arrays of scan_layout / topk_layout, the int64 products); it launches nothing and needs no device.
 //
 //   python tests/workspace_args.py --rows > rows.txt
@@ -133,6 +134,14 @@ static void one(const std::string &fn, const Row &a)
     } else if (fn == "d3f_fps_workspace_bytes" || fn == "d3f_fps_pixels_workspace_bytes") {
         const FpsLayout L = fps_layout(a[0], fn == "d3f_fps_workspace_bytes" ? 4 : 8);
         check(fn, a, "fps_layout", {L.dist, L.maxima}, L.total, want);
+        // a round's workgroups each own one 16-byte entry of their parity's half of `maxima`: never more workgroups than entries
+        const int64_t entries = (L.total - L.maxima) / (2 * 16);
+        ++g_checked;
+        if (entries != kFpsMaxBlocks || fps_blocks(a[0]) < 1 || fps_blocks(a[0]) > entries) {
+            ++g_bad;
+            std::cout << "BAD " << fn << "( " << a[0] << " ) fps_blocks: " << fps_blocks(a[0]) << " workgroups a round, fps_layout.maxima holds " << entries
+                      << " entries per parity (kFpsMaxBlocks " << kFpsMaxBlocks << ")\n";
+        }
     } else if (fn == "d3f_backproject_workspace_bytes") {
         const PixelCountsLayout L = pixel_counts_layout(a[0] * a[1]);
         check(fn, a, "pixel_counts_layout", {L.counts}, L.total, want);

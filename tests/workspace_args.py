@@ -3,7 +3,8 @@ that return 0 (zero, negative, over the limit, NULL views), the smallest valid s
 behind it, and one workload-sized shape.  A row is the tuple of the function's arguments; views and grids are tuples of their integers (None: NULL).
 
     python tests/workspace_args.py LIBRARY     prints the record of that library as JSON (how tests/workspace_bytes.json was made, once,
-                                               from the library of the commit before the layouts; see the test's docstring)
+                                               from the library of the commit before the layouts; see the test's docstring.  Rows added
+                                               later go to the END of a function's list and of its record: the older values stay as they are)
     python tests/workspace_args.py --rows      prints "function arg arg ..." lines: the table for a program that is not Python
 """
 import ctypes
@@ -51,6 +52,7 @@ VOLUME = (128, 128, 64)                                                         
 
 ORDER_N = [0, -1, 1] + around(64, 1 << 14, 1 << 19) + [1000000, I31, I31 + 1]       # 256-byte pad of 4 n; 2 n = 2^15 and 2^20 counters
 POOL_K = [0, 1] + around(63, S - 1) + [65535]                                      # K + 1 words: the 256-byte pad, the scan's second level
+FPS_EDGES = [262144, 262145, 262399, 262400]                                       # 256 * 1024 and 256 * 1025 - 1: the window in which 1024 points per workgroup would need 257 of them
 POOL_CAP = [0, 1] + around(256, 65536) + [1 << 21, 1 << 30]                        # fold levels; above n: clamped to n
 
 TABLE = {
@@ -87,9 +89,9 @@ TABLE = {
                                             (3, 1, 1, _lib.CONSENSUS_MAX_SURVIVORS + 1), (3, 1, 0, 1), (3, 1, 1, 1)]
                                            + [(8, 1, t, 64) for t in around(B, 64 * B, S * B)] + [(8, 8, 1 << 21, 64), (8, 8, (1 << 21) + 1, 64), (8, 8, I31 // 512, 64)]
                                            + [(8, 4, 1000, s) for s in around(4, 64, 256) + [4096, _lib.CONSENSUS_MAX_SURVIVORS]]),
-    # distances of 4 and of 8 bytes, rounded up to 16
-    "d3f_fps_workspace_bytes": [(n,) for n in [0, -1, 1] + around(4, 8, 1024) + [200000, I31]],
-    "d3f_fps_pixels_workspace_bytes": [(n,) for n in [0, -1, 1] + around(2, 4, 1024) + [307200, I31]],
+    # distances of 4 and of 8 bytes, rounded up to 16; 256 workgroups of 1024 points, the last n they hold, and the first of 1025 and more each (FPS_EDGES)
+    "d3f_fps_workspace_bytes": [(n,) for n in [0, -1, 1] + around(4, 8, 1024) + [200000, I31] + FPS_EDGES],
+    "d3f_fps_pixels_workspace_bytes": [(n,) for n in [0, -1, 1] + around(2, 4, 1024) + [307200, I31] + FPS_EDGES],
     "d3f_backproject_workspace_bytes": [(0, 4), (4, 0), (-1, 4), (4, -1), (1, 1), (1, 256), (1, 257), (16, 16), (480, 640), (32768, 65535)],
     # the table doubles where 2 (n1 + n2) passes it
     "d3f_vox_iou_workspace_bytes": [(-1, 4), (4, -1), (0, 0), (1, 0), (512, 0), (512, 1), (0, 1024), (1, 1024), (100000, 90000), (1 << 29, 1 << 29)],
