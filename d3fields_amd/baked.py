@@ -77,6 +77,13 @@ _POOL_KEYS = ("count", "moments", "centroid", "covariance")     # output keys of
 _RAY_KEYS = ("t", "depth", "hit_mask", "points", "normal")      # output keys of raycast / render: a set of that name cannot be asked for there
 
 
+def _rows_in_place(t):
+    """can the library read a [nx, ny, nz, C] set where it lies?  channels adjacent, voxels one constant stride >= C apart in flat order"""
+    nx, ny, nz, C = t.shape
+    sv = t.stride(2)
+    return t.stride(3) == 1 and sv >= C and t.stride(1) == nz * sv and t.stride(0) == ny * nz * sv
+
+
 def _check_band(band, who):
     try:
         value = float(band)
@@ -397,7 +404,8 @@ class BakedField:
     step        the lattice step h > 0
     grid_shape  torch.Size([nx, ny, nz]), every extent >= 2, z fastest
     dist        float32 [nx, ny, nz];  valid: bool [nx, ny, nz]
-    names()     the channel sets, each float32 [nx, ny, nz, C]
+    names()     the channel sets, each float32 [nx, ny, nz, C] -- or float16 after half() / Fusion.bake(rows_dtype=torch.float16): rows_dtype(name),
+                rows_bytes; the lookups read either storage and give the same bits, the methods with row loops of their own need float()
 
     A CLEARANCE field (clearance()) has no sets; its dist is the distance to the nearest site, and it has d2 int32 [nx, ny, nz] (squared
     voxel distance), nearest_voxel int32 (flat index of that site, -1: none), sites bool, and nearest_site(pts).  They are None elsewhere.
@@ -446,11 +454,13 @@ class BakedField:
 
     # ---- construction ---------------------------------------------------------------------------------------------------------
     @classmethod
-    def from_arrays(cls, origin, step, dist, valid=None, fills=None, **named):
+    def from_arrays(cls, origin, step, dist, valid=None, fills=None, rows_dtype=None, **named):
         """A field from volumes made elsewhere (a Gaussian-smoothed `dist`, ...): dist [nx,ny,nz] float32, valid None (every
         voxel) or bool / uint8 of the same shape, named sets [nx,ny,nz,C] float32, all on one ROCm device; fills: None or
         {name: [C] row a point outside the valid cells gets} (default zeros).  Tensors are used in place where they are
-        contiguous float32 / bool."""
+        contiguous float32 / bool.
+        rows_dtype: None (every set becomes float32), torch.float16 or {name: dtype}: a set given as float16 whose dtype this names
+        is KEPT as half rows (half()); such a set is also used in place as a view whose voxels are a constant stride >= C apart."""
         origin = tuple(float(o) for o in origin)
         if len(origin) != 3:
             raise ValueError("from_arrays: origin must hold three coordinates")
@@ -486,23 +496,46 @@ class BakedField:
                 raise RuntimeError("BakedField: %s is on %s, dist on %s" % (k, t.device, dev))
         dist = dist.detach().to(torch.float32).contiguous()
         valid = torch.ones(shape, dtype=torch.bool, device=dev) if valid is None else (valid.detach() != 0).contiguous()
-        sets = {k: t.detach().to(torch.float32).contiguous() for k, t in named.items()}
+        if rows_dtype is not None and not isinstance(rows_dtype, dict):
+            rows_dtype = {k: rows_dtype for k in named}
+        rows_dtype = dict(rows_dtype or {})
+        for k, d in rows_dtype.items():
+            if k not in named:
+                raise ValueError("from_arrays: rows_dtype names the unknown set %r" % (k,))
+            if d not in (torch.float32, torch.float16):
+                raise ValueError("from_arrays: rows_dtype of %r must be torch.float32 or torch.float16, got %r" % (k, d))
+        sets = {}
+        for k, t in named.items():
+            t = t.detach()
+            if rows_dtype.get(k) == torch.float16:
+                t = t.to(torch.float16)
+                sets[k] = t if _rows_in_place(t) else t.contiguous()
+            else:
+                sets[k] = t.to(torch.float32).contiguous()
         fills = {k: (None if fills.get(k) is None else fills[k].detach().to(torch.float32).contiguous()) for k in sets}
         return cls(origin, step, dist, valid, sets, fills)
 
     @classmethod
-    def from_fusion(cls, fusion, boundaries, step_size, return_names=(), band=None):
+    def from_fusion(cls, fusion, boundaries, step_size, return_names=(), band=None, rows_dtype=None, max_rows_bytes=1 << 30):
         """Fusion.bake: one eval_grid, its tensors viewed (not copied) as the volume; a projected name's fill row is -b, what
         Fusion.eval returns for an all-invalid point.  With a band: the distance-only grid pass, d3f_band_mark, and ONE
         batch_eval of the M stored voxel centres (the grid's own axis values) whose [M, C] outputs are the row arrays -- no
-        [nx, ny, nz, C] array exists at any time."""
+        [nx, ny, nz, C] array exists at any time.
+        rows_dtype=torch.float16: the rows are stored as half (half()) and never all held in float32 -- the voxel centres (banded: the M
+        stored ones; dense: all, after the distance-only grid pass, in flat-index order) are evaluated in chunks of at most max_rows_bytes
+        of float32 rows and each chunk is converted into the preallocated half array: the bytes of bake(...).half()."""
         from .fusion import _grid_axes
         names = list(return_names)
+        if rows_dtype not in (None, torch.float32, torch.float16):
+            raise ValueError("bake: rows_dtype must be None, torch.float32 or torch.float16, got %r" % (rows_dtype,))
+        as_half = rows_dtype == torch.float16
+        if as_half and (isinstance(max_rows_bytes, bool) or not isinstance(max_rows_bytes, int) or max_rows_bytes < 1):
+            raise ValueError("bake: max_rows_bytes must be a positive integer, got %r" % (max_rows_bytes,))
         if band is not None:
             band = _check_band(band, "bake")
             _check_band_names(names)
         with torch.no_grad():
-            res = fusion.eval_grid(boundaries, step_size, return_names=names if band is None else [])
+            res = fusion.eval_grid(boundaries, step_size, return_names=names if band is None and not as_half else [])
         nx, ny, nz = res["grid_shape"]
         if min(nx, ny, nz) < 2:
             raise ValueError("bake: the grid %s needs at least two voxels along every axis" % ((nx, ny, nz),))
@@ -512,11 +545,17 @@ class BakedField:
         step = float(torch.tensor(step_size, dtype=torch.float32))
         fills = {k: (-fusion._head_on(k, dev)[1]).contiguous() if k in fusion._projections else None for k in names}
         dist, valid = res["dist"].view(nx, ny, nz), res["valid_mask"].view(nx, ny, nz)
-        if band is None:
+        if band is None and not as_half:
             sets = {k: res[k].view(nx, ny, nz, -1) for k in names}
             return cls(origin, step, dist, valid, sets, fills, boundaries=boundaries, axes=axes)
         field = cls(origin, step, dist, valid, {}, {}, boundaries=boundaries, axes=axes)
+        if band is None:                  # dense half rows: every voxel centre, slab by slab
+            rows = field._half_rows(fusion, names, None, nx * ny * nz, max_rows_bytes)
+            field._sets, field._fills = {k: rows[k].view(nx, ny, nz, -1) for k in names}, dict(fills)
+            return field
         mark = field._mark(band)
+        if as_half:
+            return field._banded(band, mark, field._half_rows(fusion, names, mark[2], mark[2].shape[0], max_rows_bytes), fills)
         pts = field._voxel_centres(mark[2])
         with torch.no_grad():
             if pts.shape[0] > 0:
@@ -525,6 +564,22 @@ class BakedField:
             else:                     # nothing within the band: empty row arrays of the widths the query would write
                 rows = {k: torch.empty((0, fusion._query_map(k, dev).shape[3]), dtype=torch.float32, device=dev) for k in names}
         return field._banded(band, mark, rows, fills)
+
+    def _half_rows(self, fusion, names, voxels, m, max_rows_bytes):
+        """{name: float16 [m, C]}: the rows of the voxels with flat indices `voxels` (None: 0 .. m - 1), evaluated at their centres in
+        chunks of at most max_rows_bytes of float32 rows (all names together; at least one voxel) and converted chunk by chunk"""
+        dev = self.device
+        widths = {k: fusion._query_map(k, dev).shape[3] for k in names}
+        rows = {k: torch.empty((m, widths[k]), dtype=torch.float16, device=dev) for k in names}
+        per = max(1, int(max_rows_bytes) // max(4 * sum(widths.values()), 1))
+        with torch.no_grad():
+            for q0 in range(0, m if names else 0, per):
+                q1 = min(q0 + per, m)
+                idx = torch.arange(q0, q1, device=dev) if voxels is None else voxels[q0:q1]
+                part = fusion.batch_eval(self._voxel_centres(idx), return_names=names)
+                for k in names:
+                    rows[k][q0:q1] = part[k]      # (copy_ converts: round to nearest even, as .to(torch.float16))
+        return rows
 
     # ---- the band -------------------------------------------------------------------------------------------------------------
     def _mark(self, band):
@@ -626,11 +681,72 @@ class BakedField:
                            _lib.ptr(self.cell_valid))
 
     def _set_array(self, names):
+        """the d3f_volume_set array of `names`: the one place that builds them, so the storage word always follows the tensor's dtype"""
         arr = (_lib.VolumeSet * max(len(names), 1))()
         for s, k in enumerate(names):
             t = self._sets[k]
-            arr[s] = _lib.VolumeSet(t.data_ptr(), t.shape[-1], 0, t.stride(-2), _lib.ptr(self._fills[k]))      # dense: the voxel stride; banded: the row stride
+            word = _lib.DTYPE_F16 if t.dtype == torch.float16 else _lib.DTYPE_F32
+            arr[s] = _lib.VolumeSet(t.data_ptr(), t.shape[-1], word, t.stride(-2), _lib.ptr(self._fills[k]))      # dense: the voxel stride; banded: the row stride (in elements)
         return arr
+
+    # ---- storage of the rows ----------------------------------------------------------------------------------------------------
+    def rows_dtype(self, name):
+        """torch.float32 or torch.float16: how the rows of `name` are stored"""
+        self._names([name])
+        return self._sets[name].dtype
+
+    @property
+    def rows_bytes(self):
+        """the bytes of all stored rows (every set; dist, valid and the band's volumes are not counted)"""
+        return sum(t.numel() * t.element_size() for t in self._sets.values())
+
+    def _with_sets(self, sets):
+        """a field that shares everything of this one (dist / valid / cell_valid / slot / cell_band ...) but holds `sets`"""
+        f = object.__new__(type(self))
+        f.__dict__.update(self.__dict__)
+        f._sets, f._fills = dict(sets), dict(self._fills)
+        return f
+
+    def half(self, names=None, check=False):
+        """A new field whose named sets (None: all) are STORED as IEEE half: `.to(torch.float16)`, round to nearest even, a value beyond
+        +-65504 becomes +-Inf.  dist / valid / cell_valid / slot / cell_band are shared, not copied.  eval / eval_dist / backward /
+        autograd / raycast / render read such rows (d3f_volume_set's storage word): each half is widened exactly and takes the float32
+        chain, so a lookup equals the lookup of float() bit for bit at half the row bytes.  Fill rows, outputs and gradients stay float32.
+        The methods that read rows with loops of their own (pool, links / parts, flow, warp, align / normal_equations / relocate, locate)
+        raise TypeError on a half set: call float() first.
+        check=True: ValueError if a finite stored value of a valid voxel would not stay finite (one host synchronisation)."""
+        names = self._names(self.names() if names is None else names)
+        sets = dict(self._sets)
+        for k in names:
+            t = sets[k]
+            if t.dtype == torch.float16:
+                continue
+            h = t.to(torch.float16)
+            if check:
+                lost = torch.isfinite(t) & ~torch.isfinite(h)
+                if self.band is None:
+                    lost &= self.valid.unsqueeze(-1)
+                if bool(lost.any()):
+                    raise ValueError("half: set %r holds %d finite values of valid voxels beyond the half range (+-65504)" % (k, int(lost.sum())))
+            sets[k] = h
+        return self._with_sets(sets)
+
+    def float(self, names=None):
+        """The inverse of half(): a new field whose named sets (None: all) are float32, every stored half widened exactly"""
+        names = self._names(self.names() if names is None else names)
+        sets = dict(self._sets)
+        for k in names:
+            sets[k] = sets[k].to(torch.float32)
+        return self._with_sets(sets)
+
+    def _need_float_rows(self, who, names):
+        """the methods whose kernels read float32 rows only refuse a half set here, before any call into the library: converting on the
+        quiet would allocate the very array the caller chose not to hold"""
+        for k in names:
+            t = self._sets.get(k)
+            if t is not None and t.dtype != torch.float32:
+                raise TypeError("%s: the rows of %r are stored as %s and this method reads float32 rows; use float([%r]) (or float()) first"
+                                % (who, k, str(t.dtype).replace("torch.", ""), k))
 
     def _names(self, return_names):
         names = self.names() if return_names is None else list(return_names)
@@ -846,6 +962,7 @@ class BakedField:
         if connectivity not in (6, 18, 26):
             raise ValueError("links: connectivity must be 6, 18 or 26, got %r" % (connectivity,))
         code, threshold = self._link_rule("links", name, rule, tau, cos)
+        self._need_float_rows("links", [name])
         members = self._members(self._site_mask("links", iso, "free", sites))
         return self._links(name, code, threshold, members, connectivity)
 
@@ -856,6 +973,7 @@ class BakedField:
         per spatially connected piece of each instance.  pool, mask, largest, label_at, boxes_world and clearance(sites=) take the result."""
         self._check_ccl("parts", connectivity, min_voxels)
         code, threshold = self._link_rule("parts", name, rule, tau, cos)
+        self._need_float_rows("parts", [name])
         members = self._members(self._site_mask("parts", iso, "free", sites))
         links = self._links(name, code, threshold, members, connectivity)
         labels, kept, found, stats = self._label(members, connectivity, min_voxels, links=links)
@@ -881,6 +999,8 @@ class BakedField:
                 raise ValueError("flow: %r was not baked in %s, which holds %s" % (name, who, f.names()))
         if self._channels(name) != other._channels(name):
             raise ValueError("flow: %r has %d channels here and %d in the other field" % (name, self._channels(name), other._channels(name)))
+        self._need_float_rows("flow", [name])
+        other._need_float_rows("flow (the other field)", [name])
         if tuple(self.grid_shape) != tuple(other.grid_shape) or self.origin != other.origin or self.step != other.step:
             raise ValueError("flow: the fields must share one grid: %s at %s step %g here, %s at %s step %g there" % (
                 tuple(self.grid_shape), self.origin, self.step, tuple(other.grid_shape), other.origin, other.step))
@@ -965,6 +1085,7 @@ class BakedField:
         behind the part was never observed.  Rows are copied (background) or blended from eight corner rows (moved) in float32 without fused
         operations.  The result also has source, rows_known, part_box_from, part_box_to (see the class).  No host read on a dense field, the
         one of d3f_band_mark on a banded one.  Not differentiable."""
+        self._need_float_rows("warp", self._names(return_names))
         if isinstance(motions, PartMotions):
             self._check_same_grid("warp", "motions", motions)
             pose = motions.pose
@@ -1091,6 +1212,7 @@ class BakedField:
         if K > nx * ny * nz:
             raise ValueError("pool: count = %d exceeds the %d voxels" % (K, nx * ny * nz))
         names, voted = self._names(return_names), self._names(list(votes))
+        self._need_float_rows("pool", names + voted)
         wide = [k for k in voted if self._channels(k) > _lib.POOL_MAX_VOTE_CHANNELS]
         if wide:
             raise ValueError("pool: votes over %s: more than %d channels" % (wide, _lib.POOL_MAX_VOTE_CHANNELS))
@@ -1636,6 +1758,7 @@ class BakedField:
         from .corr_utils import _dist_code
         who = "locate"
         names = self._names([name])
+        self._need_float_rows(who, names)
         code = _dist_code(dist_type)
         dev = self.device
         if not isinstance(descriptors, torch.Tensor) or descriptors.dim() != 2:
@@ -1679,6 +1802,7 @@ class BakedField:
 
     def _align_problem(self, who, points, name, targets, dist_targets, weights, dist_weight, feat_weight, outside):
         """the checked, contiguous inputs of one alignment problem and the model centroids (d3f_volume_align_centroid)"""
+        self._need_float_rows(who, [] if name is None else [name])
         if not isinstance(points, torch.Tensor) or points.dim() != 3 or points.shape[2] != 3:
             raise ValueError("%s: points must be [I, n, 3], got %s" % (who, list(getattr(points, "shape", ())) or type(points).__name__))
         I, n = int(points.shape[0]), int(points.shape[1])
@@ -1835,6 +1959,7 @@ class BakedField:
         the host wait for the stream, as it does on its own.  No autograd: outputs never require grad."""
         from .consensus import consensus_poses
         who = "relocate"
+        self._need_float_rows(who, [name])
         if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3:
             raise ValueError("relocate: points must be [M, 3] (one model), got %s" % (list(getattr(points, "shape", ())) or type(points).__name__))
         M = int(points.shape[0])

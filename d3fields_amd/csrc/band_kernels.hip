@@ -86,10 +86,11 @@ __global__ __launch_bounds__(kBlock) void band_slot_kernel(const uint8_t *__rest
 struct BandRows {
     const VolSet &S;
     const int32_t (&slot)[8];
-    __device__ __forceinline__ void operator()(const float *(&row)[8]) const
+    template <class T>      // float, or _Float16 for a half set: the stride counts elements
+    __device__ __forceinline__ void operator()(const T *(&row)[8]) const
     {
 #pragma unroll
-        for (int c = 0; c < 8; ++c) row[c] = S.data + (int64_t)slot[c] * S.stride;
+        for (int c = 0; c < 8; ++c) row[c] = reinterpret_cast<const T *>(S.data) + (int64_t)slot[c] * S.stride;
     }
 };
 
@@ -107,8 +108,10 @@ __device__ __forceinline__ bool any_narrow(const VolParams &P, bool backward)
     return any;
 }
 
-template <bool WIDE>
-__global__ __launch_bounds__(kBlock, 4) void band_sample_kernel(BandParams B)
+// F16: some set of the launch is stored as half (volume_rows.h); the <.., false> instances are the float32-only code
+// (four workgroups per CU hold the float32 instances at 128 VGPRs; an instance with both row forms would spill there, so it asks for three)
+template <bool WIDE, bool F16>
+__global__ __launch_bounds__(kBlock, F16 ? 3 : 4) void band_sample_kernel(BandParams B)
 {
     const VolParams &P = B.V;
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -139,7 +142,7 @@ __global__ __launch_bounds__(kBlock, 4) void band_sample_kernel(BandParams B)
             int32_t slot[8] = {0, 0, 0, 0, 0, 0, 0, 0};
             if (in_band) load_slots(B, me.base, sx, sy, slot);
             for (int s = 0; s < P.n_sets; ++s)
-                if (P.sets[s].C <= kVolNarrowMax) sample_row(P.sets[s], i, in_band, w, 0, 1, BandRows{P.sets[s], slot});
+                if (P.sets[s].C <= kVolNarrowMax) sample_row<F16>(P.sets[s], i, in_band, w, 0, 1, BandRows{P.sets[s], slot});
         }
     }
     if (WIDE) {
@@ -156,12 +159,12 @@ __global__ __launch_bounds__(kBlock, 4) void band_sample_kernel(BandParams B)
             int32_t slot[8] = {0, 0, 0, 0, 0, 0, 0, 0};
             if (base >= 0) load_slots(B, base, sx, sy, slot);
             for (int s = 0; s < P.n_sets; ++s)
-                if (P.sets[s].C > kVolNarrowMax) sample_row(P.sets[s], wave_first + src, base >= 0, w, sub, 16, BandRows{P.sets[s], slot});
+                if (P.sets[s].C > kVolNarrowMax) sample_row<F16>(P.sets[s], wave_first + src, base >= 0, w, sub, 16, BandRows{P.sets[s], slot});
         }
     }
 }
 
-template <bool WIDE>
+template <bool WIDE, bool F16>
 __global__ __launch_bounds__(kBlock) void band_backward_kernel(BandParams B)
 {
     const VolParams &P = B.V;
@@ -190,7 +193,7 @@ __global__ __launch_bounds__(kBlock) void band_backward_kernel(BandParams B)
                     int32_t slot[8];
                     load_slots(B, me.base, sx, sy, slot);
                     for (int s = 0; s < P.n_sets; ++s)
-                        if (P.sets[s].C <= kVolNarrowMax && P.sets[s].grad) backward_row(P.sets[s], i, f, 0, 1, acc, BandRows{P.sets[s], slot});
+                        if (P.sets[s].C <= kVolNarrowMax && P.sets[s].grad) backward_row<F16>(P.sets[s], i, f, 0, 1, acc, BandRows{P.sets[s], slot});
                 }
             }
         }
@@ -210,7 +213,7 @@ __global__ __launch_bounds__(kBlock) void band_backward_kernel(BandParams B)
                 load_slots(B, base, sx, sy, slot);
                 for (int s = 0; s < P.n_sets; ++s)
                     if (P.sets[s].C > kVolNarrowMax && P.sets[s].grad)
-                        backward_row(P.sets[s], wave_first + src, f, sub, 16, part, BandRows{P.sets[s], slot});
+                        backward_row<F16>(P.sets[s], wave_first + src, f, sub, 16, part, BandRows{P.sets[s], slot});
             }
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
@@ -233,6 +236,13 @@ bool any_wide(const VolParams &P, bool backward)
 {
     for (int s = 0; s < P.n_sets; ++s)
         if (P.sets[s].C > kVolNarrowMax && (!backward || P.sets[s].grad)) return true;
+    return false;
+}
+
+bool any_f16(const VolParams &P, bool backward)
+{
+    for (int s = 0; s < P.n_sets; ++s)
+        if (P.sets[s].f16 && (!backward || P.sets[s].grad)) return true;
     return false;
 }
 
@@ -261,10 +271,10 @@ hipError_t launch_band_sample(const BandParams &B, hipStream_t s)
 {
     const int64_t blocks = (B.V.n + kBlock - 1) / kBlock;
     if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-    if (any_wide(B.V, false))
-        hipLaunchKernelGGL(band_sample_kernel<true>, dim3((unsigned)blocks), dim3(kBlock), 0, s, B);
-    else
-        hipLaunchKernelGGL(band_sample_kernel<false>, dim3((unsigned)blocks), dim3(kBlock), 0, s, B);
+    const bool wide = any_wide(B.V, false), f16 = any_f16(B.V, false);
+    auto kernel = wide ? (f16 ? band_sample_kernel<true, true> : band_sample_kernel<true, false>)
+                       : (f16 ? band_sample_kernel<false, true> : band_sample_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kBlock), 0, s, B);
     return hipGetLastError();
 }
 
@@ -272,10 +282,10 @@ hipError_t launch_band_backward(const BandParams &B, hipStream_t s)
 {
     const int64_t blocks = (B.V.n + kBlock - 1) / kBlock;
     if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-    if (any_wide(B.V, true))
-        hipLaunchKernelGGL(band_backward_kernel<true>, dim3((unsigned)blocks), dim3(kBlock), 0, s, B);
-    else
-        hipLaunchKernelGGL(band_backward_kernel<false>, dim3((unsigned)blocks), dim3(kBlock), 0, s, B);
+    const bool wide = any_wide(B.V, true), f16 = any_f16(B.V, true);
+    auto kernel = wide ? (f16 ? band_backward_kernel<true, true> : band_backward_kernel<true, false>)
+                       : (f16 ? band_backward_kernel<false, true> : band_backward_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kBlock), 0, s, B);
     return hipGetLastError();
 }
 

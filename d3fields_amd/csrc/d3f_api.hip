@@ -80,15 +80,37 @@ int check_set_shape(const char *who, int s, const d3f_volume_set &set)
     return fail(D3F_ERR_BAD_SHAPE, "%s: set %d: C=%d outside [1,%d]", who, s, set.C, D3F_VOLUME_MAX_CHANNELS);
 }
 
+// the set's storage word (`reserved`): float32 everywhere; IEEE half only where the entry point's row loops have a half form (half_ok: the
+// four lookups).  Called by EVERY entry point that takes a set, right after check_set_shape: a loop that knows float32 only would read
+// halves as floats and run past the rows.
+int check_set_storage(const char *who, int s, const d3f_volume_set &set, bool half_ok)
+{
+    if (set.reserved == D3F_DTYPE_F32 || (half_ok && set.reserved == D3F_DTYPE_F16)) return D3F_OK;
+    if (set.reserved == D3F_DTYPE_F16)
+        return fail(D3F_ERR_BAD_DTYPE, "%s: set %d: rows stored as half (D3F_DTYPE_F16) are read by the lookups only; this entry point needs float32 rows", who, s);
+    return fail(D3F_ERR_BAD_DTYPE, "%s: set %d: storage word %d is neither D3F_DTYPE_F32 nor D3F_DTYPE_F16", who, s, set.reserved);
+}
+
+bool set_is_half(const d3f_volume_set &set) { return set.reserved == D3F_DTYPE_F16; }
+
 int check_set_layout(const char *who, int s, const d3f_volume_set &set)
 {
     if (set.stride_voxel < set.C) return fail(D3F_ERR_BAD_LAYOUT, "%s: set %d: stride_voxel=%lld < C=%d", who, s, (long long)set.stride_voxel, set.C);
+    if (set_is_half(set)) {
+        if (!aligned(set.data, 2)) return fail(D3F_ERR_BAD_LAYOUT, "%s: set %d: data must be 2-byte aligned", who, s);
+        return D3F_OK;
+    }
     if (!aligned(set.data, 4)) return fail(D3F_ERR_BAD_LAYOUT, "%s: set %d: data must be 4-byte aligned", who, s);
     return D3F_OK;
 }
 
 // may the rows of a set move as 16-byte vectors?  (and-ed with the alignment of what is written or read beside them by the caller)
-bool set_reads_vectors(const d3f_volume_set &set) { return set.C % 4 == 0 && set.stride_voxel % 4 == 0 && aligned(set.data, 16); }
+// float32: four channels to a vector; half: eight
+bool set_reads_vectors(const d3f_volume_set &set)
+{
+    const int per = set_is_half(set) ? 8 : 4;
+    return set.C % per == 0 && set.stride_voxel % per == 0 && aligned(set.data, 16);
+}
 
 // one thread per item, per_block items to a workgroup: the grid's x has 31 bits
 int check_launch_blocks(const char *who, int64_t n, int64_t per_block)
@@ -715,7 +737,7 @@ int d3f_volume_cell_valid(const d3f_volume *vol, uint8_t *cell_valid_out, void *
 
 // the checks the forward and the backward lookup share; fills P but for the outputs / gradients.  Returns 1 for "nothing to do".
 static int volume_common(const char *who, const d3f_volume *vol, const float *pts, int64_t n, const d3f_volume_set *sets, int32_t n_sets,
-                         d3f::VolParams &P, bool null_data_ok = false)
+                         d3f::VolParams &P, bool null_data_ok = false, bool half_ok = true)
 {
     const int rc = check_volume(who, vol);
     if (rc != D3F_OK) return rc;
@@ -723,8 +745,10 @@ static int volume_common(const char *who, const d3f_volume *vol, const float *pt
     if (n < 0) return fail(D3F_ERR_INVALID_ARG, "%s: n=%lld is negative", who, (long long)n);
     if (n_sets < 0 || n_sets > D3F_MAX_MAPS) return fail(D3F_ERR_BAD_SHAPE, "%s: n_sets=%d outside [0,%d]", who, n_sets, D3F_MAX_MAPS);
     if (n_sets > 0 && !sets) return fail(D3F_ERR_INVALID_ARG, "%s: sets is NULL with n_sets=%d", who, n_sets);
-    for (int s = 0; s < n_sets; ++s)
+    for (int s = 0; s < n_sets; ++s) {
         if (const int rc = check_set_shape(who, s, sets[s])) return rc;
+        if (const int rc = check_set_storage(who, s, sets[s], half_ok)) return rc;
+    }
     if (n == 0) return 1;
     if (!vol->dist || !vol->cell_valid || !pts) return fail(D3F_ERR_INVALID_ARG, "%s: vol->dist / vol->cell_valid / pts must be non-NULL", who);
     if (!aligned(vol->dist, 4) || !aligned(pts, 4)) return fail(D3F_ERR_BAD_LAYOUT, "%s: vol->dist / pts must be 4-byte aligned", who);
@@ -740,6 +764,7 @@ static int volume_common(const char *who, const d3f_volume *vol, const float *pt
         S.stride = sets[s].stride_voxel;
         S.C = sets[s].C;
         S.vec = set_reads_vectors(sets[s]) ? 1 : 0;      // and-ed with the alignment of out / grad by the caller
+        S.f16 = set_is_half(sets[s]) ? 1 : 0;
     }
     P.dist = vol->dist;
     P.cell = vol->cell_valid;
@@ -941,6 +966,7 @@ int d3f_volume_links(const uint8_t *site, const uint8_t *valid, const int32_t *s
         return fail(D3F_ERR_INVALID_ARG, "volume_links: threshold=%g, the cosine bound must lie in [0, 1]", (double)threshold);
     if (const int rc = check_extents("volume_links", nx, ny, nz)) return rc;
     if (const int rc = check_set_shape("volume_links", 0, *set)) return rc;
+    if (const int rc = check_set_storage("volume_links", 0, *set, false)) return rc;
     if (const int rc = check_set_layout("volume_links", 0, *set)) return rc;
     if (!aligned(slot, 4) || !aligned(out_links, 2)) return fail(D3F_ERR_BAD_LAYOUT, "volume_links: slot must be 4-byte aligned, out_links 2-byte aligned");
     hipError_t e = d3f::launch_volume_links(site, valid, slot, nx, ny, nz, set->data, set->C, set->stride_voxel, set_reads_vectors(*set), rule, threshold,
@@ -961,6 +987,8 @@ int d3f_volume_flow(const uint8_t *site_a, const int32_t *slot_a, const d3f_volu
     if (const int rc = check_extents("volume_flow", nx, ny, nz)) return rc;
     if (const int rc = check_set_shape("volume_flow", 0, *set_a)) return rc;             // set 0: set_a, set 1: set_b
     if (set_b->C != set_a->C) return fail(D3F_ERR_BAD_SHAPE, "volume_flow: C=%d of set_a, C=%d of set_b: the sets must have the same width", set_a->C, set_b->C);
+    if (const int rc = check_set_storage("volume_flow", 0, *set_a, false)) return rc;
+    if (const int rc = check_set_storage("volume_flow", 1, *set_b, false)) return rc;
     if (const int rc = check_set_layout("volume_flow", 0, *set_a)) return rc;
     if (const int rc = check_set_layout("volume_flow", 1, *set_b)) return rc;
     if (!aligned(slot_a, 4) || !aligned(slot_b, 4) || !aligned(out_target, 4) || !aligned(out_cost, 4) || !aligned(out_axis_cost, 4))
@@ -1002,6 +1030,7 @@ int d3f_volume_pool(const int32_t *label, int32_t nx, int32_t ny, int32_t nz, in
     int64_t mean_channels = 0;
     for (int s = 0; s < n_sets; ++s) {
         if (const int rc = check_set_shape("volume_pool", s, sets[s])) return rc;
+        if (const int rc = check_set_storage("volume_pool", s, sets[s], false)) return rc;
         if (modes[s] == D3F_POOL_VOTES && sets[s].C > D3F_POOL_MAX_VOTE_CHANNELS)
             return fail(D3F_ERR_BAD_SHAPE, "volume_pool: set %d: votes over C=%d channels, more than %d", s, sets[s].C, D3F_POOL_MAX_VOTE_CHANNELS);
         if (modes[s] == D3F_POOL_MEAN) mean_channels += sets[s].C;
@@ -1148,8 +1177,10 @@ int d3f_volume_warp_rows(const d3f_warp_rows *args, void *stream)
     const int32_t n_sets = args->n_sets;
     if (n_sets < 0 || n_sets > D3F_MAX_MAPS) return fail(D3F_ERR_BAD_SHAPE, "%s: n_sets=%d outside [0,%d]", who, n_sets, D3F_MAX_MAPS);
     if (n_sets > 0 && !args->sets) return fail(D3F_ERR_INVALID_ARG, "%s: sets is NULL with n_sets=%d", who, n_sets);
-    for (int s = 0; s < n_sets; ++s)
+    for (int s = 0; s < n_sets; ++s) {
         if (const int rc = check_set_shape(who, s, args->sets[s])) return rc;
+        if (const int rc = check_set_storage(who, s, args->sets[s], false)) return rc;
+    }
     if (args->m == 0) return D3F_OK;
     const bool empty = band && band->n_rows == 0;
     if (!args->source || !args->out_known || (args->K > 0 && !args->pose) || (n_sets > 0 && !args->out_sets))
@@ -1173,6 +1204,7 @@ int d3f_volume_warp_rows(const d3f_warp_rows *args, void *stream)
         S.stride = set.stride_voxel;
         S.C = set.C;
         S.vec = set_reads_vectors(set) && aligned(args->out_sets[s], 16) ? 1 : 0;
+        S.f16 = 0;
     }
     A.source = args->source;
     A.pose = args->pose;
@@ -1380,7 +1412,7 @@ int d3f_volume_align_accumulate(const d3f_volume *vol, const d3f_band *band, con
     const bool empty_band = band && band->n_rows == 0;
     d3f::AlignParams A;
     // (volume_common answers n == 0 with "nothing to do": the instances only scale the count)
-    const int rc = volume_common(who, vol, points, I == 0 ? 0 : n, set, set ? 1 : 0, A.V, empty_band);
+    const int rc = volume_common(who, vol, points, I == 0 ? 0 : n, set, set ? 1 : 0, A.V, empty_band, false);      // (float32 rows only)
     if (rc != D3F_OK) return rc == 1 ? D3F_OK : rc;
     const int64_t chunks = d3f::align_chunks(n);
     if (chunks > 0x7fffffffLL / I) return fail(D3F_ERR_BAD_SHAPE, "%s: I=%lld instances of %lld workgroups are too many for one launch", who, (long long)I, (long long)chunks);

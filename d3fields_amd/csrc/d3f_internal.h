@@ -210,13 +210,14 @@ hipError_t launch_volume_gaussian(const float *src, float *dst, int nx, int ny, 
 // volume_kernels.hip: trilinear lookups in a baked volume
 constexpr int kVolNarrowMax = 16;           // channels of a set sampled one lane per point; a wider set takes sixteen lanes per point
 struct VolSet {
-    const float *data;       // row of voxel q: data + q * stride
+    const float *data;       // row of voxel q: data + q * stride (f16: in halves, from the same address)
     const float *fill;       // C floats or nullptr (zeros): the row of a point that is not valid
     float *out;              // forward: [n, C]
     const float *grad;       // backward: [n, C] or nullptr
     int64_t stride;
     int32_t C;
     int32_t vec;             // 1: rows (and out / grad rows) move as 16-byte vectors
+    int32_t f16;             // 1: the rows are IEEE half (D3F_DTYPE_F16): d3f_volume_sample / d3f_band_sample and their backwards only
 };
 struct VolParams {
     const float *dist;

@@ -30,19 +30,22 @@ struct DenseRows {
     const VolSet &S;
     int32_t base;
     int64_t sx, sy;
-    __device__ __forceinline__ void operator()(const float *(&row)[8]) const
+    template <class T>      // float, or _Float16 for a half set: the stride counts elements
+    __device__ __forceinline__ void operator()(const T *(&row)[8]) const
     {
 #pragma unroll
-        for (int c = 0; c < 8; ++c) row[c] = S.data + ((int64_t)base + corner_offset(c, sx, sy)) * S.stride;
+        for (int c = 0; c < 8; ++c) row[c] = reinterpret_cast<const T *>(S.data) + ((int64_t)base + corner_offset(c, sx, sy)) * S.stride;
     }
 };
 
+template <bool F16>
 __device__ __forceinline__ void sample_row(const VolSet &S, int64_t i, int32_t base, const float (&w)[8], int64_t sx, int64_t sy, int first, int lanes)
 {
-    sample_row(S, i, base >= 0, w, first, lanes, DenseRows{S, base, sx, sy});
+    sample_row<F16>(S, i, base >= 0, w, first, lanes, DenseRows{S, base, sx, sy});
 }
 
-template <bool WIDE>
+// F16: some set of the launch is stored as half (volume_rows.h); the <.., false> instances are the float32-only code
+template <bool WIDE, bool F16>
 __global__ __launch_bounds__(kBlock) void volume_sample_kernel(VolParams P)
 {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -64,7 +67,7 @@ __global__ __launch_bounds__(kBlock) void volume_sample_kernel(VolParams P)
         P.out_dist[i] = d;
         P.out_valid[i] = me.base >= 0 ? 1 : 0;
         for (int s = 0; s < P.n_sets; ++s)
-            if (P.sets[s].C <= kVolNarrowMax) sample_row(P.sets[s], i, me.base, w, sx, sy, 0, 1);
+            if (P.sets[s].C <= kVolNarrowMax) sample_row<F16>(P.sets[s], i, me.base, w, sx, sy, 0, 1);
     }
     if (WIDE) {
         const int lane = threadIdx.x & 63, group = lane >> 4, sub = lane & 15;
@@ -78,20 +81,21 @@ __global__ __launch_bounds__(kBlock) void volume_sample_kernel(VolParams P)
             float w[8];
             corner_weights(tx, ty, tz, w);
             for (int s = 0; s < P.n_sets; ++s)
-                if (P.sets[s].C > kVolNarrowMax) sample_row(P.sets[s], wave_first + src, base, w, sx, sy, sub, 16);
+                if (P.sets[s].C > kVolNarrowMax) sample_row<F16>(P.sets[s], wave_first + src, base, w, sx, sy, sub, 16);
         }
     }
 }
 
 // ---- backward -----------------------------------------------------------------------------------------------------------------
 // the point is valid and S.grad is not null
+template <bool F16>
 __device__ __forceinline__ void backward_row(const VolSet &S, int64_t i, int32_t base, const FaceWeights &f, int64_t sx, int64_t sy, int first, int lanes,
                                              float (&acc)[3])
 {
-    backward_row(S, i, f, first, lanes, acc, DenseRows{S, base, sx, sy});
+    backward_row<F16>(S, i, f, first, lanes, acc, DenseRows{S, base, sx, sy});
 }
 
-template <bool WIDE>
+template <bool WIDE, bool F16>
 __global__ __launch_bounds__(kBlock) void volume_backward_kernel(VolParams P)
 {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -111,7 +115,7 @@ __global__ __launch_bounds__(kBlock) void volume_backward_kernel(VolParams P)
                 add_derivative(f, v, P.grad_dist[i], acc);
             }
             for (int s = 0; s < P.n_sets; ++s)
-                if (P.sets[s].C <= kVolNarrowMax && P.sets[s].grad) backward_row(P.sets[s], i, me.base, f, sx, sy, 0, 1, acc);
+                if (P.sets[s].C <= kVolNarrowMax && P.sets[s].grad) backward_row<F16>(P.sets[s], i, me.base, f, sx, sy, 0, 1, acc);
         }
     }
     if (WIDE) {
@@ -126,7 +130,7 @@ __global__ __launch_bounds__(kBlock) void volume_backward_kernel(VolParams P)
             if (base >= 0) {
                 const FaceWeights f = face_weights(tx, ty, tz);
                 for (int s = 0; s < P.n_sets; ++s)
-                    if (P.sets[s].C > kVolNarrowMax && P.sets[s].grad) backward_row(P.sets[s], wave_first + src, base, f, sx, sy, sub, 16, part);
+                    if (P.sets[s].C > kVolNarrowMax && P.sets[s].grad) backward_row<F16>(P.sets[s], wave_first + src, base, f, sx, sy, sub, 16, part);
             }
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
@@ -170,6 +174,13 @@ bool any_wide(const VolParams &P, bool backward)
     return false;
 }
 
+bool any_f16(const VolParams &P, bool backward)
+{
+    for (int s = 0; s < P.n_sets; ++s)
+        if (P.sets[s].f16 && (!backward || P.sets[s].grad)) return true;
+    return false;
+}
+
 }  // namespace
 
 hipError_t launch_volume_cell_valid(const uint8_t *valid, uint8_t *cell, int nx, int ny, int nz, hipStream_t s)
@@ -183,10 +194,10 @@ hipError_t launch_volume_sample(const VolParams &P, hipStream_t s)
 {
     const int64_t blocks = (P.n + kBlock - 1) / kBlock;
     if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-    if (any_wide(P, false))
-        hipLaunchKernelGGL(volume_sample_kernel<true>, dim3((unsigned)blocks), dim3(kBlock), 0, s, P);
-    else
-        hipLaunchKernelGGL(volume_sample_kernel<false>, dim3((unsigned)blocks), dim3(kBlock), 0, s, P);
+    const bool wide = any_wide(P, false), f16 = any_f16(P, false);
+    auto kernel = wide ? (f16 ? volume_sample_kernel<true, true> : volume_sample_kernel<true, false>)
+                       : (f16 ? volume_sample_kernel<false, true> : volume_sample_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kBlock), 0, s, P);
     return hipGetLastError();
 }
 
@@ -194,10 +205,10 @@ hipError_t launch_volume_backward(const VolParams &P, hipStream_t s)
 {
     const int64_t blocks = (P.n + kBlock - 1) / kBlock;
     if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-    if (any_wide(P, true))
-        hipLaunchKernelGGL(volume_backward_kernel<true>, dim3((unsigned)blocks), dim3(kBlock), 0, s, P);
-    else
-        hipLaunchKernelGGL(volume_backward_kernel<false>, dim3((unsigned)blocks), dim3(kBlock), 0, s, P);
+    const bool wide = any_wide(P, true), f16 = any_f16(P, true);
+    auto kernel = wide ? (f16 ? volume_backward_kernel<true, true> : volume_backward_kernel<true, false>)
+                       : (f16 ? volume_backward_kernel<false, true> : volume_backward_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kBlock), 0, s, P);
     return hipGetLastError();
 }
 

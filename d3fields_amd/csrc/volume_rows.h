@@ -68,9 +68,61 @@ __device__ __forceinline__ float4 blend4(const float (&w)[8], const float4 (&v)[
 
 __device__ __forceinline__ float fill_of(const VolSet &S, int ch) { return S.fill ? S.fill[ch] : 0.0f; }
 
+// ---- rows stored as IEEE half (VolSet::f16; include/d3fields_hip.h) ------------------------------------------
+// A stored half is widened to float32 exactly (one v_cvt_f32_f16; subnormals, signed zeros, Inf and NaN keep their value) and then
+// takes the float32 chain above unchanged: w0 * v0 is a plain multiply, the seven other corners are fmaf.  One 16-byte load is eight
+// channels, so a vector step is two blend4 / eight add_derivative.
+// The eight halves of a vector stay four packed words until a channel is needed (kept as integers so that the compiler does not widen
+// all eight corners x eight channels up front: 64 VGPRs where the float32 form holds 32).
+__device__ __forceinline__ float widen(uint32_t bits16) { return (float)__builtin_bit_cast(_Float16, (uint16_t)bits16); }
+
+template <int J>      // channel J = 0..7 of a 16-byte vector of halves
+__device__ __forceinline__ float channel_f16(const uint4 &r)
+{
+    const uint32_t word = J < 2 ? r.x : J < 4 ? r.y : J < 6 ? r.z : r.w;
+    return widen((J & 1) ? word >> 16 : word & 0xffffu);
+}
+
+// channels FIRST .. FIRST + 3 of eight corner vectors, widened
+template <int FIRST>
+__device__ __forceinline__ float4 blend4_f16(const float (&w)[8], const uint4 (&r)[8])
+{
+    float4 v[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) v[c] = make_float4(channel_f16<FIRST>(r[c]), channel_f16<FIRST + 1>(r[c]), channel_f16<FIRST + 2>(r[c]), channel_f16<FIRST + 3>(r[c]));
+    return blend4(w, v);
+}
+
+// the row loops of sample_row for a half set; o: the output row of the point
+template <class Rows>
+__device__ __forceinline__ void sample_row_f16(const VolSet &S, float *o, const float (&w)[8], int first, int lanes, Rows rows)
+{
+    const _Float16 *row[8];
+    rows(row);
+    if (S.vec) {
+        for (int k = 8 * first; k < S.C; k += 8 * lanes) {
+            uint4 r[8];
+#pragma unroll
+            for (int c = 0; c < 8; ++c) r[c] = *reinterpret_cast<const uint4 *>(row[c] + k);
+            *reinterpret_cast<float4 *>(o + k) = blend4_f16<0>(w, r);
+            __builtin_amdgcn_sched_barrier(0);      // the first four channels are done before the other four are widened
+            *reinterpret_cast<float4 *>(o + k + 4) = blend4_f16<4>(w, r);
+        }
+    } else {
+        for (int k = first; k < S.C; k += lanes) {
+            float v[8];
+#pragma unroll
+            for (int c = 0; c < 8; ++c) v[c] = (float)row[c][k];
+            o[k] = blend(w, v);
+        }
+    }
+}
+
 // channels [first, C) in steps of `lanes` vectors / floats of the row of point i: lanes = 1 is phase A, 16 is phase B.
 // rows(row): called for a point that has rows (`has`), fills the eight corner row pointers; otherwise the fill row is written
-template <class Rows>
+// (float32 in either storage: a half set with vectors has C % 8 == 0 and 16-byte output rows, so the float4 loop covers it).
+// F16: the instance may meet half sets (a wave-uniform branch per set, outside the channel loop); false is the float32-only code.
+template <bool F16 = false, class Rows>
 __device__ __forceinline__ void sample_row(const VolSet &S, int64_t i, bool has, const float (&w)[8], int first, int lanes, Rows rows)
 {
     float *o = S.out + i * S.C;
@@ -81,6 +133,10 @@ __device__ __forceinline__ void sample_row(const VolSet &S, int64_t i, bool has,
         } else {
             for (int k = first; k < S.C; k += lanes) o[k] = fill_of(S, k);
         }
+        return;
+    }
+    if (F16 && S.f16) {
+        sample_row_f16(S, o, w, first, lanes, rows);
         return;
     }
     const float *row[8];
@@ -140,11 +196,57 @@ __device__ __forceinline__ void add_derivative(const FaceWeights &f, const float
     acc[2] = fmaf(g, dz, acc[2]);
 }
 
-// S.grad is not null; rows(row) fills the eight corner row pointers of the point's cell
+// acc += g * d blend / d (tx, ty, tz) for channel J of eight corner vectors
+template <int J>
+__device__ __forceinline__ void add_derivative_f16(const FaceWeights &f, const uint4 (&r)[8], float g, float (&acc)[3])
+{
+    const float v[8] = {channel_f16<J>(r[0]), channel_f16<J>(r[1]), channel_f16<J>(r[2]), channel_f16<J>(r[3]),
+                        channel_f16<J>(r[4]), channel_f16<J>(r[5]), channel_f16<J>(r[6]), channel_f16<J>(r[7])};
+    add_derivative(f, v, g, acc);
+    __builtin_amdgcn_sched_barrier(0);      // one channel's eight widened corners at a time
+}
+
+// the row loops of backward_row for a half set; g: the (float32) gradient row of the point.  Channels are summed in ascending order within
+// a lane, eight to a vector step: with one lane (a narrow set) that is the float32 form's order, with sixteen the channel -> lane map differs.
 template <class Rows>
+__device__ __forceinline__ void backward_row_f16(const VolSet &S, const float *g, const FaceWeights &f, int first, int lanes, float (&acc)[3], Rows rows)
+{
+    const _Float16 *row[8];
+    rows(row);
+    if (S.vec) {
+        for (int k = 8 * first; k < S.C; k += 8 * lanes) {
+            uint4 r[8];
+#pragma unroll
+            for (int c = 0; c < 8; ++c) r[c] = *reinterpret_cast<const uint4 *>(row[c] + k);
+            const float4 g0 = *reinterpret_cast<const float4 *>(g + k), g1 = *reinterpret_cast<const float4 *>(g + k + 4);
+            add_derivative_f16<0>(f, r, g0.x, acc);
+            add_derivative_f16<1>(f, r, g0.y, acc);
+            add_derivative_f16<2>(f, r, g0.z, acc);
+            add_derivative_f16<3>(f, r, g0.w, acc);
+            add_derivative_f16<4>(f, r, g1.x, acc);
+            add_derivative_f16<5>(f, r, g1.y, acc);
+            add_derivative_f16<6>(f, r, g1.z, acc);
+            add_derivative_f16<7>(f, r, g1.w, acc);
+        }
+    } else {
+        for (int k = first; k < S.C; k += lanes) {
+            float v[8];
+#pragma unroll
+            for (int c = 0; c < 8; ++c) v[c] = (float)row[c][k];
+            add_derivative(f, v, g[k], acc);
+        }
+    }
+}
+
+// S.grad is not null; rows(row) fills the eight corner row pointers of the point's cell.  F16: as sample_row
+template <bool F16 = false, class Rows>
 __device__ __forceinline__ void backward_row(const VolSet &S, int64_t i, const FaceWeights &f, int first, int lanes, float (&acc)[3], Rows rows)
 {
     const float *g = S.grad + i * S.C;
+    if (F16 && S.f16) {
+        backward_row_f16(S, g, f, first, lanes, acc, rows);
+        return;
+    }
     const float *row[8];
     rows(row);
     if (S.vec) {

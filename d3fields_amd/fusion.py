@@ -923,7 +923,7 @@ class Fusion:
             self._subtract_offsets(out, names, dev)
         return out
 
-    def bake(self, boundaries, step_size, return_names=[], band=None):
+    def bake(self, boundaries, step_size, return_names=[], band=None, rows_dtype=None, max_rows_bytes=1 << 30):
         """eval_grid(boundaries, step_size, return_names) kept as a baked.BakedField: its eval(pts) interpolates that volume
         trilinearly (eight corner rows per point, no projection into the views) and has a closed-form gradient w.r.t. pts.
         The field holds the grid query's tensors and no reference to this object: it keeps answering, unchanged, after update().
@@ -931,9 +931,13 @@ class Fusion:
 
         band (a world length > 0, e.g. 0.005): bake channel rows only for the voxels a cell within `band` of the surface needs
         (DESIGN.md 15).  dist / valid stay dense; the rows come from one batch_eval of the stored voxel centres, so no
-        [nx, ny, nz, C] array is ever allocated.  Lookups add 'in_band'; outside the band a set reads as its fill row."""
+        [nx, ny, nz, C] array is ever allocated.  Lookups add 'in_band'; outside the band a set reads as its fill row.
+
+        rows_dtype=torch.float16: the rows are STORED as IEEE half (BakedField.half) and never all held in float32:
+        the voxel centres are evaluated in chunks of at most max_rows_bytes of float32 rows, each converted into the half array.
+        The result holds the bytes of bake(...).half()."""
         from .baked import BakedField
-        return BakedField.from_fusion(self, boundaries, step_size, return_names, band=band)
+        return BakedField.from_fusion(self, boundaries, step_size, return_names, band=band, rows_dtype=rows_dtype, max_rows_bytes=max_rows_bytes)
 
     def grid_shell(self, boundaries, step_size, dist_threshold=0.005):
         """Flat indices (ascending) and coordinates of the grid points with valid_mask & |dist| < dist_threshold:

@@ -398,10 +398,28 @@ typedef struct d3f_volume {
     const uint8_t *valid;
     const uint8_t *cell_valid;
 } d3f_volume;
+/* STORAGE of a set's rows: the word `reserved` of d3f_volume_set (the name is kept; every caller that passes 0 gets float32 rows, as before).
+ *   D3F_DTYPE_F32 (0)  rows of C floats.
+ *   D3F_DTYPE_F16 (1)  rows of C IEEE halves.  `data` then points at 2-byte elements (its declared type stays const float *),
+ *                      stride_voxel and C stay in ELEMENTS (as the strides of d3f_channel_map do), data must be 2-byte aligned
+ *                      (D3F_ERR_BAD_LAYOUT otherwise).  fill, every output row and every gradient row stay float32.
+ *   any other value    D3F_ERR_BAD_DTYPE, in every entry point that takes a set.
+ * Half rows are read by d3f_volume_sample, d3f_volume_sample_backward, d3f_band_sample and d3f_band_sample_backward only; every other
+ * entry point that takes a set (d3f_volume_pool, d3f_volume_links, d3f_volume_flow, d3f_volume_align_accumulate, d3f_volume_warp_rows)
+ * answers D3F_ERR_BAD_DTYPE for a half set and launches nothing.  Storage is per set: one call may mix float32 and half sets.
+ * Numerics of a half set: each stored half is widened to float32 exactly (subnormals, +-0, +-Inf and NaN included) and then runs
+ * through the unchanged chain -- out = w0*v0 (a plain multiply: a product of -0 stays -0), then fma(w_c, v_c, out) in the corner order
+ * of d3f_volume_sample, and the face-weight chain of the backward -- so a lookup returns the bits the float32 lookup returns on the
+ * widened rows.  The backward of a set of up to 16 channels equals the float32 backward on the widened rows bit for bit; a wider set's
+ * per-lane partial sums cover other channels than the float32 form's (eight per vector, not four), so its last bits may differ from
+ * it, but not between two runs.
+ * Vector rule of a half set: rows move as 16-byte vectors (EIGHT channels) where C % 8 == 0, stride_voxel % 8 == 0, data is 16-byte
+ * aligned and the output / gradient rows are 16-byte aligned, as scalar halves otherwise; the boundary between one lane per point
+ * and sixteen lanes per point stays 16 channels. */
 typedef struct d3f_volume_set {
     const float *data;
     int32_t C;
-    int32_t reserved;          /* 0 */
+    int32_t reserved;          /* the storage word: D3F_DTYPE_F32 (0) or D3F_DTYPE_F16 (1), see above */
     int64_t stride_voxel;
     const float *fill;         /* C floats on the device, or NULL = zeros */
 } d3f_volume_set;
