@@ -131,6 +131,20 @@ class WarpRows(ctypes.Structure):
                 ("voxels", _vp), ("m", _i64), ("out_sets", ctypes.POINTER(_vp)), ("out_known", _vp)]
 
 
+class MergeSelect(ctypes.Structure):
+    """struct d3f_merge_select (host memory; include/d3fields_hip_ext.h)"""
+    _fields_ = [("nx", _i32), ("ny", _i32), ("nz", _i32), ("reserved", _i32), ("dist_a", _vp), ("valid_a", _vp), ("weight_a", _vp), ("dist_b", _vp), ("valid_b", _vp),
+                ("weight_b", _vp), ("weight_a_all", _f32), ("weight_b_all", _f32), ("w_max", _f32), ("gap", _f32), ("out_dist", _vp), ("out_weight", _vp),
+                ("out_beta", _vp), ("out_valid", _vp), ("out_kind", _vp)]
+
+
+class MergeRows(ctypes.Structure):
+    """struct d3f_merge_rows (host memory; include/d3fields_hip_ext.h)"""
+    _fields_ = [("nx", _i32), ("ny", _i32), ("nz", _i32), ("n_sets", _i32), ("band_a", ctypes.POINTER(Band)), ("band_b", ctypes.POINTER(Band)),
+                ("sets_a", ctypes.POINTER(VolumeSet)), ("sets_b", ctypes.POINTER(VolumeSet)), ("kind", _vp), ("beta", _vp), ("voxels", _vp), ("m", _i64),
+                ("out_sets", ctypes.POINTER(_vp)), ("out_known", _vp), ("reserved", _i64)]
+
+
 class Pinhole(ctypes.Structure):
     """struct d3f_pinhole (host memory)"""
     _fields_ = [("K", _f32 * 9), ("pose", _f32 * 12), ("H", _i32), ("W", _i32)]
@@ -294,6 +308,16 @@ STREAMED = frozenset("d3f_" + n for n in """
 # the others that return a status; everything else returns a value
 STATUS = STREAMED | {"d3f_eval_plan_query", "d3f_eval_plan_query_lattice"}
 
+# The entry points added after ABI 16's main table, declared by include/d3fields_hip_ext.h and exported by the same library.  The main header and
+# the three tables above are closed (host tests pin their counts); what is added since goes here, in the same (restype, argtypes) form.
+EXT_SIGNATURES = {
+    "d3f_volume_merge_select": (ctypes.c_int, [ctypes.POINTER(MergeSelect), _vp]),
+    "d3f_volume_merge_rows": (ctypes.c_int, [ctypes.POINTER(MergeRows), _vp]),
+}
+# ... whose declaration ends in `void *stream`
+EXT_STREAMED = frozenset(["d3f_volume_merge_select", "d3f_volume_merge_rows"])
+MERGE_NONE, MERGE_KEEP, MERGE_NEW, MERGE_BLEND, MERGE_RESET = 0, 1, 2, 3, 4
+
 _lib = None
 
 
@@ -322,8 +346,8 @@ def load():
             raise ImportError("libd3fields_hip.so is %s and hipcc is not available to build it: %s"
                               % ("missing" if not os.path.exists(path) else "out of date with csrc/", exc))
     lib = ctypes.CDLL(path)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)     # AttributeError if the .so lacks a declared symbol
+    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
+        fn = getattr(lib, name)     # AttributeError if the .so lacks a declared symbol (of either header)
         fn.restype = res
         fn.argtypes = args
     got = lib.d3f_abi_version()
@@ -376,7 +400,7 @@ class on:
         return self._guard.__exit__(*exc)
 
     def __getattr__(self, name):
-        if name not in SIGNATURES:
+        if name not in SIGNATURES and name not in EXT_SIGNATURES:
             raise AttributeError(name)
         return functools.partial(self._call, name)
 
@@ -390,10 +414,10 @@ class on:
             elif isinstance(a, ctypes.Structure):
                 a = ctypes.byref(a)
             conv.append(a)
-        if name in STREAMED:
+        if name in STREAMED or name in EXT_STREAMED:
             conv.append(self.stream)
         out = getattr(self.lib, name)(*conv)
-        if name in STATUS:
+        if name in STATUS or (name in EXT_SIGNATURES and EXT_SIGNATURES[name][0] is ctypes.c_int):
             return check(out)
         return out
 

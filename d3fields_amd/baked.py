@@ -423,11 +423,17 @@ class BakedField:
     part_box_from and part_box_to int32 [K, 2, 3] (the inclusive boxes of each part's owner voxels and of the voxels it won; an empty box is
     lo = INT32_MAX, hi = INT32_MIN).  They are None elsewhere.
 
+    A MERGED field (merge()) is an ordinary dense or banded field that also has weight float32 [nx, ny, nz] (the summed weight of what was
+    seen there, 0 where nothing was; the next merge() uses it as this field's weights), merged_from uint8 [nx, ny, nz] (MERGE_NONE 0: neither
+    field knew the voxel, MERGE_KEEP 1: only the older one, MERGE_NEW 2: only the newer one, MERGE_BLEND 3: both, averaged, MERGE_RESET 4: both,
+    too far apart, the newer one taken) and rows_known bool as a warped field has it.  weight and merged_from are None elsewhere.
+
     A BANDED field (to_band / Fusion.bake(band=)) holds each set as [M, C] rows of the stored voxels instead, and has
     band (the world length), slot int32 [nx, ny, nz] (-1: no row), cell_band uint8 [nx-1, ny-1, nz-1], band_voxels int32 [M]
     (ascending flat indices), band_points() and stored_fraction; its lookups add 'in_band'.  A dense field has band = None.
 
     It holds tensors only -- no reference to the Fusion that made it -- and stays valid after Fusion.update()."""
+    MERGE_NONE, MERGE_KEEP, MERGE_NEW, MERGE_BLEND, MERGE_RESET = _lib.MERGE_NONE, _lib.MERGE_KEEP, _lib.MERGE_NEW, _lib.MERGE_BLEND, _lib.MERGE_RESET
 
     def __init__(self, origin, step, dist, valid, sets, fills, boundaries=None, axes=None):
         self.origin = tuple(float(o) for o in origin)
@@ -448,6 +454,7 @@ class BakedField:
         self.d2 = self.nearest_voxel = self.sites = None      # a clearance field's (clearance()); None on every other field
         self.cost = self.next_voxel = self.free = None         # a travel field's (travel()); None on every other field
         self.source = self.rows_known = self.part_box_from = self.part_box_to = None      # a warped field's (warp()); None on every other field
+        self.weight = self.merged_from = None                  # a merged field's (merge(), which sets rows_known too); None on every other field
         self.cell_valid = torch.empty((nx - 1, ny - 1, nz - 1), dtype=torch.uint8, device=self.device)
         with self._on() as q:
             q.d3f_volume_cell_valid(self._volume(), self.cell_valid)
@@ -1154,6 +1161,126 @@ class BakedField:
         moved.source = source
         moved.part_box_from, moved.part_box_to = boxes[:, 0:6].reshape(K, 2, 3), boxes[:, 6:12].reshape(K, 2, 3)
         return moved
+
+    # ---- merge ----------------------------------------------------------------------------------------------------------------
+    def _merge_weight(self, who, what, w):
+        """a scalar weight: a finite number > 0"""
+        if isinstance(w, bool) or not isinstance(w, (int, float)):
+            raise TypeError("%s: %s must be a number, got %s" % (who, what, type(w).__name__))
+        if not (0.0 < float(w) < math.inf):
+            raise ValueError("%s: %s must be finite and > 0, got %r" % (who, what, w))
+        return float(w)
+
+    def merge(self, other, weight=1.0, other_weight=1.0, max_weight=None, reset_gap=None, band=None, return_names=None):
+        """What have I seen so far?  This field (the older one, the memory) and `other` (the newer observation) on the same grid merged into
+        one (d3f_volume_merge_select / d3f_volume_merge_rows, csrc/merge_kernels.hip, declared by include/d3fields_hip_ext.h; DESIGN.md
+        section 30) -> a new BakedField.  What only one of them knows is kept, what both know is averaged by their weights -- the running
+        weighted average of a truncated distance volume, extended to the channel rows -- and where their distances differ by more than
+        reset_gap the newer one wins:
+
+            memory = a
+            for b in later_bakes:
+                pm        = b_prev.flow(...).motions(...)
+                predicted = memory.warp(pm, owners, which=...)
+                memory    = predicted.merge(b)
+
+        other         a BakedField of this grid, dense or banded, its sets float32 or half (half rows are widened exactly; the result is float32)
+        weight        this field's weight per voxel where it has no `weight` volume (a merged field has one, and then it is used instead)
+        other_weight  a number, or a float32 [nx, ny, nz] tensor (a per-voxel view count, say); left at 1.0 with `other` a merged field: other.weight
+        max_weight    the cap of the summed weight (None: no cap): with a cap the memory never outweighs a new frame by more than max_weight : w
+        reset_gap     a world length in dist's units (None: never): both usable and |dist - other.dist| > reset_gap -> the voxel is `other`'s
+        band          None: the result is dense iff both fields are dense, else banded with self.band or, this field being dense, other.band;
+                      a world length: the result is banded with it
+        return_names  the sets of the result (None: the names both fields hold); each must have equal channels on both sides
+        A voxel is usable on a side iff it is valid there, its dist is not NaN and its weight is finite and > 0.  Rows: both fields have one
+        -> a + beta * (b - a) per channel with beta = w_b / (w_a + w_b); one has -> that row, bit for bit; none (a banded side stores none
+        there) -> this field's fill row and rows_known False.  The result also has weight, merged_from and rows_known (see the class).  A
+        banded result goes select, d3f_band_mark on the merged dist, the rows of the stored voxels only: no dense row array exists at any
+        time.  No host read on the dense path, the one of d3f_band_mark on the banded one.  Not differentiable."""
+        if not isinstance(other, BakedField):
+            raise TypeError("merge: other must be a BakedField, got %s" % type(other).__name__)
+        self._check_same_grid("merge", "other", other)
+        if other.device != self.device:
+            raise ValueError("merge: other is on %s, the field on %s" % (other.device, self.device))
+        if return_names is None:
+            return_names = [k for k in self.names() if k in other._sets]
+        names = self._names(return_names)
+        other._names(names)
+        for k in names:
+            if self._channels(k) != other._channels(k):
+                raise ValueError("merge: set %r has %d channels here and %d in other" % (k, self._channels(k), other._channels(k)))
+        mine = getattr(self, "weight", None)
+        wa = 1.0 if mine is not None else self._merge_weight("merge", "weight", weight)
+        theirs, wb = None, 1.0
+        if isinstance(other_weight, torch.Tensor):
+            if other_weight.dtype != torch.float32 or tuple(other_weight.shape) != tuple(self.grid_shape):
+                raise ValueError("merge: other_weight must be a number or a float32 tensor of shape %s, got %s %s" % (
+                    tuple(self.grid_shape), other_weight.dtype, tuple(other_weight.shape)))
+            if other_weight.device != self.device:
+                raise ValueError("merge: other_weight is on %s, the field on %s" % (other_weight.device, self.device))
+            theirs = other_weight.detach().contiguous()
+        else:
+            wb = self._merge_weight("merge", "other_weight", other_weight)
+            if wb == 1.0 and getattr(other, "weight", None) is not None:
+                theirs = other.weight
+        if max_weight is None:
+            max_weight = math.inf
+        if isinstance(max_weight, bool) or not isinstance(max_weight, (int, float)):
+            raise TypeError("merge: max_weight must be None or a number, got %s" % type(max_weight).__name__)
+        if not float(max_weight) > 0.0:
+            raise ValueError("merge: max_weight must be > 0 (None or inf: no cap), got %r" % (max_weight,))
+        if reset_gap is None:
+            reset_gap = math.inf
+        if isinstance(reset_gap, bool) or not isinstance(reset_gap, (int, float)):
+            raise TypeError("merge: reset_gap must be None or a number, got %s" % type(reset_gap).__name__)
+        if not float(reset_gap) >= 0.0:
+            raise ValueError("merge: reset_gap must be >= 0 (None or inf: never reset), got %r" % (reset_gap,))
+        if band is not None:
+            band = _check_band(band, "merge")
+        elif self.band is not None or other.band is not None:
+            band = self.band if self.band is not None else other.band
+        if band is not None:
+            _check_band_names(names)
+        dev = self.device
+        if dev.type != "cuda":
+            raise RuntimeError("merge: the field must live on the ROCm device; there is no CPU path")
+        nx, ny, nz = self.grid_shape
+        n = nx * ny * nz
+        dist = torch.empty((nx, ny, nz), dtype=torch.float32, device=dev)
+        wsum = torch.empty((nx, ny, nz), dtype=torch.float32, device=dev)
+        beta = torch.empty((nx, ny, nz), dtype=torch.float32, device=dev)
+        valid = torch.empty((nx, ny, nz), dtype=torch.uint8, device=dev)
+        kind = torch.empty((nx, ny, nz), dtype=torch.uint8, device=dev)
+        sel = _lib.MergeSelect(nx, ny, nz, 0, _lib.ptr(self.dist), _lib.ptr(self.valid), _lib.ptr(mine), _lib.ptr(other.dist), _lib.ptr(other.valid),
+                               _lib.ptr(theirs), wa, wb, float(max_weight), float(reset_gap), _lib.ptr(dist), _lib.ptr(wsum), _lib.ptr(beta), _lib.ptr(valid),
+                               _lib.ptr(kind))
+        with self._on() as q:
+            q.d3f_volume_merge_select(sel)
+        merged = type(self)(self.origin, self.step, dist, valid.view(torch.bool), {}, {}, boundaries=self.boundaries, axes=self._axes)
+        if band is None:
+            mark, voxels, m = None, None, n
+        else:
+            mark = merged._mark(band)
+            voxels, m = mark[2], mark[2].shape[0]
+        known = torch.empty(m, dtype=torch.uint8, device=dev)
+        rows = {k: torch.empty((m, self._channels(k)), dtype=torch.float32, device=dev) for k in names}
+        if m > 0:
+            outs = (ctypes.c_void_p * max(len(names), 1))(*[rows[k].data_ptr() for k in names])
+            band_a = None if self.band is None else self._band_struct()
+            band_b = None if other.band is None else other._band_struct()
+            args = _lib.MergeRows(nx, ny, nz, len(names), None if band_a is None else ctypes.pointer(band_a), None if band_b is None else ctypes.pointer(band_b),
+                                  self._set_array(names), other._set_array(names), _lib.ptr(kind), _lib.ptr(beta), _lib.ptr(voxels), m, outs, _lib.ptr(known), 0)
+            with self._on() as q:
+                q.d3f_volume_merge_rows(args)
+        fills = {k: self._fills[k] for k in names}
+        if band is None:
+            merged._sets, merged._fills = {k: rows[k].view(nx, ny, nz, -1) for k in names}, fills
+            merged.rows_known = known.view(torch.bool).view(nx, ny, nz)
+        else:
+            merged = merged._banded(band, mark, rows, fills)
+            merged.rows_known = known.view(torch.bool)
+        merged.weight, merged.merged_from = wsum, kind
+        return merged
 
     def components(self, iso=0.0, unknown="free", connectivity=26, min_voxels=1, sites=None, links=None):
         """The connected components of the occupied voxels (d3f_volume_components) -> Components.

@@ -14,7 +14,8 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 INCLUDE = os.path.join(os.path.dirname(PKG_DIR), "include")
 LIB_PATH = os.path.join(PKG_DIR, "libd3fields_hip.so")
-SOURCES = ["fuse_launch.hip", "fuse_direct.hip", "fuse_runs.hip", "fuse_sliced.hip", "fuse_window.hip", "fuse_rows.hip", "fuse_backward.hip", "scan_kernels.hip", "order_kernels.hip", "grid_kernels.hip", "mesh_kernels.hip", "volume_kernels.hip", "band_kernels.hip", "edt_kernels.hip", "ccl_kernels.hip", "parts_kernels.hip", "flow_kernels.hip", "pool_kernels.hip", "motion_kernels.hip", "warp_kernels.hip", "geodesic_kernels.hip", "segment_kernels.hip", "peaks_kernels.hip", "align_kernels.hip", "consensus_kernels.hip", "raycast_kernels.hip", "pcd_kernels.hip", "assoc_kernels.hip", "misc_kernels.hip", "proj_kernels.hip", "moment_kernels.hip", "corr_kernels.hip", "track_kernels.hip", "d3f_api.hip"]
+PUBLIC_HEADERS = ["d3fields_hip.h", "d3fields_hip_ext.h"]      # the main table of the C ABI, and the entry points added after it
+SOURCES = ["fuse_launch.hip", "fuse_direct.hip", "fuse_runs.hip", "fuse_sliced.hip", "fuse_window.hip", "fuse_rows.hip", "fuse_backward.hip", "scan_kernels.hip", "order_kernels.hip", "grid_kernels.hip", "mesh_kernels.hip", "volume_kernels.hip", "band_kernels.hip", "edt_kernels.hip", "ccl_kernels.hip", "parts_kernels.hip", "flow_kernels.hip", "pool_kernels.hip", "motion_kernels.hip", "warp_kernels.hip", "merge_kernels.hip", "geodesic_kernels.hip", "segment_kernels.hip", "peaks_kernels.hip", "align_kernels.hip", "consensus_kernels.hip", "raycast_kernels.hip", "pcd_kernels.hip", "assoc_kernels.hip", "misc_kernels.hip", "proj_kernels.hip", "moment_kernels.hip", "corr_kernels.hip", "track_kernels.hip", "d3f_api.hip"]
 
 # -ffp-contract=off: the arithmetic contract says which products are fused; only
 # explicit fmaf() may fuse.  No -ffast-math: IEEE division and accurate expf are part of parity.
@@ -53,7 +54,7 @@ def source_fingerprint():
     h = hashlib.sha256(" ".join(HIPCC_FLAGS + _sources() + (["-DD3F_EXPERIMENTS"] if _experiments() else [])).encode())
     files = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if os.path.isfile(os.path.join(CSRC, f))]
     files += [os.path.join(CSRC, s) for s in EXPERIMENT_SOURCES if _experiments()]
-    for path in sorted(files) + [os.path.join(INCLUDE, "d3fields_hip.h")]:
+    for path in sorted(files) + [os.path.join(INCLUDE, h) for h in PUBLIC_HEADERS]:
         h.update(os.path.basename(path).encode())
         with open(path, "rb") as fh:
             h.update(fh.read())
@@ -95,7 +96,7 @@ def build_library(force=False, extra_flags=(), verbose=False):
 def _build_locked(hipcc, force, extra_flags, verbose):
     objdir = os.path.join(PKG_DIR, "build_exp" if _experiments() else "build")
     os.makedirs(objdir, exist_ok=True)
-    headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [os.path.join(INCLUDE, "d3fields_hip.h")]
+    headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [os.path.join(INCLUDE, h) for h in PUBLIC_HEADERS]
     cflags = [f for f in HIPCC_FLAGS if f != "-shared"] + list(extra_flags) + (["-DD3F_EXPERIMENTS"] if _experiments() else []) + ["-I", INCLUDE, "-I", CSRC, "-c"]
     jobs, objs = [], []
     for s in _sources():

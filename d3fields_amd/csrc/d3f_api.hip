@@ -8,6 +8,7 @@
 #include <stdlib.h>
 
 #include "d3f_internal.h"
+#include "d3fields_hip_ext.h"      // the entry points added after the main table of ABI 16
 
 namespace {
 
@@ -1218,6 +1219,120 @@ int d3f_volume_warp_rows(const d3f_warp_rows *args, void *stream)
     A.out_known = args->out_known;
     hipError_t e = d3f::launch_warp_rows(A, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_warp_rows launch");
+}
+
+// ---- two baked fields on one grid merged into one (merge_kernels.hip; declared by include/d3fields_hip_ext.h) ----
+// the grid of both calls: the extents of a d3f_volume
+static int check_merge_grid(const char *who, int32_t nx, int32_t ny, int32_t nz)
+{
+    d3f_volume vol = {};
+    vol.nx = nx; vol.ny = ny; vol.nz = nz;
+    return check_volume(who, &vol);
+}
+
+// in (0, +inf]
+static bool positive_or_inf(float x) { return x > 0.0f; }
+
+int d3f_volume_merge_select(const d3f_merge_select *args, void *stream)
+{
+    const char *who = "volume_merge_select";
+    if (!args) return fail(D3F_ERR_INVALID_ARG, "%s: args is NULL", who);
+    if (const int rc = check_merge_grid(who, args->nx, args->ny, args->nz)) return rc;
+    if (args->reserved != 0) return fail(D3F_ERR_INVALID_ARG, "%s: reserved=%d, must be 0", who, args->reserved);
+    if (!args->weight_a && !positive_finite(args->weight_a_all))
+        return fail(D3F_ERR_INVALID_ARG, "%s: weight_a_all=%g must be > 0 and finite where weight_a is NULL", who, (double)args->weight_a_all);
+    if (!args->weight_b && !positive_finite(args->weight_b_all))
+        return fail(D3F_ERR_INVALID_ARG, "%s: weight_b_all=%g must be > 0 and finite where weight_b is NULL", who, (double)args->weight_b_all);
+    if (!positive_or_inf(args->w_max)) return fail(D3F_ERR_INVALID_ARG, "%s: w_max=%g must be in (0, +inf]", who, (double)args->w_max);
+    if (!(args->gap >= 0.0f)) return fail(D3F_ERR_INVALID_ARG, "%s: gap=%g must be in [0, +inf]", who, (double)args->gap);
+    if (!args->dist_a || !args->valid_a || !args->dist_b || !args->valid_b)
+        return fail(D3F_ERR_INVALID_ARG, "%s: dist_a / valid_a / dist_b / valid_b must be non-NULL", who);
+    if (!args->out_dist || !args->out_weight || !args->out_beta || !args->out_valid || !args->out_kind)
+        return fail(D3F_ERR_INVALID_ARG, "%s: out_dist / out_weight / out_beta / out_valid / out_kind must be non-NULL", who);
+    if (!aligned(args->dist_a, 4) || !aligned(args->weight_a, 4) || !aligned(args->dist_b, 4) || !aligned(args->weight_b, 4) || !aligned(args->out_dist, 4) ||
+        !aligned(args->out_weight, 4) || !aligned(args->out_beta, 4))
+        return fail(D3F_ERR_BAD_LAYOUT, "%s: dist_a / weight_a / dist_b / weight_b / out_dist / out_weight / out_beta must be aligned to their element size", who);
+    d3f::MergeSelectArgs A;
+    A.dist_a = args->dist_a; A.weight_a = args->weight_a; A.valid_a = args->valid_a;
+    A.dist_b = args->dist_b; A.weight_b = args->weight_b; A.valid_b = args->valid_b;
+    A.wa = args->weight_a_all; A.wb = args->weight_b_all;
+    A.w_max = args->w_max; A.gap = args->gap;
+    A.n = (int64_t)args->nx * args->ny * args->nz;
+    A.out_dist = args->out_dist; A.out_weight = args->out_weight; A.out_beta = args->out_beta;
+    A.out_valid = args->out_valid; A.out_kind = args->out_kind;
+    hipError_t e = d3f::launch_merge_select(A, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_merge_select launch");
+}
+
+int d3f_volume_merge_rows(const d3f_merge_rows *args, void *stream)
+{
+    const char *who = "volume_merge_rows";
+    if (!args) return fail(D3F_ERR_INVALID_ARG, "%s: args is NULL", who);
+    if (const int rc = check_merge_grid(who, args->nx, args->ny, args->nz)) return rc;
+    const d3f_band *bands[2] = {args->band_a, args->band_b};
+    for (int side = 0; side < 2; ++side)
+        if (bands[side] && (bands[side]->n_rows < 0 || bands[side]->n_rows > 0x7fffffffLL))
+            return fail(D3F_ERR_BAD_SHAPE, "%s: band_%c->n_rows=%lld outside [0, 2^31 - 1]", who, 'a' + side, (long long)bands[side]->n_rows);
+    const int32_t n_sets = args->n_sets;
+    if (n_sets < 0 || n_sets > D3F_MAX_MAPS) return fail(D3F_ERR_BAD_SHAPE, "%s: n_sets=%d outside [0,%d]", who, n_sets, D3F_MAX_MAPS);
+    if (n_sets > 0 && (!args->sets_a || !args->sets_b)) return fail(D3F_ERR_INVALID_ARG, "%s: sets_a / sets_b is NULL with n_sets=%d", who, n_sets);
+    for (int s = 0; s < n_sets; ++s) {                           // (the messages count a's sets 0 .., b's n_sets ..)
+        if (const int rc = check_set_shape(who, s, args->sets_a[s])) return rc;
+        if (const int rc = check_set_shape(who, n_sets + s, args->sets_b[s])) return rc;
+        if (args->sets_a[s].C != args->sets_b[s].C)
+            return fail(D3F_ERR_BAD_SHAPE, "%s: pair %d: sets_a C=%d != sets_b C=%d", who, s, args->sets_a[s].C, args->sets_b[s].C);
+        if (const int rc = check_set_storage(who, s, args->sets_a[s], true)) return rc;
+        if (const int rc = check_set_storage(who, n_sets + s, args->sets_b[s], true)) return rc;
+    }
+    const int64_t n = (int64_t)args->nx * args->ny * args->nz;
+    if (args->reserved != 0) return fail(D3F_ERR_INVALID_ARG, "%s: reserved=%lld, must be 0", who, (long long)args->reserved);
+    if (args->m < 0) return fail(D3F_ERR_INVALID_ARG, "%s: m=%lld is negative", who, (long long)args->m);
+    if (!args->voxels && args->m != n) return fail(D3F_ERR_INVALID_ARG, "%s: m=%lld with voxels NULL, must be the voxel count %lld", who, (long long)args->m, (long long)n);
+    if (args->m == 0) return D3F_OK;
+    const bool empty[2] = {bands[0] && bands[0]->n_rows == 0, bands[1] && bands[1]->n_rows == 0};
+    if (!args->kind || !args->beta || !args->out_known || (n_sets > 0 && !args->out_sets))
+        return fail(D3F_ERR_INVALID_ARG, "%s: kind / beta / out_known / out_sets must be non-NULL", who);
+    for (int side = 0; side < 2; ++side)
+        if (bands[side] && !empty[side] && !bands[side]->slot)
+            return fail(D3F_ERR_INVALID_ARG, "%s: band_%c->slot must be non-NULL with n_rows > 0", who, 'a' + side);
+    if (!aligned(args->beta, 4) || !aligned(args->voxels, 4) || (bands[0] && !empty[0] && !aligned(bands[0]->slot, 4)) ||
+        (bands[1] && !empty[1] && !aligned(bands[1]->slot, 4)))
+        return fail(D3F_ERR_BAD_LAYOUT, "%s: beta / voxels / band_a->slot / band_b->slot must be aligned to their element size", who);
+    d3f::MergeRowsArgs A;
+    for (int s = 0; s < n_sets; ++s) {
+        const d3f_volume_set &sa = args->sets_a[s], &sb = args->sets_b[s];
+        if (!sa.data && !empty[0]) return fail(D3F_ERR_INVALID_ARG, "%s: set %d: data is NULL", who, s);
+        if (!sb.data && !empty[1]) return fail(D3F_ERR_INVALID_ARG, "%s: set %d: data is NULL", who, n_sets + s);
+        if (const int rc = check_set_layout(who, s, sa)) return rc;
+        if (const int rc = check_set_layout(who, n_sets + s, sb)) return rc;
+        if (!aligned(sa.fill, 4)) return fail(D3F_ERR_BAD_LAYOUT, "%s: set %d: fill must be 4-byte aligned", who, s);
+        if (!args->out_sets[s]) return fail(D3F_ERR_INVALID_ARG, "%s: out_sets[%d] is NULL", who, s);
+        if (!aligned(args->out_sets[s], 4)) return fail(D3F_ERR_BAD_LAYOUT, "%s: out_sets[%d] must be 4-byte aligned", who, s);
+        d3f::MergeSet &S = A.sets[s];
+        S.a = sa.data;
+        S.b = sb.data;
+        S.fill = sa.fill;
+        S.out = static_cast<float *>(args->out_sets[s]);
+        S.stride_a = sa.stride_voxel;
+        S.stride_b = sb.stride_voxel;
+        S.C = sa.C;
+        S.vec = set_reads_vectors(sa) && set_reads_vectors(sb) && aligned(args->out_sets[s], 16) ? 1 : 0;
+        S.f16_a = set_is_half(sa) ? 1 : 0;
+        S.f16_b = set_is_half(sb) ? 1 : 0;
+    }
+    A.kind = args->kind;
+    A.beta = args->beta;
+    A.voxels = args->voxels;
+    A.m = args->m;
+    A.n = n;
+    A.banded_a = bands[0] != nullptr;
+    A.banded_b = bands[1] != nullptr;
+    A.slot_a = bands[0] && !empty[0] ? bands[0]->slot : nullptr;
+    A.slot_b = bands[1] && !empty[1] ? bands[1]->slot : nullptr;
+    A.n_sets = n_sets;
+    A.out_known = args->out_known;
+    hipError_t e = d3f::launch_merge_rows(A, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_merge_rows launch");
 }
 
 // ---- cost-to-go through free space (geodesic_kernels.hip) ----

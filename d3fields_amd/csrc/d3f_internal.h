@@ -382,6 +382,38 @@ struct WarpRowsArgs {
 hipError_t launch_warp_select(const WarpSelectArgs &A, hipStream_t s);
 hipError_t launch_warp_rows(const WarpRowsArgs &A, hipStream_t s);
 
+// merge_kernels.hip: two baked fields on one grid merged into one (include/d3fields_hip_ext.h)
+struct MergeSelectArgs {
+    const float *dist_a, *weight_a, *dist_b, *weight_b;      // a weight volume or nullptr: the scalar
+    const uint8_t *valid_a, *valid_b;
+    float wa, wb, w_max, gap;
+    int64_t n;
+    float *out_dist, *out_weight, *out_beta;
+    uint8_t *out_valid, *out_kind;
+};
+struct MergeSet {
+    const void *a, *b;           // the rows of either side: floats or halves (f16_a / f16_b)
+    const float *fill;           // a's fill row or nullptr (zeros)
+    float *out;                  // [m, C]
+    int64_t stride_a, stride_b;  // in elements
+    int32_t C;
+    int32_t vec;                 // 1: both rows and the output row move as 16-byte vectors
+    int32_t f16_a, f16_b;
+};
+struct MergeRowsArgs {
+    const uint8_t *kind;
+    const float *beta;
+    const int32_t *voxels;       // or nullptr: every voxel in flat order (m = the voxel count)
+    const int32_t *slot_a, *slot_b;      // a banded side: nullptr with no stored voxel
+    bool banded_a, banded_b;
+    int64_t m, n;
+    int32_t n_sets;
+    MergeSet sets[D3F_MAX_MAPS];
+    uint8_t *out_known;
+};
+hipError_t launch_merge_select(const MergeSelectArgs &A, hipStream_t s);
+hipError_t launch_merge_rows(const MergeRowsArgs &A, hipStream_t s);
+
 // geodesic_kernels.hip: cost-to-go through free space, exact shortest paths on the lattice; w: host int32[3]
 struct GeoLayout { int64_t header, flags, list, total; int64_t tiles; };
 GeoLayout geodesic_layout(int nx, int ny, int nz);
