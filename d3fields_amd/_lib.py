@@ -145,6 +145,25 @@ class MergeRows(ctypes.Structure):
                 ("out_sets", ctypes.POINTER(_vp)), ("out_known", _vp), ("reserved", _i64)]
 
 
+class CoarsenSelect(ctypes.Structure):
+    """struct d3f_coarsen_select (host memory; include/d3fields_hip_pyramid.h)"""
+    _fields_ = [("nx", _i32), ("ny", _i32), ("nz", _i32), ("min_children", _i32), ("dist", _vp), ("valid", _vp), ("out_dist", _vp), ("out_valid", _vp),
+                ("out_children", _vp), ("reserved", _i64)]
+
+
+class CoarsenRows(ctypes.Structure):
+    """struct d3f_coarsen_rows (host memory; include/d3fields_hip_pyramid.h)"""
+    _fields_ = [("nx", _i32), ("ny", _i32), ("nz", _i32), ("n_sets", _i32), ("band", ctypes.POINTER(Band)), ("sets", ctypes.POINTER(VolumeSet)), ("children", _vp),
+                ("voxels", _vp), ("m", _i64), ("out_sets", ctypes.POINTER(_vp)), ("out_known", _vp), ("reserved", _i64)]
+
+
+class FlowSeeded(ctypes.Structure):
+    """struct d3f_flow_seeded (host memory; include/d3fields_hip_pyramid.h)"""
+    _fields_ = [("site_a", _vp), ("slot_a", _vp), ("set_a", ctypes.POINTER(VolumeSet)), ("site_b", _vp), ("slot_b", _vp), ("set_b", ctypes.POINTER(VolumeSet)),
+                ("seed", _vp), ("nx", _i32), ("ny", _i32), ("nz", _i32), ("radius", _i32), ("max_cost2", _f32), ("reserved", _i32), ("out_target", _vp),
+                ("out_cost", _vp), ("out_axis_cost", _vp)]
+
+
 class Pinhole(ctypes.Structure):
     """struct d3f_pinhole (host memory)"""
     _fields_ = [("K", _f32 * 9), ("pose", _f32 * 12), ("H", _i32), ("W", _i32)]
@@ -318,6 +337,27 @@ EXT_SIGNATURES = {
 EXT_STREAMED = frozenset(["d3f_volume_merge_select", "d3f_volume_merge_rows"])
 MERGE_NONE, MERGE_KEEP, MERGE_NEW, MERGE_BLEND, MERGE_RESET = 0, 1, 2, 3, 4
 
+# The extension header is closed as well (a host test pins it to the merge pair).  From here on a feature brings a header of its own and ONE
+# entry here: header file name -> (signatures in the (restype, argtypes) form, the names whose declaration ends in `void *stream`).  load(),
+# on.__getattr__ and on._call treat every entry as they treat EXT_*, and tests/test_pyramid_host.py checks each header against its own table.
+FEATURE_TABLES = {
+    "d3fields_hip_pyramid.h": ({
+        "d3f_volume_coarsen_select": (ctypes.c_int, [ctypes.POINTER(CoarsenSelect), _vp]),
+        "d3f_volume_coarsen_rows": (ctypes.c_int, [ctypes.POINTER(CoarsenRows), _vp]),
+        "d3f_volume_flow_seeded": (ctypes.c_int, [ctypes.POINTER(FlowSeeded), _vp]),
+    }, frozenset(["d3f_volume_coarsen_select", "d3f_volume_coarsen_rows", "d3f_volume_flow_seeded"])),
+}
+FLOW_SEED_MAX = 16384
+
+
+def _feature(name):
+    """(restype, argtypes, streamed) of an entry point of FEATURE_TABLES, or None"""
+    for signatures, streamed in FEATURE_TABLES.values():
+        if name in signatures:
+            return signatures[name] + (name in streamed,)
+    return None
+
+
 _lib = None
 
 
@@ -346,8 +386,9 @@ def load():
             raise ImportError("libd3fields_hip.so is %s and hipcc is not available to build it: %s"
                               % ("missing" if not os.path.exists(path) else "out of date with csrc/", exc))
     lib = ctypes.CDLL(path)
-    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
-        fn = getattr(lib, name)     # AttributeError if the .so lacks a declared symbol (of either header)
+    features = [item for signatures, _ in FEATURE_TABLES.values() for item in signatures.items()]
+    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + features:
+        fn = getattr(lib, name)     # AttributeError if the .so lacks a declared symbol (of any header)
         fn.restype = res
         fn.argtypes = args
     got = lib.d3f_abi_version()
@@ -400,7 +441,7 @@ class on:
         return self._guard.__exit__(*exc)
 
     def __getattr__(self, name):
-        if name not in SIGNATURES and name not in EXT_SIGNATURES:
+        if name not in SIGNATURES and name not in EXT_SIGNATURES and _feature(name) is None:
             raise AttributeError(name)
         return functools.partial(self._call, name)
 
@@ -414,10 +455,11 @@ class on:
             elif isinstance(a, ctypes.Structure):
                 a = ctypes.byref(a)
             conv.append(a)
-        if name in STREAMED or name in EXT_STREAMED:
+        feature = _feature(name)
+        if name in STREAMED or name in EXT_STREAMED or (feature is not None and feature[2]):
             conv.append(self.stream)
         out = getattr(self.lib, name)(*conv)
-        if name in STATUS or (name in EXT_SIGNATURES and EXT_SIGNATURES[name][0] is ctypes.c_int):
+        if name in STATUS or (name in EXT_SIGNATURES and EXT_SIGNATURES[name][0] is ctypes.c_int) or (feature is not None and feature[0] is ctypes.c_int):
             return check(out)
         return out
 

@@ -210,11 +210,13 @@ class Flow:
                   takes no part
     offset        float64 [nx, ny, nz, 3] or None (refine=False): the sub-voxel correction in voxel units, per axis
                   0.5 (f- - f+) / (f- - 2 f0 + f+) clamped to [-0.5, 0.5]; 0 where a side is +Inf or the denominator is not > 0; NaN where unmatched
+    coarse        the flows of the coarser levels, coarsest first, on the Flow that BakedField.flow_pyramid returns; None on every other flow
     origin, step, grid_shape   of the fields it came from; no reference to the fields themselves"""
 
     def __init__(self, origin, step, target, cost, axis_cost=None):
         self.origin, self.step, self.grid_shape = tuple(origin), float(step), torch.Size(target.shape)
         self.target, self.cost, self.axis_cost = target, cost, axis_cost
+        self.coarse = None
         self.matched = target >= 0
         n = target.numel()
         own = _voxel_coords(torch.arange(n, device=target.device).view(self.grid_shape), self.grid_shape)
@@ -241,6 +243,27 @@ class Flow:
                 raise ValueError("Flow.displacement: this flow was computed with refine=False; pass refined=False")
             return (d + self.offset) * self.step
         return torch.where(self.matched[..., None], d * self.step, torch.full_like(d, float("nan")))
+
+    def seed(self, grid_shape, refined=True):
+        """The prediction this flow makes for the next FINER grid (BakedField.coarsen halves a grid; this goes the other way) -> int32
+        [nx, ny, nz, 3] in fine voxels, the `seed` of BakedField.flow on that grid.  Fine voxel (x, y, z) takes coarse voxel (x >> 1, y >> 1,
+        z >> 1): where that voxel is matched the seed is 2 * voxel_offset, or with refined and an `offset` round(2 * (voxel_offset +
+        offset)) (float64, round half to even); where it is unmatched the seed is 0.  grid_shape must halve to this flow's grid
+        ((n + 1) // 2 per axis).  Torch indexing only, no kernel."""
+        try:
+            fine = tuple(int(e) for e in grid_shape)
+        except (TypeError, ValueError):
+            raise TypeError("Flow.seed: grid_shape must be three integers, got %r" % (grid_shape,))
+        if len(fine) != 3 or tuple((e + 1) // 2 for e in fine) != tuple(self.grid_shape) or min(fine) < 1:
+            raise ValueError("Flow.seed: grid_shape %s does not halve to this flow's grid %s" % (fine, tuple(self.grid_shape)))
+        dev = self.target.device
+        ix, iy, iz = (torch.arange(e, device=dev) >> 1 for e in fine)
+        if refined and self.offset is not None:
+            whole = torch.round(2.0 * (self.voxel_offset.double() + self.offset))
+            whole = torch.where(self.matched[..., None], whole, torch.zeros_like(whole)).to(torch.int32)
+        else:
+            whole = 2 * self.voxel_offset      # (0 where unmatched)
+        return whole[ix[:, None, None], iy[None, :, None], iz[None, None, :]].contiguous()
 
     def consistent(self, back, tol_voxels=1):
         """The forward-backward test -> bool [nx, ny, nz]: a voxel passes when it is matched, `back` (the flow of the other field to this one)
@@ -428,6 +451,10 @@ class BakedField:
     field knew the voxel, MERGE_KEEP 1: only the older one, MERGE_NEW 2: only the newer one, MERGE_BLEND 3: both, averaged, MERGE_RESET 4: both,
     too far apart, the newer one taken) and rows_known bool as a warped field has it.  weight and merged_from are None elsewhere.
 
+    A COARSENED field (coarsen() / pyramid()) is an ordinary dense or banded field at twice the step that also has children uint8 [nx, ny, nz]
+    (bit c = 4i + 2j + k: the finer voxel (2x + i, 2y + j, 2z + k) was valid with a dist that is no NaN) and rows_known as a merged field has it.
+    children is None elsewhere.
+
     A BANDED field (to_band / Fusion.bake(band=)) holds each set as [M, C] rows of the stored voxels instead, and has
     band (the world length), slot int32 [nx, ny, nz] (-1: no row), cell_band uint8 [nx-1, ny-1, nz-1], band_voxels int32 [M]
     (ascending flat indices), band_points() and stored_fraction; its lookups add 'in_band'.  A dense field has band = None.
@@ -455,6 +482,7 @@ class BakedField:
         self.cost = self.next_voxel = self.free = None         # a travel field's (travel()); None on every other field
         self.source = self.rows_known = self.part_box_from = self.part_box_to = None      # a warped field's (warp()); None on every other field
         self.weight = self.merged_from = None                  # a merged field's (merge(), which sets rows_known too); None on every other field
+        self.children = None                                   # a coarsened field's (coarsen(), which sets rows_known too); None on every other field
         self.cell_valid = torch.empty((nx - 1, ny - 1, nz - 1), dtype=torch.uint8, device=self.device)
         with self._on() as q:
             q.d3f_volume_cell_valid(self._volume(), self.cell_valid)
@@ -986,7 +1014,7 @@ class BakedField:
         labels, kept, found, stats = self._label(members, connectivity, min_voxels, links=links)
         return Components(self.origin, self.step, labels, kept, found, stats, members, connectivity, min_voxels)
 
-    def flow(self, other, name, radius_voxels=2, max_cost=None, iso=0.0, sites=None, other_sites=None, refine=True):
+    def flow(self, other, name, radius_voxels=2, max_cost=None, iso=0.0, sites=None, other_sites=None, refine=True, seed=None):
         """How did it move?  For every member voxel of this field the voxel of `other` -- a field on the same grid -- within Chebyshev distance
         radius_voxels whose stored row of `name` is closest in L2 (d3f_volume_flow, csrc/flow_kernels.hip) -> Flow.
 
@@ -995,6 +1023,10 @@ class BakedField:
         max_cost       None, or a distance between rows >= 0: a candidate takes part only if its squared distance is <= float32(max_cost)^2
         iso, sites     this field's members, as links() takes them; other_sites: the other field's (None: its own valid & (dist <= iso))
         refine         also the costs of the target's six axis neighbours, and from them the sub-voxel `offset`
+        seed           None, or an int32 [nx, ny, nz, 3] tensor on the device (Flow.seed of a coarser flow): the window of every member is centred
+                       on voxel + seed instead of the voxel (d3f_volume_flow_seeded, csrc/flow_seeded_kernels.hip); ties
+                       go to the candidate nearest that centre; a member whose seed leaves [-16384, 16384] stays unmatched.  A zero seed gives
+                       the bytes of seed=None
         Members are the sites that are valid and, on a banded field, stored.  The costs are float32 sums in ascending channel order; ties go
         to the nearer candidate, then to the lower flat index: the same bytes on every run.  Not differentiable."""
         if not isinstance(other, BakedField):
@@ -1015,6 +1047,13 @@ class BakedField:
             raise ValueError("flow: the other field is on %s, this one on %s" % (other.device, self.device))
         if isinstance(radius_voxels, bool) or not isinstance(radius_voxels, int) or not 1 <= radius_voxels <= _lib.FLOW_MAX_RADIUS:
             raise ValueError("flow: radius_voxels must be an integer in 1..%d, got %r" % (_lib.FLOW_MAX_RADIUS, radius_voxels))
+        if seed is not None:
+            if not isinstance(seed, torch.Tensor):
+                raise TypeError("flow: seed must be None or an int32 tensor, got %s" % type(seed).__name__)
+            if seed.dtype != torch.int32 or tuple(seed.shape) != tuple(self.grid_shape) + (3,):
+                raise ValueError("flow: seed must be an int32 tensor of shape %s, got %s %s" % (tuple(self.grid_shape) + (3,), seed.dtype, tuple(seed.shape)))
+            if seed.device != self.device:
+                raise ValueError("flow: seed is on %s, the field on %s" % (seed.device, self.device))
         max_cost2 = math.inf
         if max_cost is not None:
             max_cost = float(max_cost)
@@ -1038,8 +1077,131 @@ class BakedField:
         site_a, site_b = members_a.contiguous().view(torch.uint8), members_b.contiguous().view(torch.uint8)
         set_a, set_b = self._set_array([name]), other._set_array([name])
         with self._on() as q:
-            q.d3f_volume_flow(site_a, self.slot, set_a, site_b, other.slot, set_b, nx, ny, nz, radius_voxels, max_cost2, target, cost, axis)
+            if seed is None:
+                q.d3f_volume_flow(site_a, self.slot, set_a, site_b, other.slot, set_b, nx, ny, nz, radius_voxels, max_cost2, target, cost, axis)
+            else:
+                seed = seed.detach().contiguous()
+                q.d3f_volume_flow_seeded(_lib.FlowSeeded(_lib.ptr(site_a), _lib.ptr(self.slot), set_a, _lib.ptr(site_b), _lib.ptr(other.slot), set_b, _lib.ptr(seed),
+                                                         nx, ny, nz, radius_voxels, max_cost2, 0, _lib.ptr(target), _lib.ptr(cost), _lib.ptr(axis)))
         return Flow(self.origin, self.step, target, cost, axis)
+
+    # ---- the pyramid ----------------------------------------------------------------------------------------------------------
+    def coarsen(self, min_children=1, band=None, return_names=None):
+        """This field at half the resolution (d3f_volume_coarsen_select / d3f_volume_coarsen_rows, csrc/pyramid_kernels.hip, declared by
+        include/d3fields_hip_pyramid.h) -> a new BakedField of ceil(n / 2) voxels per axis with step 2 * step and
+        origin + step / 2.  Coarse voxel (X, Y, Z) has the children (2X + i, 2Y + j, 2Z + k), i, j, k in {0, 1}, inside this grid.
+
+        min_children  1..8: the coarse voxel is valid iff at least that many children are valid with a dist that is no NaN; its dist is their
+                      float32 mean (summed in ascending flat index, times 1 / count), 1e3 elsewhere
+        band          None: the result is dense iff this field is dense, else banded with self.band; a world length: banded with it
+        return_names  the sets of the result (None: all)
+        Rows: the float32 mean of the rows of the children that count and, on a banded field, are stored; none -> the fill row and
+        rows_known False.  Half rows are widened exactly; the result is float32 (half() it).  The result also has `children` (uint8 masks)
+        and rows_known.  A banded result goes select, d3f_band_mark on the coarse dist, the rows of the stored coarse voxels only: no dense
+        coarse row array exists at any time.  Every extent must be at least 3.  No host read on the dense path, the one of d3f_band_mark
+        on the banded one.  Not differentiable.  travel / components / locate / clearance accept the result as any field: a cheap first pass."""
+        if isinstance(min_children, bool) or not isinstance(min_children, int):
+            raise TypeError("coarsen: min_children must be an integer, got %s" % type(min_children).__name__)
+        if not 1 <= min_children <= 8:
+            raise ValueError("coarsen: min_children must lie in 1..8, got %r" % (min_children,))
+        names = self._names(return_names)
+        if band is not None:
+            band = _check_band(band, "coarsen")
+        elif self.band is not None:
+            band = self.band
+        if band is not None:
+            _check_band_names(names)
+        nx, ny, nz = self.grid_shape
+        if min(nx, ny, nz) < 3:
+            raise ValueError("coarsen: every extent must be at least 3 (a field needs 2 voxels per axis), this grid is %s" % (tuple(self.grid_shape),))
+        dev = self.device
+        if dev.type != "cuda":
+            raise RuntimeError("coarsen: the field must live on the ROCm device; there is no CPU path")
+        cx, cy, cz = (nx + 1) // 2, (ny + 1) // 2, (nz + 1) // 2
+        nc = cx * cy * cz
+        dist = torch.empty((cx, cy, cz), dtype=torch.float32, device=dev)
+        valid = torch.empty((cx, cy, cz), dtype=torch.uint8, device=dev)
+        children = torch.empty((cx, cy, cz), dtype=torch.uint8, device=dev)
+        sel = _lib.CoarsenSelect(nx, ny, nz, min_children, _lib.ptr(self.dist), _lib.ptr(self.valid), _lib.ptr(dist), _lib.ptr(valid), _lib.ptr(children), 0)
+        with self._on() as q:
+            q.d3f_volume_coarsen_select(sel)
+        origin = tuple(o + self.step / 2 for o in self.origin)
+        coarse = type(self)(origin, 2.0 * self.step, dist, valid.view(torch.bool), {}, {})
+        if band is None:
+            mark, voxels, m = None, None, nc
+        else:
+            mark = coarse._mark(band)
+            voxels, m = mark[2], mark[2].shape[0]
+        known = torch.empty(m, dtype=torch.uint8, device=dev)
+        rows = {k: torch.empty((m, self._channels(k)), dtype=torch.float32, device=dev) for k in names}
+        if m > 0:
+            outs = (ctypes.c_void_p * max(len(names), 1))(*[rows[k].data_ptr() for k in names])
+            src = None if self.band is None else self._band_struct()
+            args = _lib.CoarsenRows(nx, ny, nz, len(names), None if src is None else ctypes.pointer(src), self._set_array(names), _lib.ptr(children), _lib.ptr(voxels),
+                                    m, outs, _lib.ptr(known), 0)
+            with self._on() as q:
+                q.d3f_volume_coarsen_rows(args)
+        fills = {k: self._fills[k] for k in names}
+        if band is None:
+            coarse._sets, coarse._fills = {k: rows[k].view(cx, cy, cz, -1) for k in names}, fills
+            coarse.rows_known = known.view(torch.bool).view(cx, cy, cz)
+        else:
+            coarse = coarse._banded(band, mark, rows, fills)
+            coarse.rows_known = known.view(torch.bool)
+        coarse.children = children
+        return coarse
+
+    def _max_levels(self):
+        """how often this grid halves before an extent drops below 2"""
+        e, levels = min(self.grid_shape), 0
+        while e >= 3:
+            e, levels = (e + 1) // 2, levels + 1
+        return levels
+
+    def pyramid(self, levels, **kw):
+        """[self, coarsen(**kw), its coarsen(**kw), ...]: `levels` coarser fields behind this one, each at half the resolution of the one before"""
+        if isinstance(levels, bool) or not isinstance(levels, int):
+            raise TypeError("pyramid: levels must be an integer, got %s" % type(levels).__name__)
+        if levels < 0 or levels > self._max_levels():
+            raise ValueError("pyramid: levels = %r, the grid %s allows 0..%d (every level needs extents of at least 2)" % (
+                levels, tuple(self.grid_shape), self._max_levels()))
+        out = [self]
+        for _ in range(levels):
+            out.append(out[-1].coarsen(**kw))
+        return out
+
+    def flow_pyramid(self, other, name, levels=2, radius_voxels=2, fine_radius_voxels=1, min_children=1, refine=True, **flow_kw):
+        """How far did it move?  Coarse-to-fine flow over the pyramids of both fields (DESIGN.md section 31) -> the Flow of the finest level;
+        its `coarse` lists the flows of the coarser levels, coarsest first.  The coarsest level runs flow() at radius_voxels; every finer
+        level runs flow(seed=) at fine_radius_voxels round the prediction Flow.seed makes from the level above.  Reach: about radius_voxels *
+        2**levels voxels of this grid, where flow() alone ends at 4.  flow_kw (max_cost, iso) goes to every level; sites / other_sites
+        belong to one grid and are refused.  consistent, displacement and motions work on the result as on any Flow."""
+        if not isinstance(other, BakedField):
+            raise ValueError("flow_pyramid: other must be a BakedField, got %r" % (type(other).__name__,))
+        if isinstance(levels, bool) or not isinstance(levels, int):
+            raise TypeError("flow_pyramid: levels must be an integer, got %s" % type(levels).__name__)
+        for what, rv in (("radius_voxels", radius_voxels), ("fine_radius_voxels", fine_radius_voxels)):
+            if isinstance(rv, bool) or not isinstance(rv, int) or not 1 <= rv <= _lib.FLOW_MAX_RADIUS:
+                raise ValueError("flow_pyramid: %s must be an integer in 1..%d, got %r" % (what, _lib.FLOW_MAX_RADIUS, rv))
+        for k in flow_kw:
+            if k not in ("max_cost", "iso"):
+                raise TypeError("flow_pyramid: unexpected argument %r (max_cost and iso go to every level)" % (k,))
+        if tuple(self.grid_shape) != tuple(other.grid_shape) or self.origin != other.origin or self.step != other.step:
+            raise ValueError("flow_pyramid: the fields must share one grid: %s at %s step %g here, %s at %s step %g there" % (
+                tuple(self.grid_shape), self.origin, self.step, tuple(other.grid_shape), other.origin, other.step))
+        for f, who in ((self, "this field"), (other, "the other field")):
+            if name not in f._sets:
+                raise ValueError("flow_pyramid: %r was not baked in %s, which holds %s" % (name, who, f.names()))
+        self._need_float_rows("flow_pyramid", [name])
+        other._need_float_rows("flow_pyramid (the other field)", [name])
+        mine = self.pyramid(levels, min_children=min_children, return_names=[name])
+        theirs = other.pyramid(levels, min_children=min_children, return_names=[name])
+        flows = [mine[-1].flow(theirs[-1], name, radius_voxels=radius_voxels, refine=refine, **flow_kw)]
+        for a, b in zip(mine[-2::-1], theirs[-2::-1]):
+            flows.append(a.flow(b, name, radius_voxels=fine_radius_voxels, refine=refine, seed=flows[-1].seed(a.grid_shape, refined=refine), **flow_kw))
+        out = flows[-1]
+        out.coarse = flows[:-1]
+        return out
 
     # ---- warp -----------------------------------------------------------------------------------------------------------------
     def _check_label_volume(self, who, what, t):

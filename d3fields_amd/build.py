@@ -14,8 +14,8 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 INCLUDE = os.path.join(os.path.dirname(PKG_DIR), "include")
 LIB_PATH = os.path.join(PKG_DIR, "libd3fields_hip.so")
-PUBLIC_HEADERS = ["d3fields_hip.h", "d3fields_hip_ext.h"]      # the main table of the C ABI, and the entry points added after it
-SOURCES = ["fuse_launch.hip", "fuse_direct.hip", "fuse_runs.hip", "fuse_sliced.hip", "fuse_window.hip", "fuse_rows.hip", "fuse_backward.hip", "scan_kernels.hip", "order_kernels.hip", "grid_kernels.hip", "mesh_kernels.hip", "volume_kernels.hip", "band_kernels.hip", "edt_kernels.hip", "ccl_kernels.hip", "parts_kernels.hip", "flow_kernels.hip", "pool_kernels.hip", "motion_kernels.hip", "warp_kernels.hip", "merge_kernels.hip", "geodesic_kernels.hip", "segment_kernels.hip", "peaks_kernels.hip", "align_kernels.hip", "consensus_kernels.hip", "raycast_kernels.hip", "pcd_kernels.hip", "assoc_kernels.hip", "misc_kernels.hip", "proj_kernels.hip", "moment_kernels.hip", "corr_kernels.hip", "track_kernels.hip", "d3f_api.hip"]
+PUBLIC_HEADERS = ["d3fields_hip.h", "d3fields_hip_ext.h", "d3fields_hip_pyramid.h"]      # the main table of the C ABI, the entry points added after it, a header per later feature
+SOURCES = ["fuse_launch.hip", "fuse_direct.hip", "fuse_runs.hip", "fuse_sliced.hip", "fuse_window.hip", "fuse_rows.hip", "fuse_backward.hip", "scan_kernels.hip", "order_kernels.hip", "grid_kernels.hip", "mesh_kernels.hip", "volume_kernels.hip", "band_kernels.hip", "edt_kernels.hip", "ccl_kernels.hip", "parts_kernels.hip", "flow_kernels.hip", "flow_seeded_kernels.hip", "pyramid_kernels.hip", "pool_kernels.hip", "motion_kernels.hip", "warp_kernels.hip", "merge_kernels.hip", "geodesic_kernels.hip", "segment_kernels.hip", "peaks_kernels.hip", "align_kernels.hip", "consensus_kernels.hip", "raycast_kernels.hip", "pcd_kernels.hip", "assoc_kernels.hip", "misc_kernels.hip", "proj_kernels.hip", "moment_kernels.hip", "corr_kernels.hip", "track_kernels.hip", "d3f_api.hip"]
 
 # -ffp-contract=off: the arithmetic contract says which products are fused; only
 # explicit fmaf() may fuse.  No -ffast-math: IEEE division and accurate expf are part of parity.

@@ -9,6 +9,7 @@
 
 #include "d3f_internal.h"
 #include "d3fields_hip_ext.h"      // the entry points added after the main table of ABI 16
+#include "d3fields_hip_pyramid.h"  // ... and the pyramid's, a header per feature from here on
 
 namespace {
 
@@ -1333,6 +1334,131 @@ int d3f_volume_merge_rows(const d3f_merge_rows *args, void *stream)
     A.out_known = args->out_known;
     hipError_t e = d3f::launch_merge_rows(A, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_merge_rows launch");
+}
+
+// ---- a baked field at half the resolution (pyramid_kernels.hip; declared by include/d3fields_hip_pyramid.h) ----
+int d3f_volume_coarsen_select(const d3f_coarsen_select *args, void *stream)
+{
+    const char *who = "volume_coarsen_select";
+    if (!args) return fail(D3F_ERR_INVALID_ARG, "%s: args is NULL", who);
+    if (const int rc = check_extents(who, args->nx, args->ny, args->nz)) return rc;
+    if (args->min_children < 1 || args->min_children > 8) return fail(D3F_ERR_INVALID_ARG, "%s: min_children=%d outside [1,8]", who, args->min_children);
+    if (args->reserved != 0) return fail(D3F_ERR_INVALID_ARG, "%s: reserved=%lld, must be 0", who, (long long)args->reserved);
+    if (!args->dist || !args->valid) return fail(D3F_ERR_INVALID_ARG, "%s: dist / valid must be non-NULL", who);
+    if (!args->out_dist || !args->out_valid || !args->out_children) return fail(D3F_ERR_INVALID_ARG, "%s: out_dist / out_valid / out_children must be non-NULL", who);
+    if (!aligned(args->dist, 4) || !aligned(args->out_dist, 4)) return fail(D3F_ERR_BAD_LAYOUT, "%s: dist / out_dist must be aligned to their element size", who);
+    d3f::CoarsenSelectArgs A;
+    A.dist = args->dist;
+    A.valid = args->valid;
+    A.nx = args->nx; A.ny = args->ny; A.nz = args->nz;
+    A.cy = (args->ny + 1) / 2;
+    A.cz = (args->nz + 1) / 2;
+    A.min_children = args->min_children;
+    A.nc = (int64_t)((args->nx + 1) / 2) * A.cy * A.cz;
+    A.out_dist = args->out_dist;
+    A.out_valid = args->out_valid;
+    A.out_children = args->out_children;
+    hipError_t e = d3f::launch_coarsen_select(A, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_coarsen_select launch");
+}
+
+int d3f_volume_coarsen_rows(const d3f_coarsen_rows *args, void *stream)
+{
+    const char *who = "volume_coarsen_rows";
+    if (!args) return fail(D3F_ERR_INVALID_ARG, "%s: args is NULL", who);
+    if (const int rc = check_extents(who, args->nx, args->ny, args->nz)) return rc;
+    const d3f_band *band = args->band;
+    if (band && (band->n_rows < 0 || band->n_rows > 0x7fffffffLL))
+        return fail(D3F_ERR_BAD_SHAPE, "%s: band->n_rows=%lld outside [0, 2^31 - 1]", who, (long long)band->n_rows);
+    const int32_t n_sets = args->n_sets;
+    if (n_sets < 0 || n_sets > D3F_MAX_MAPS) return fail(D3F_ERR_BAD_SHAPE, "%s: n_sets=%d outside [0,%d]", who, n_sets, D3F_MAX_MAPS);
+    if (n_sets > 0 && !args->sets) return fail(D3F_ERR_INVALID_ARG, "%s: sets is NULL with n_sets=%d", who, n_sets);
+    for (int s = 0; s < n_sets; ++s) {
+        if (const int rc = check_set_shape(who, s, args->sets[s])) return rc;
+        if (const int rc = check_set_storage(who, s, args->sets[s], true)) return rc;
+    }
+    const int32_t cy = (args->ny + 1) / 2, cz = (args->nz + 1) / 2;
+    const int64_t nc = (int64_t)((args->nx + 1) / 2) * cy * cz;
+    if (args->reserved != 0) return fail(D3F_ERR_INVALID_ARG, "%s: reserved=%lld, must be 0", who, (long long)args->reserved);
+    if (args->m < 0) return fail(D3F_ERR_INVALID_ARG, "%s: m=%lld is negative", who, (long long)args->m);
+    if (!args->voxels && args->m != nc)
+        return fail(D3F_ERR_INVALID_ARG, "%s: m=%lld with voxels NULL, must be the coarse voxel count %lld", who, (long long)args->m, (long long)nc);
+    if (args->m == 0) return D3F_OK;
+    const bool empty = band && band->n_rows == 0;
+    if (!args->children || !args->out_known || (n_sets > 0 && !args->out_sets)) return fail(D3F_ERR_INVALID_ARG, "%s: children / out_known / out_sets must be non-NULL", who);
+    if (band && !empty && !band->slot) return fail(D3F_ERR_INVALID_ARG, "%s: band->slot must be non-NULL with n_rows > 0", who);
+    if (!aligned(args->voxels, 4) || (band && !empty && !aligned(band->slot, 4)))
+        return fail(D3F_ERR_BAD_LAYOUT, "%s: voxels / band->slot must be aligned to their element size", who);
+    d3f::CoarsenRowsArgs A;
+    for (int s = 0; s < n_sets; ++s) {
+        const d3f_volume_set &set = args->sets[s];
+        if (!set.data && !empty) return fail(D3F_ERR_INVALID_ARG, "%s: set %d: data is NULL", who, s);
+        if (const int rc = check_set_layout(who, s, set)) return rc;
+        if (!aligned(set.fill, 4)) return fail(D3F_ERR_BAD_LAYOUT, "%s: set %d: fill must be 4-byte aligned", who, s);
+        if (!args->out_sets[s]) return fail(D3F_ERR_INVALID_ARG, "%s: out_sets[%d] is NULL", who, s);
+        if (!aligned(args->out_sets[s], 4)) return fail(D3F_ERR_BAD_LAYOUT, "%s: out_sets[%d] must be 4-byte aligned", who, s);
+        d3f::CoarsenSet &S = A.sets[s];
+        S.data = set.data;
+        S.fill = set.fill;
+        S.out = static_cast<float *>(args->out_sets[s]);
+        S.stride = set.stride_voxel;
+        S.C = set.C;
+        S.vec = set_reads_vectors(set) && aligned(args->out_sets[s], 16) ? 1 : 0;
+        S.f16 = set_is_half(set) ? 1 : 0;
+    }
+    A.children = args->children;
+    A.voxels = args->voxels;
+    A.slot = band && !empty ? band->slot : nullptr;
+    A.banded = band != nullptr;
+    A.m = args->m;
+    A.nc = nc;
+    A.nx = args->nx; A.ny = args->ny; A.nz = args->nz; A.cy = cy; A.cz = cz;
+    A.n_sets = n_sets;
+    A.out_known = args->out_known;
+    hipError_t e = d3f::launch_coarsen_rows(A, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_coarsen_rows launch");
+}
+
+// ---- the flow with a per-voxel seed (flow_seeded_kernels.hip; declared by include/d3fields_hip_pyramid.h): d3f_volume_flow's checks in its order ----
+int d3f_volume_flow_seeded(const d3f_flow_seeded *args, void *stream)
+{
+    const char *who = "volume_flow_seeded";
+    if (!args) return fail(D3F_ERR_INVALID_ARG, "%s: args is NULL", who);
+    const d3f_volume_set *set_a = args->set_a, *set_b = args->set_b;
+    if (!args->site_a || !args->site_b || !set_a || !set_b) return fail(D3F_ERR_INVALID_ARG, "%s: site_a, site_b, set_a or set_b is NULL", who);
+    if (!set_a->data || !set_b->data) return fail(D3F_ERR_INVALID_ARG, "%s: set_a->data or set_b->data is NULL", who);
+    if (!args->out_target || !args->out_cost) return fail(D3F_ERR_INVALID_ARG, "%s: out_target or out_cost is NULL", who);
+    if (args->radius < 1 || args->radius > D3F_FLOW_MAX_RADIUS) return fail(D3F_ERR_INVALID_ARG, "%s: radius=%d outside [1,%d]", who, args->radius, D3F_FLOW_MAX_RADIUS);
+    if (args->max_cost2 != args->max_cost2) return fail(D3F_ERR_INVALID_ARG, "%s: max_cost2 is NaN (+Inf means no threshold)", who);
+    if (args->reserved != 0) return fail(D3F_ERR_INVALID_ARG, "%s: reserved=%d, must be 0", who, args->reserved);
+    if (const int rc = check_extents(who, args->nx, args->ny, args->nz)) return rc;
+    if (const int rc = check_set_shape(who, 0, *set_a)) return rc;             // set 0: set_a, set 1: set_b
+    if (set_b->C != set_a->C) return fail(D3F_ERR_BAD_SHAPE, "%s: C=%d of set_a, C=%d of set_b: the sets must have the same width", who, set_a->C, set_b->C);
+    if (const int rc = check_set_storage(who, 0, *set_a, false)) return rc;
+    if (const int rc = check_set_storage(who, 1, *set_b, false)) return rc;
+    if (const int rc = check_set_layout(who, 0, *set_a)) return rc;
+    if (const int rc = check_set_layout(who, 1, *set_b)) return rc;
+    if (!aligned(args->slot_a, 4) || !aligned(args->slot_b, 4) || !aligned(args->seed, 4) || !aligned(args->out_target, 4) || !aligned(args->out_cost, 4) ||
+        !aligned(args->out_axis_cost, 4))
+        return fail(D3F_ERR_BAD_LAYOUT, "%s: slots, seed and outputs must be 4-byte aligned", who);
+    d3f::FlowSeededArgs A;
+    A.site_a = args->site_a; A.site_b = args->site_b;
+    A.slot_a = args->slot_a; A.slot_b = args->slot_b;
+    A.data_a = static_cast<const float *>(set_a->data); A.data_b = static_cast<const float *>(set_b->data);
+    A.stride_a = set_a->stride_voxel; A.stride_b = set_b->stride_voxel;
+    A.seed = args->seed;
+    A.target = args->out_target;
+    A.cost = args->out_cost;
+    A.nx = args->nx; A.ny = args->ny; A.nz = args->nz;
+    A.C = set_a->C;
+    A.r = args->radius;
+    A.vec = set_reads_vectors(*set_a) && set_reads_vectors(*set_b) ? 1 : 0;
+    A.max_cost2 = args->max_cost2;
+    hipError_t e = d3f::launch_flow_seeded(A, static_cast<hipStream_t>(stream));
+    if (e == hipSuccess && args->out_axis_cost)
+        e = d3f::launch_flow_axis(A.slot_a, A.data_a, A.stride_a, A.site_b, A.slot_b, A.data_b, A.stride_b, A.C, A.nx, A.ny, A.nz, A.target, args->out_axis_cost,
+                                  static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? D3F_OK : hip_fail(e, "volume_flow_seeded launch");
 }
 
 // ---- cost-to-go through free space (geodesic_kernels.hip) ----

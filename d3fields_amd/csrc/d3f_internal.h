@@ -272,6 +272,56 @@ hipError_t launch_volume_links(const uint8_t *site, const uint8_t *valid, const 
 hipError_t launch_volume_flow(const uint8_t *site_a, const int32_t *slot_a, const float *data_a, int64_t stride_a, const uint8_t *site_b, const int32_t *slot_b,
                               const float *data_b, int64_t stride_b, int C, bool vec, int nx, int ny, int nz, int radius, float max_cost2, int32_t *out_target,
                               float *out_cost, float *out_axis_cost, hipStream_t s);
+// ... its axis-cost pass alone (flow_axis_kernel), from targets already written: shared with the seeded flow, whose rule is the same
+hipError_t launch_flow_axis(const int32_t *slot_a, const float *data_a, int64_t stride_a, const uint8_t *site_b, const int32_t *slot_b, const float *data_b,
+                            int64_t stride_b, int C, int nx, int ny, int nz, const int32_t *target, float *out_axis_cost, hipStream_t s);
+
+// flow_seeded_kernels.hip: the flow with every member's window centred on a per-voxel seed (include/d3fields_hip_pyramid.h)
+struct FlowSeededArgs {
+    const uint8_t *site_a, *site_b;
+    const int32_t *slot_a, *slot_b;
+    const float *data_a, *data_b;
+    int64_t stride_a, stride_b;
+    const int32_t *seed;         // [n, 3] or nullptr: zeros
+    int32_t *target;
+    float *cost;
+    int32_t nx, ny, nz, C, r;
+    int32_t vec;                 // 1: the rows of both sets move as 16-byte vectors
+    float max_cost2;
+};
+hipError_t launch_flow_seeded(const FlowSeededArgs &A, hipStream_t s);
+
+// pyramid_kernels.hip: a baked field at half the resolution (include/d3fields_hip_pyramid.h)
+struct CoarsenSelectArgs {
+    const float *dist;
+    const uint8_t *valid;
+    int32_t nx, ny, nz, cy, cz, min_children;
+    int64_t nc;                  // coarse voxels
+    float *out_dist;
+    uint8_t *out_valid, *out_children;
+};
+struct CoarsenSet {
+    const void *data;            // the fine rows: floats or halves (f16)
+    const float *fill;           // or nullptr (zeros)
+    float *out;                  // [m, C]
+    int64_t stride;              // in elements
+    int32_t C;
+    int32_t vec;                 // 1: the rows and the output row move as 16-byte vectors
+    int32_t f16;
+};
+struct CoarsenRowsArgs {
+    const uint8_t *children;
+    const int32_t *voxels;       // or nullptr: every coarse voxel in flat order
+    const int32_t *slot;         // a banded source: nullptr with no stored voxel
+    bool banded;
+    int64_t m, nc;
+    int32_t nx, ny, nz, cy, cz;
+    int32_t n_sets;
+    CoarsenSet sets[D3F_MAX_MAPS];
+    uint8_t *out_known;
+};
+hipError_t launch_coarsen_select(const CoarsenSelectArgs &A, hipStream_t s);
+hipError_t launch_coarsen_rows(const CoarsenRowsArgs &A, hipStream_t s);
 
 // pool_kernels.hip: mean rows, votes and moments of the baked field per component
 struct PoolArgs {

@@ -269,4 +269,16 @@ hipError_t launch_volume_flow(const uint8_t *site_a, const int32_t *slot_a, cons
     return hipGetLastError();
 }
 
+// the axis pass alone, over targets that another kernel wrote (the seeded flow: flow_seeded_kernels.hip); flow_axis_kernel reads nothing else of A
+// than slot and rows
+hipError_t launch_flow_axis(const int32_t *slot_a, const float *data_a, int64_t stride_a, const uint8_t *site_b, const int32_t *slot_b, const float *data_b,
+                            int64_t stride_b, int C, int nx, int ny, int nz, const int32_t *target, float *out_axis_cost, hipStream_t s)
+{
+    FlowArgs a{nullptr, site_b, slot_a, slot_b, data_a, data_b, stride_a, stride_b, const_cast<int32_t *>(target), nullptr, out_axis_cost, nx, ny, nz, C, 0, 0, 0,
+               0.0f};
+    const int32_t n = nx * ny * nz;
+    hipLaunchKernelGGL(flow_axis_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, a, n);
+    return hipGetLastError();
+}
+
 }  // namespace d3f
